@@ -30,6 +30,7 @@ sys.path.insert(0, ROOT)
 
 PEAK_TFLOPS = {"bf16": 2500.0, "fp32": 157.3}      # dense MFMA peaks, MI355X_MICROARCH.md
 PMC_FILE = "r06_pmc_rollout.json"                    # HBM counters of the dominant kernel (separate --pmc passes, committed)
+DUMP_BYTES, DUMP_SEED = 48 << 20, 20240                # --dump-outputs: bytes of array data in all, seed of the sampled positions
 
 
 def _sha16(path):
@@ -56,7 +57,40 @@ def parse():
     p.add_argument("--no-workloads", action="store_true", help="skip the compact cfg2 B=1 / cfg4 / cfg5 legs (the `workloads` object)")
     p.add_argument("--reps", type=int, default=7, help="the timed region of exactly --steps steps is repeated this many times behind a >= 0.5 s "
                                                        "ramp; `value` / `ms_per_step` are the MEDIAN region (min / max / reps in config.timing)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the headline leg's last timed step returned as DIR/<name>.npy (rank 0; fp32, fp64 "
+                        "stays fp64): the whole array when it fits its share of %d MiB, else a fixed seeded sample of its flattened elements "
+                        "(the same positions in every run with the same arguments), so that two builds can be compared output for output"
+                        % (DUMP_BYTES >> 20))
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(result, names, out_dir):
+    """Write each tensor of `result` (one tensor or a tuple) as out_dir/<name>.npy.  An array larger than its share of DUMP_BYTES is
+    reduced to the elements at DUMP_SEED's sorted random flat positions (a 1-D array; they depend only on the element count and the
+    share).  -> {name: (shape of the full output, number of elements written)}"""
+    import numpy as np
+    ts = (result,) if isinstance(result, torch.Tensor) else tuple(result)
+    names = list(names) if len(names) == len(ts) else [f"out{i}" for i in range(len(ts))]
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, t in zip(names, ts):
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        cap = (DUMP_BYTES // len(ts)) // (8 if dt == torch.float64 else 4)
+        flat = t.reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), cap, replace=False))
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+            arr = flat.to(dt).cpu().numpy()
+        else:
+            arr = t.to(dt).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        info[name] = (list(t.shape), int(arr.size))
+    return info
 
 
 def visible_gpus():
@@ -288,10 +322,11 @@ def cvit_cpu_leg(lg, gpu_frames_per_s):
             "gpu_over_cpu": round(gpu_frames_per_s / fps, 1)}
 
 
-def rollout_leg(config, batch_arg, dtype_arg, steps, warmup, dev, rank, world, dist, want_roofline, graph=False, reps=1):
+def rollout_leg(config, batch_arg, dtype_arg, steps, warmup, dev, rank, world, dist, want_roofline, graph=False, reps=1, dump_dir=None):
     """One timed leg: `steps` rollouts (CViT: model calls) of `config` at per-GPU batch `batch_arg` (None: workload.batch_size), barrier +
     synchronize on both sides, MAX over ranks; then (rank 0) the instrumented pass for the roofline entry.  graph=True replays the whole
-    rollout as ONE captured HIP graph (B = 1: the 100-odd launches of a rollout are issue-bound on the host)."""
+    rollout as ONE captured HIP graph (B = 1: the 100-odd launches of a rollout are issue-bound on the host).  dump_dir: write what the
+    last timed step returned there (dump_outputs)."""
     class _A:      # the names the body below was written against
         pass
     args = _A()
@@ -324,16 +359,14 @@ def rollout_leg(config, batch_arg, dtype_arg, steps, warmup, dev, rank, world, d
 
     x_cvit = fmt.process_input(batch)[0][0].to(dev) if kind == "cvit" else None
 
-    def step():
+    def step():      # -> what a caller of the timed path receives: CViT's prediction, a rollout's (y_pred, y_ref)
         with torch.inference_mode():
             if kind == "cvit":
                 return model(x_cvit)
             if kind == "fno":
                 with amp():
-                    y, _ = tante_amd.rollout_model(model, batch, fmt, n_steps, device=dev)
-                return y
-            y, _ = tante_amd.rollout_model(model, batch, fmt, n_steps, device=dev)
-        return y
+                    return tante_amd.rollout_model(model, batch, fmt, n_steps, device=dev)
+            return tante_amd.rollout_model(model, batch, fmt, n_steps, device=dev)
 
     # graph: False = the eager loop, True = tante_amd.GraphedRollout (one captured HIP graph per rollout), "auto" = decided in the warm-up:
     # the eager loop unless the captured rollout is clearly (> 2 %) faster -- small batches and busy hosts, where the host's ~100 launches
@@ -347,7 +380,7 @@ def rollout_leg(config, batch_arg, dtype_arg, steps, warmup, dev, rank, world, d
                 roll = tante_amd.GraphedRollout(model, batch, fmt, n_steps, device=dev)
 
                 def graph_step():
-                    return roll(batch)[0]
+                    return roll(batch)
             else:
                 side = torch.cuda.Stream(device=dev)
                 side.wait_stream(torch.cuda.current_stream(dev))
@@ -387,11 +420,21 @@ def rollout_leg(config, batch_arg, dtype_arg, steps, warmup, dev, rank, world, d
             dist.barrier()
             torch.cuda.synchronize()
 
+    last = [None]
+    if dump_dir is not None:      # keep each step's result (from the warm-up on, so the allocator holds both generations before timing)
+        run_step = step
+
+        def step():
+            last[0] = run_step()
     for _ in range(args.warmup):
         step()
     clk0 = shader_clock_mhz(dev.index or 0)
     elapsed, regions, n_ramp = timed_regions(step, args.steps, reps, sync, dist, dev, ramp_s=0.5 if reps > 1 else 0.0)
     clk1 = shader_clock_mhz(dev.index or 0)
+    dumped = None
+    if dump_dir is not None:      # the last timed step's result, read before anything else runs (graph outputs are overwritten by a replay)
+        dumped = dump_outputs(last[0], ("y",) if kind == "cvit" else ("y_pred", "y_ref"), dump_dir)
+        last[0] = None
     frames = B * n_steps * args.steps * world
     value = frames / elapsed
     timing = {"reps": len(regions), "statistic": "median region" if len(regions) > 1 else "single region", "ramp_steps_untimed": n_ramp,
@@ -519,7 +562,7 @@ def rollout_leg(config, batch_arg, dtype_arg, steps, warmup, dev, rank, world, d
                                                  "are rebuilt when a weight changes"}
 
     return {"value": value, "elapsed": elapsed, "roofline": roofline, "model": model, "batch": batch, "cfg": cfg, "wl": wl, "kind": kind, "B": B,
-            "n_steps": n_steps, "T_in": T_in, "res": res, "D": D, "dtype": dtype, "graph": graph_note, "timing": timing}
+            "n_steps": n_steps, "T_in": T_in, "res": res, "D": D, "dtype": dtype, "graph": graph_note, "timing": timing, "dumped": dumped}
 
 
 def main():
@@ -555,7 +598,11 @@ def main():
 
     leg = rollout_leg(args.config, args.batch, args.dtype, args.steps, args.warmup, dev, rank, world, dist, not args.no_roofline,
                       graph=True if args.graph else (False if (args.no_graph or world > 1) else "auto"),      # (multi-rank runs: eager unless asked)
-                      reps=args.reps)
+                      reps=args.reps, dump_dir=args.dump_outputs if rank == 0 else None)
+    if leg["dumped"] is not None:
+        for name, (shape, n) in leg["dumped"].items():
+            print(f"bench.py: {args.dump_outputs}/{name}.npy: {n} of the {shape} output's elements"
+                  + ("" if n == torch.Size(shape).numel() else f" (sample seeded {DUMP_SEED})"), file=sys.stderr)
     import tante_amd
     from tante_amd import kernels as K
     value, elapsed, roofline, model, batch, cfg, wl, kind = (leg[k] for k in ("value", "elapsed", "roofline", "model", "batch", "cfg", "wl", "kind"))

@@ -126,19 +126,17 @@ def test_configs_and_validation():
         m = tante_amd.build_model(cfg, md)
         if n_params:
             assert sum(p.numel() for p in m.parameters()) == n_params
-    ref_yaml = "/root/reference/configs/tante.yaml"
-    if os.path.exists(ref_yaml):      # the reference's own yaml loads unchanged (build container only)
-        cfg = tante_amd.load_config(ref_yaml)
-        m = tante_amd.build_model(cfg, tante_amd.TanteMetadata(n_fields=11, spatial_resolution=(256, 256)))
+    # the three model configurations the reference ships, through this repository's configs with the same model blocks
+    # (tante_am_order1.yaml = its configs/tante.yaml, cvit_rb.yaml = cvit.yaml, fno_vf.yaml = fno.yaml); its tante.yaml also
+    # carries the spectral keys modes1 / modes2 next to a CNN encoder, which the constructor must accept and ignore
+    am = tante_amd.TanteMetadata(n_fields=11, spatial_resolution=(256, 256))
+    for extra in ({}, {"modes1": 32, "modes2": 32}):
+        m = tante_amd.build_model(tante_amd.load_config(os.path.join(ROOT, "configs", "tante_am_order1.yaml")), am, **extra)
         assert sum(p.numel() for p in m.parameters()) == 4229939
-    # all three model configurations the reference ships build from its own files (build container only)
-    ref_dir = "/root/reference/configs"
-    if os.path.isdir(ref_dir):
-        am = tante_amd.TanteMetadata(n_fields=11, spatial_resolution=(256, 256))
-        kinds = {"tante.yaml": "TANTE", "cvit.yaml": "CViT", "fno.yaml": "FNO"}
-        for name, kind in kinds.items():
-            m = tante_amd.build_model(tante_amd.load_config(os.path.join(ref_dir, name)), am)
-            assert type(m).__name__ == kind, (name, type(m).__name__)
+    kinds = {"tante_am_order1.yaml": "TANTE", "cvit_rb.yaml": "CViT", "fno_vf.yaml": "FNO"}
+    for name, kind in kinds.items():
+        m = tante_amd.build_model(tante_amd.load_config(os.path.join(ROOT, "configs", name)), am)
+        assert type(m).__name__ == kind, (name, type(m).__name__)
     md = tante_amd.TanteMetadata(n_fields=1, spatial_resolution=(16, 16))
     with pytest.raises(ValueError):
         tante_amd.TANTE(in_T=2, dset_metadata=md, taylor_order=2, attn_axes="TH", embed_dim=16, patch_scale=8)

@@ -1,5 +1,6 @@
-import sys, torch
-sys.path.insert(0, "/root/repo/tests"); sys.path.insert(0, "/root/repo")
+import os, sys, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, ROOT)
 import tante_amd
 from conftest import load_golden, split_prefix, rel_err
 dev = torch.device("cuda:0")

@@ -1,5 +1,5 @@
-import sys, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import tante_amd
 from tante_amd import autograd as A, train_forward as TF
 dev = torch.device("cuda:0")
