@@ -529,3 +529,86 @@ def test_split_gradient_allreduce_equals_one_call_gloo_world2():
         assert outs[(1234, 9000)][1] == [1234, 1007, 7766] and outs["none"][1] == [10_007] and outs[(0, 10_007)][1] == [10_007]
         assert outs["plan"][1] == [100, 100, 1007, 1900, 1000, 1000, 4900], outs["plan"][1]
     assert res[0][1] == res[1][1]
+
+
+def test_train_op_references_match_the_oracles():
+    """The float64 references of tests/test_hip_train_ops.py, evaluated in float32, against the CPU oracles (which tests/golden pins to
+    the reference model's own outputs), so a wrong reference cannot let a wrong kernel pass.  Every comparison <= 1e-5 relative L2."""
+    import math
+    import torch.nn.functional as F
+    import test_hip_train_ops as R
+    from oracle import cvit_oracle as CO, spectral_oracle as SO, tante_oracle as TO
+
+    def rel(a, b):
+        return float((a.double() - b.double()).norm() / b.double().norm())
+
+    g = torch.Generator().manual_seed(5)
+    # attention: mha with identity q / k projections and output projection, a random v projection (cvit_oracle.mha)
+    nb, nh, D, Lq, Lk = 2, 3, 8, 37, 29
+    C = nh * D
+    q, kv = torch.randn(nb, Lq, C, generator=g), torch.randn(nb, Lk, C, generator=g)
+    Wv = torch.randn(C, C, generator=g) / math.sqrt(C)
+    eye, zero = torch.eye(C), torch.zeros(C)
+    w = {"attn.in_proj_weight": torch.cat([eye, eye, Wv]), "attn.in_proj_bias": torch.zeros(3 * C), "attn.out_proj.weight": eye,
+         "attn.out_proj.bias": zero}
+    v = TO.linear(kv, Wv, None)
+
+    def heads(t):
+        return t.view(nb, -1, nh, D).transpose(1, 2)
+    got = R.ref_attention(heads(q), heads(kv), heads(v)).transpose(1, 2).reshape(nb, Lq, C)
+    assert rel(got, CO.mha(w, q, kv, nh)) < 1e-5
+    # LayerNorm affine
+    x, ga, be = torch.randn(50, 65, generator=g) + 3.0, torch.randn(65, generator=g), torch.randn(65, generator=g)
+    assert rel(R.ref_layer_norm(x, ga, be, 1e-5), TO.layer_norm(x, ga, be, 1e-5)) < 1e-5
+    # grid embedding: coord_embedding ends in Linear -> LayerNorm; the Linear appends the constants 0 and 1 to the embedding, from which
+    # the LayerNorm's shift and scale are undone exactly: c = (z - z_0) / (z_1 - z_0)
+    for eps, kind in ((40.0, "random"), (1e5, "near")):
+        grid = torch.rand(64, 2, generator=g)
+        coords = R._queries(kind, grid, 33, g)
+        LD = 24
+        lat = torch.randn(64, LD, generator=g)
+        cfg = CO.CvitCfg(4, 1, (8, 8), grid_size=(8, 8), latent_dim=LD, dec_emb_dim=LD + 2, eps=eps)
+        wg = {"grid": grid, "latents": lat, "embedding.0.weight": torch.cat([torch.eye(LD), torch.zeros(2, LD)]),
+              "embedding.0.bias": torch.cat([torch.zeros(LD + 1), torch.ones(1)]), "embedding.1.weight": torch.ones(LD + 2),
+              "embedding.1.bias": torch.zeros(LD + 2)}
+        z = CO.coord_embedding(wg, cfg, coords).double()
+        c_oracle = (z[:, :LD] - z[:, LD:LD + 1]) / (z[:, LD + 1:] - z[:, LD:LD + 1])
+        assert rel(R.ref_grid_embed(coords, grid, lat, eps), c_oracle) < 1e-5, eps
+    # Fourier embedding
+    kern = torch.randn(2, 16, generator=g) * 2 * math.pi
+    coords = torch.rand(40, 2, generator=g)
+    cfg = CO.CvitCfg(4, 1, (8, 8), dec_emb_dim=32, embedding_type="fourier")
+    assert rel(R.ref_fourier_embed(coords, kern), CO.coord_embedding({"embedding.0.kernel": kern}, cfg, coords)) < 1e-5
+    # spectral layer: the test's edge shapes (Nyquist kept, odd sizes and clipped modes, overlapping / coinciding bands, wider weight)
+    for n, Cin, Cout, H, W, m1, m2, wm1, wm2 in R.SPEC_CASES[:5]:
+        x = torch.randn(n, Cin, H, W, generator=g)
+        wre, wim = torch.randn(Cin, Cout, wm1, wm2, generator=g), torch.randn(Cin, Cout, wm1, wm2, generator=g)
+        w0, b0 = torch.randn(Cout, Cin, 1, 1, generator=g), torch.randn(Cout, generator=g)
+        ws = {"weight": torch.complex(wre, wim), "w0.weight": w0, "w0.bias": b0}
+        assert rel(R.ref_spectral_layer(x, wre, wim, w0, b0, m1, m2), SO.spectral_layer(ws, x, m1, m2)) < 1e-5, (H, W, m1, m2)
+    # crop + bilinear resize (both directions, non-integer ratios) against the oracle's F.interpolate restatement
+    full = torch.randn(2, 13, 11, 3, generator=g)
+    for Ho, Wo in ((23, 16), (4, 5)):
+        want = TO._bilinear_resize(full[:, 1:11, 2:9, :].permute(0, 3, 1, 2), Ho, Wo)
+        assert rel(R.ref_crop_resize(full, (1, 2), 10, 7, Ho, Wo, True), want) < 1e-5
+        assert rel(R.ref_crop_resize(full, (1, 2), 10, 7, Ho, Wo, False), want.permute(0, 2, 3, 1)) < 1e-5
+    # im2col: patch matrix x conv weight = RealConv2d (stride P and overlapping stride P/2, both with the oracle's padding and pooling)
+    n, Cin, Cout, H, W, P = 2, 3, 5, 16, 12, 4
+    x = torch.randn(n, Cin, H, W, generator=g)
+    wc, bc = torch.randn(Cout, Cin, P, P, generator=g), torch.randn(Cout, generator=g)
+    for ov in (0.0, 0.5):
+        s, p = TO._stride_pad(P, ov)
+        Ho, Wo = (H + 2 * p - P) // s + 1, (W + 2 * p - P) // s + 1
+        rows = R.ref_im2col(x.permute(0, 2, 3, 1), P, s, p) @ wc.permute(0, 2, 3, 1).reshape(Cout, -1).t() + bc
+        y = TO._adaptive_avg_pool(rows.view(n, Ho, Wo, Cout).permute(0, 3, 1, 2), H // P, W // P)
+        assert rel(y, TO.real_conv2d(x, wc, bc, P, ov)) < 1e-5, ov
+    # col2im: tap matrix (input rows x transposed-conv weight) folded = RealTransConv2d, resized where the oracle resizes
+    xt = torch.randn(n, Cin, 5, 6, generator=g)
+    wt, bt = torch.randn(Cin, Cout, P, P, generator=g), torch.randn(Cout, generator=g)
+    for ov in (0.0, 0.5):
+        s, p = TO._stride_pad(P, ov)
+        taps = xt.permute(0, 2, 3, 1).reshape(-1, Cin) @ wt.permute(0, 2, 3, 1).reshape(Cin, -1)
+        y = R.ref_col2im(taps, bt, n, 5, 6, P, s, p, Cout)
+        if y.shape[1:3] != (5 * P, 6 * P):
+            y = R.ref_crop_resize(y, (0, 0), y.shape[1], y.shape[2], 5 * P, 6 * P, False)
+        assert rel(y.permute(0, 3, 1, 2), TO.real_transconv2d(xt, wt, bt, P, ov)) < 1e-5, ov
