@@ -1575,6 +1575,11 @@ class TaylorFn(Function):
         return (dinp, None, None) + tuple(d.view(B, 1, *ishape[2:]) for d in dds)
 
 
+def _tail_freed(node: str):
+    raise RuntimeError(f"{node}: the fused training tail frees its saved activations in its first backward, so it cannot run backward twice "
+                       "(retain_graph=True); set TANTE_TRAIN_FUSED_TAIL=0 for a graph that is back-propagated more than once")
+
+
 class TailFn(Function):
     """The token-local tail of a rollout call as ONE autograd node, one launch forward and one backward (csrc/tail_chain.hip):
     every order's derivative head (dec_CNN, enc_dec_cnn.py:263-277) -> Taylor sum (tante.py:165-171) -> predicted frame -> its
@@ -1626,6 +1631,8 @@ class TailFn(Function):
     @staticmethod
     def backward(ctx, d_out, d_z):
         cfg, saved, enc = ctx.cfg, ctx.saved, ctx.enc
+        if saved is None:
+            _tail_freed("TailFn")
         B, T, HW, D, Hp, Wp = cfg.B, cfg.T, cfg.HW, cfg.D, cfg.Hp, cfg.Wp
         Tk = B * HW
         n_ord = len(saved)
@@ -1723,6 +1730,8 @@ class EncTailFn(Function):
     @staticmethod
     def backward(ctx, d_z):
         cfg, enc = ctx.cfg, ctx.enc
+        if enc is None:
+            _tail_freed("EncTailFn")
         n_img, Tk = ctx.geo
         D = cfg.D
         dev, bf = d_z.device, torch.bfloat16

@@ -612,3 +612,37 @@ def test_train_op_references_match_the_oracles():
         if y.shape[1:3] != (5 * P, 6 * P):
             y = R.ref_crop_resize(y, (0, 0), y.shape[1], y.shape[2], 5 * P, 6 * P, False)
         assert rel(y.permute(0, 3, 1, 2), TO.real_transconv2d(xt, wt, bt, P, ov)) < 1e-5, ov
+
+
+def test_train_tail_references_match_the_oracles():
+    """The float64 references of tests/test_hip_train_tail.py (decoder, encoder, Taylor sum), evaluated in float32, against the CPU
+    oracles' dec_cnn / enc_cnn (F.conv_transpose2d / F.conv2d, patch scale 8) and taylor_coeff, so a wrong reference cannot let a wrong
+    kernel pass.  Every comparison <= 1e-5 relative L2."""
+    import test_hip_train_tail as R
+    from oracle import tante_oracle as TO
+
+    def rel(a, b):
+        return float((a.double() - b.double()).norm() / b.double().norm())
+
+    g = torch.Generator().manual_seed(6)
+    B, T, Hp, Wp, D = 2, 3, 2, 3, 5
+    dec_shapes = [(256, 128, 2, 2), (128,), (128, 64, 2, 2), (64,), (64, D, 2, 2), (D,)]
+    enc_shapes = [(64, D, 2, 2), (64,), (128, 64, 2, 2), (128,), (256, 128, 2, 2), (256,)]
+    dp = [torch.randn(s, generator=g) / (16.0 if len(s) > 1 else 1.0) for s in dec_shapes]
+    ep = [torch.randn(s, generator=g) / (8.0 if len(s) > 1 else 1.0) for s in enc_shapes]
+    wd = {f"dec_conv_{i // 2 + 1}.deconv.{'weight' if i % 2 == 0 else 'bias'}": p for i, p in enumerate(dp)}
+    we = {f"enc_conv_{i // 2 + 1}.conv.{'weight' if i % 2 == 0 else 'bias'}": p for i, p in enumerate(ep)}
+    x = torch.randn(B, T, Hp, Wp, 256, generator=g)
+    want = TO.dec_cnn(wd, x, 8)                                                    # (B, T, D, 8 Hp, 8 Wp)
+    got = R.ref_dec(x.reshape(B * T, Hp, Wp, 256), dp).reshape(want.shape)
+    assert rel(got, want) < 1e-5
+    y = torch.randn(B, T, D, 8 * Hp, 8 * Wp, generator=g)
+    want = TO.enc_cnn(we, y, 8)                                                    # (B, T, Hp, Wp, 256)
+    got = R.ref_enc(y.reshape(B * T, D, 8 * Hp, 8 * Wp), ep).reshape(want.shape)
+    assert rel(got, want) < 1e-5
+    # Taylor sum: out_i = last + sum_k d_k taylor_coeff(i, dt, k) (tante.py:165-171, as the oracle's tante_forward writes it)
+    dt, n_out = 0.37, 4
+    inp = torch.randn(B, T, D, 4, 4, generator=g)
+    ds = [torch.randn(B, 1, D, 4, 4, generator=g) for _ in range(3)]
+    want = torch.cat([inp[:, -1:] + sum(d * TO.taylor_coeff(i, dt, k + 1) for k, d in enumerate(ds)) for i in range(1, n_out + 1)], 1)
+    assert rel(R.ref_taylor(inp, dt, n_out, ds), want) < 1e-5
