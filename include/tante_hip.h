@@ -250,6 +250,13 @@ int tante_block_fused(float* x, const void* block_stream, int C, int n_head, int
  * T axis followed by tante_block_fused, bit for bit, in one pass over x. */
 int tante_block_fused_tprop(float* x, const void* block_stream, int C, int n_head, int hidden, const TanteSeq* seq, int causal, float eps,
                             const float* tprop, void* stream);
+/* The last-slot form of the T letter (L = 4), tprop = the propagator's 40 floats (as tante_block_fused_tprop) or NULL (as
+ * tante_block_fused): only the rows at position L - 1 of every sequence are written, equal bit for bit to the rows the full launch writes
+ * there; the rows at positions 0 .. L - 2 are left as they were (not even propagated).  For a stream of which only the last time slot is
+ * read afterwards (the last Taylor order of TANTE.forward).  tante_block_fused_last_supported: C = 256, 8 heads, hidden 256, L = 4. */
+int tante_block_fused_last_supported(int C, int n_head, int hidden, int L);
+int tante_block_fused_last(float* x, const void* block_stream, int C, int n_head, int hidden, const TanteSeq* seq, int causal, float eps,
+                           const float* tprop, void* stream);
 
 /* Training forward of a whole TransformerBlock in ONE launch (C = 256, 8 heads, hidden 256, sequences up to 64 tokens): the same
  * arithmetic as tante_block_fused with dropout (attn_backbone.py:47-83 in train() mode: attention-probability dropout inside

@@ -156,6 +156,21 @@ class TransformerBlock(nn.Module):
         return (FUSE_TPROP and compute == L.BF16 and self.fused and self.ln1.eps == self.ln2.eps and seq_L == 4 and self.embed_dim == 256
                 and self.n_head == 8 and self.hidden == 256 and not (self.training and self.p_drop > 0.0))
 
+    def fused_inference(self, seq_L: int, compute: int) -> bool:
+        """Does forward_tokens run this block as one fused inference launch (K.block_fused) at sequence length seq_L?"""
+        return (compute == L.BF16 and self.fused and self.ln1.eps == self.ln2.eps and not (self.training and self.p_drop > 0.0)
+                and K.block_fused_supported(self.embed_dim, self.n_head, self.hidden, seq_L))
+
+    def forward_last_slot(self, x: torch.Tensor, seq: L.Seq, causal: bool, tprop: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The T letter (L = 4) on the fused kernel, writing only the rows at slot 3 of its sequences (K.block_fused_last): those rows are
+        forward_tokens' bit for bit, the other rows of x stay as they were.  The caller checked fused_inference and
+        K.block_fused_last_supported."""
+        return K.block_fused_last(x, self._packed_fused(), self.embed_dim, self.n_head, self.hidden, seq, causal, self.ln1.eps, tprop)
+
+    def forward_subgrid(self, x: torch.Tensor, row0: int, seq: L.Seq, causal: bool) -> torch.Tensor:
+        """The fused block on the tokens `seq` reaches from row row0 of x (K.block_fused_subgrid); the caller checked fused_inference."""
+        return K.block_fused_subgrid(x, row0, self._packed_fused(), self.embed_dim, self.n_head, self.hidden, seq, causal, self.ln1.eps)
+
     def forward_tokens(self, x: torch.Tensor, seq: L.Seq, causal: bool, compute: int, tprop: Optional[torch.Tensor] = None) -> torch.Tensor:
         """In place on the flat fp32 residual stream x (tokens, C); `seq` says which tokens attend to which.  tprop: the temporal
         propagator's packed weights, applied to the rows inside the fused launch (only when takes_tprop says so)."""
@@ -323,13 +338,33 @@ class Attn_Backbone(nn.Module):
         """forward_tokens(x, ..., x_in=other) can read its input from another buffer (the first propagator launch runs out of place)."""
         return K.axis_hw_train_supported(self.H, self.W, self.C, compute)
 
+    def _last_slot_plan(self, B: int, compute: int) -> Optional[int]:
+        """forward_tokens(last_slot_only=True): the index of the last time-mixing letter when it is a T letter that runs in the last-slot
+        form (K.block_fused_last) and every later letter is an H, W or L block that runs fused on the slot-(T - 1) sub-grid; else None
+        (the full path)."""
+        axes = self.attn_axes
+        j = max(axes.rfind(a) for a in "TYXA")
+        if j < 0 or axes[j] != "T" or self.T != 4 or torch.is_grad_enabled():
+            return None
+        blk = self.blocks[j]
+        if not (blk.fused_inference(self.T, compute) and K.block_fused_last_supported(blk.embed_dim, blk.n_head, blk.hidden, self.T)):
+            return None
+        for i in range(j + 1, len(axes)):
+            if axes[i] not in "HWL" or not self.blocks[i].fused_inference(K.last_slot_seq(axes[i], B, self.T, self.H, self.W).L, compute):
+                return None
+        return j
+
     def forward_tokens(self, x: torch.Tensor, B: int, compute: int, film_src: Optional[tuple] = None, x_in: Optional[torch.Tensor] = None,
-                       film_frames: Optional[tuple] = None) -> torch.Tensor:
+                       film_frames: Optional[tuple] = None, last_slot_only: bool = False) -> torch.Tensor:
         """In place on x = (B,T,H,W,C) fp32 contiguous.  film_src = (z, t_stride, b_stride, film): x is not read but produced from the
         frame-major pre-FiLM encoder cache z while the first propagator kernel loads its planes (TANTE.forward(enc_cache=...)).
         x_in (takes_x_in): the input stream, left intact -- x is only written.
         film_frames = (TanteFrames, the frame tensors, a, b, s_emb) (planes too large for the whole-plane kernel: the spectral path at
-        512 x 512): the same, by the vertical propagator's launch (tante_axis_mlp_film); the caller asked _supported."""
+        512 x 512): the same, by the vertical propagator's launch (tante_axis_mlp_film); the caller asked _supported.
+        last_slot_only: only x's last time slot is read afterwards (inference).  Inside a backbone only the T letter mixes time slots, so
+        when the last time-mixing letter is a fused T letter it runs in the last-slot form (only its slot-(T - 1) rows are written, each
+        query still sees all T keys) and the H / W / L letters after it run on the (b, T - 1) planes alone.  The slot-(T - 1) rows come out
+        bit for bit as on the full path; the other slots are left part-way (not meaningful).  Any other backbone takes the full path."""
         T, H, W, C_ = self.T, self.H, self.W, self.C
         vp, hp, tp = self.vertical_propagator, self.horizontal_propagator, self.temporal_propagator
         if film_frames is not None:
@@ -360,10 +395,15 @@ class Attn_Backbone(nn.Module):
             tprop = self._packed_tprop()
         else:
             K.axis_mlp(x, B, T, H * W * C_, tp[0].weight, tp[0].bias, tp[2].weight, tp[2].bias, compute)
+        jl = self._last_slot_plan(B, compute) if last_slot_only else None
         ci = 0
         for i, axis in enumerate(self.attn_axes):
             blk = self.blocks[i]
-            if axis == "C":                                                                          # l.184-189
+            if jl is not None and i == jl:
+                blk.forward_last_slot(x, K.make_seq(axis, B, T, H, W), True, tprop if i == 0 else None)
+            elif jl is not None and i > jl:
+                blk.forward_subgrid(x, (T - 1) * H * W, K.last_slot_seq(axis, B, T, H, W), False)
+            elif axis == "C":                                                                          # l.184-189
                 E = self.expanded_channel
                 lift1, lift2 = self._packed_channel(compute)[ci]
                 ci += 1

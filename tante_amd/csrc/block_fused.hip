@@ -796,6 +796,24 @@ extern "C" int tante_block_fused_tprop(float* x, const void* block_stream, int C
   return 0;
 }
 
+extern "C" int tante_block_fused_last_supported(int C, int n_head, int hidden, int L) {
+  return C == 256 && n_head == 8 && hidden == 256 && L == 4 && use_fs(C, n_head, hidden, L, 0);
+}
+
+extern "C" int tante_block_fused_last(float* x, const void* block_stream, int C, int n_head, int hidden, const TanteSeq* seq, int causal,
+                                      float eps, const float* tprop, void* stream) {
+  if (!x || !block_stream || !seq) TANTE_FAIL(-1, "tante_block_fused_last: null pointer");
+  if (!tante_block_fused_last_supported(C, n_head, hidden, seq->L))
+    TANTE_FAIL(-2, "tante_block_fused_last: the feature-sliced kernel at C = 256 / 8 heads / hidden 256 / L = 4 only (C=%d heads=%d hidden=%d L=%d)",
+               C, n_head, hidden, seq->L);
+  if (((uintptr_t)x % 16) || ((uintptr_t)block_stream % 16)) TANTE_FAIL(-1, "tante_block_fused_last: buffers must be 16-byte aligned");
+  if (tante_fs_launch(x, (const char*)block_stream + block_ts_stream_bytes(C, hidden), *seq, causal, eps, (hipStream_t)stream, nullptr, tprop,
+                      true) != 0)
+    TANTE_FAIL(-2, "tante_block_fused_last: too many sequences (%d)", seq->nseq);
+  TANTE_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int tante_block_fused(float* x, const void* block_stream, int C, int n_head, int hidden, const TanteSeq* seq, int causal,
                                  float eps, void* stream) {
   if (!x || !block_stream || !seq) TANTE_FAIL(-1, "tante_block_fused: null pointer");

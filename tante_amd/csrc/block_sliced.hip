@@ -160,9 +160,17 @@ constexpr int fs_group(int ntt, int nk) {
 // MATRIX, ...  Waves w and w + 4 share a SIMD: whenever one group is in a matrix segment its partner on the SIMD is in a vector / memory
 // segment, by construction and for the whole launch (two independent workgroups start together and stay in step: MFMA-only phases
 // beside MFMA-only phases, with the matrix pipe idle through every LayerNorm / softmax / GELU phase -- SQ_VALU_MFMA_COEXEC 11 %).
-template <int TPS, int NTT, int NW, bool TRAIN, int G = 1, bool TPROP = false>
+//
+// LASTQ (inference, T letter at L = 4): only the rows at slot L - 1 of every sequence are the launch's output (the last Taylor order of a
+// rollout: its head reads slot T - 1 alone).  Every row is still loaded, propagated (TPROP), LayerNorm-ed and run through the whole
+// block -- the slot-(L - 1) query attends to all four keys -- but only the slot-(L - 1) rows are written back: a quarter of the block's
+// row stores, and with TPROP a quarter of the propagated-row stores.  Those rows are the full form's bit for bit (the arithmetic is the
+// same instruction stream).  The residual re-reads stay whole: skipping three rows in four made the loads lane-divergent branches and
+// the launch SLOWER (41.1 -> 45.5 us, cfg2 B = 8).
+template <int TPS, int NTT, int NW, bool TRAIN, int G = 1, bool TPROP = false, bool LASTQ = false>
 __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
   static_assert(!TPROP || (TPS == 1 && !TRAIN), "the fused temporal propagator: T letter (L = 4), inference");
+  static_assert(!LASTQ || (TPS == 1 && NW == 4 && G == 1 && !TRAIN), "the last-slot form: T letter (L = 4), 4 waves, inference");
   static_assert(G == 1 || (G == 2 && NW == 4), "the paired form is two 4-wave groups");
   constexpr int RT = 16 / NW;            // 16-row output tiles per wave
   constexpr int HPW = RT / 2;            // heads per wave
@@ -329,7 +337,7 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
         if (t >= 0) __builtin_nontemporal_store(v, (f32x4*)(dst + (long)t * FS_C + 16 * RT * wave + 4 * rchunk));
 #else                   // write-through (common.hip.h): 38.4 -> 37.2 us per launch and +2.4 % on the rollout, three interleaved rounds
         // the inference form only (the training form's launches are bound by their saved-tensor traffic, not by the release)
-        if (t >= 0) {
+        if (t >= 0 && (!LASTQ || (r & 3) == 3)) {      // (L = 4: row r of a tile is slot r & 3 of its sequence)
           if constexpr (TRAIN) *(f32x4*)(dst + (long)t * FS_C + 16 * RT * wave + 4 * rchunk) = v;
           else st_wt16(dst + (long)t * FS_C + 16 * RT * wave + 4 * rchunk, v);
         }
@@ -377,7 +385,7 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
           // residual slices through the propagator a second time (-DFS_TPROP_RECOMPUTE) -- costs the contraction + 64 GELUs per lane
           // once more on the critical path: 46 us per launch against 41 us (the extra 33 MB of stores drain under the q, k, v GEMMs).
 #ifndef FS_EXP_TPROP_NO_STORE      // timing experiment only (wrong results): what the propagated rows' store and re-read cost
-          if (live) *(f32x4*)(x + (long)tk * FS_C + 4 * lane) = y;
+          if (live && (!LASTQ || t == 3)) *(f32x4*)(x + (long)tk * FS_C + 4 * lane) = y;
 #endif
 #endif
           float sm = (y[0] + y[1]) + (y[2] + y[3]);
@@ -1044,13 +1052,20 @@ __global__ void fs_pack_multi_kernel(FsPackBatch B) {
   fs_pack_body((int)blockIdx.x - e * FSP_BLOCKS, q[0], q[1], nullptr, nullptr, q[2], q[3], q[4], q[5], nullptr, nullptr, q[6], q[7], B.dst[e]);
 }
 
-template <int TPS, int NTT, int NW, bool TRAIN, int G = 1, bool TPROP = false>
+template <int TPS, int NTT, int NW, bool TRAIN, int G = 1, bool TPROP = false, bool LASTQ = false>
 void fs_launch_tt(const FsArgs& A, int nwg, hipStream_t s) {
   constexpr int LDS = G * (2 * 16 * NTT * FS_ROW + 16 * NTT * NW * 8 + FS_BIAS_FLOATS * 4);
   static_assert(LDS <= 160 * 1024, "LDS per workgroup");
   static TantePerDevice attr;
-  attr.once([&] { (void)hipFuncSetAttribute((const void*)block_fs_kernel<TPS, NTT, NW, TRAIN, G, TPROP>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); });
-  hipLaunchKernelGGL((block_fs_kernel<TPS, NTT, NW, TRAIN, G, TPROP>), dim3((nwg + G - 1) / G), dim3(64 * NW * G), LDS, s, A);
+  attr.once([&] { (void)hipFuncSetAttribute((const void*)block_fs_kernel<TPS, NTT, NW, TRAIN, G, TPROP, LASTQ>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); });
+  hipLaunchKernelGGL((block_fs_kernel<TPS, NTT, NW, TRAIN, G, TPROP, LASTQ>), dim3((nwg + G - 1) / G), dim3(64 * NW * G), LDS, s, A);
+}
+// the last-slot form (LASTQ) at the geometries of the T letter's 4-wave launch: 4 tiles (three-quarter grids run the full size:
+// the form is per sequence, any geometry gives the same rows) or the half-size 2 tiles
+template <int NTT>
+void fs_launch_last(const FsArgs& A, int nwg, hipStream_t s) {
+  if (A.tprop) fs_launch_tt<1, NTT, 4, false, 1, true, true>(A, nwg, s);
+  else fs_launch_tt<1, NTT, 4, false, 1, false, true>(A, nwg, s);
 }
 // TANTE_FS_GROUPS = 2 (tante_set_option) selects the paired form; the default is the unpaired one.  Both compute the same function, bit for
 // bit (tools/fs_ab.py asserts it).  MEASURED (round 3, one box, interleaved rounds, cfg2 B = 8): the paired form is 1.2 - 2.3 us SLOWER per
@@ -1116,9 +1131,10 @@ void tante_fs_pack_folded_multi(const float* const (*params)[8], char* const* ds
 }
 
 int tante_fs_launch(float* x, const char* stream, const TanteSeq& sq, int causal, float eps, hipStream_t s, const TanteBlockTrain* tr,
-                    const float* tprop) {
+                    const float* tprop, bool lastq) {
   if (sq.nseq >= (1 << 23)) return -2;
   if (tprop && (tr || sq.L != 4)) return -5;
+  if (lastq && (tr || sq.L != 4)) return -5;
   FsArgs A;
   A.x = x; A.w = stream; A.sq = sq; A.causal = causal; A.eps = eps;
   A.out = nullptr;
@@ -1135,7 +1151,8 @@ int tante_fs_launch(float* x, const char* stream, const TanteSeq& sq, int causal
 #ifdef TANTE_ABLATE
   A.stamps = g_fs_stamps;
 #endif
-  const int L = sq.L, nw = (tr || tprop) ? 4 : fs_waves(L);      // (the training form and the fused propagator exist in the 4-wave kernels)
+  const int L = sq.L, nw = (tr || tprop || lastq) ? 4 : fs_waves(L);      // (the training form, the fused propagator and the last-slot
+                                                                          //  form exist in the 4-wave kernels)
   A.magic = (65536u + (unsigned)L - 1u) / (unsigned)L;
   // tile-aligned shapes: L | 16 (several sequences per tile), L = 32 / 48 / 64 (2 / 3 / 4 tiles per sequence, non-causal)
   int tps = 0;
@@ -1161,10 +1178,16 @@ int tante_fs_launch(float* x, const char* stream, const TanteSeq& sq, int causal
     const int spw_full = 16 * ntt / L;
     if (((long)sq.nseq + spw_full - 1) / spw_full * 4 <= resident) ntt = 2;
   }
+  if (lastq && ntt == tq) ntt = full;      // (the last-slot form is instantiated at 4 and 2 tiles only)
   A.spw = tps ? 16 * ntt / L : (16 * full) / L;
   const int nwg = (sq.nseq + A.spw - 1) / A.spw;
   // one resident round of two workgroups per CU (cfg2 / cfg3 at B = 8): the second residents start late (FsArgs.skew)
   A.skew = (!tr && nw == 4 && nwg > 256 && nwg <= 512) ? tante_opt("TANTE_FS_SKEW", 0) : 0;
+  if (lastq) {      // (L = 4, 4 waves: tps = 1; ntt is 4 or 2)
+    if (ntt == 2) fs_launch_last<2>(A, nwg, s);
+    else fs_launch_last<4>(A, nwg, s);
+    return 0;
+  }
   const int key = nw * 100 + tps * 10 + ntt;
   switch (key) {
     case 412:

@@ -202,6 +202,22 @@ def make_seq(letter: str, B: int, T: int, H: int, W: int) -> L.Seq:
     return s
 
 
+def last_slot_seq(letter: str, B: int, T: int, H: int, W: int) -> L.Seq:
+    """make_seq of a letter that stays within one (b, t) plane (H, W, L), restricted to t = T - 1: its token indices count from row
+    (T - 1) H W of the stream (block_fused_subgrid's row0)."""
+    s = L.Seq()
+    HW, THW = H * W, T * H * W
+    if letter == "H":
+        s.nseq, s.L, s.n_s0, s.S1, s.S0, s.n_l0, s.P1, s.P0 = B * W, H, W, THW, 1, H, 0, W
+    elif letter == "W":
+        s.nseq, s.L, s.n_s0, s.S1, s.S0, s.n_l0, s.P1, s.P0 = B * H, W, H, THW, W, W, 0, 1
+    elif letter == "L":
+        s.nseq, s.L, s.n_s0, s.S1, s.S0, s.n_l0, s.P1, s.P0 = B, HW, 1, THW, 0, HW, 0, 1
+    else:
+        raise ValueError(f"letter {letter!r} mixes time slots")
+    return s
+
+
 def dense_seq(nseq: int, Lq: int) -> L.Seq:
     s = L.Seq()
     s.nseq, s.L, s.n_s0, s.S1, s.S0, s.n_l0, s.P1, s.P0 = nseq, Lq, 1, Lq, 0, Lq, 0, 1
@@ -367,6 +383,33 @@ def block_fused(x: torch.Tensor, block_stream: torch.Tensor, C_: int, n_head: in
         return x
     L.check(L.lib().tante_block_fused(_p(x), _p(block_stream), C_, n_head, hidden, C.byref(seq), int(causal), eps, _stream()),
             "tante_block_fused")
+    return x
+
+
+# The two launches of a backbone whose stream is read at its last time slot only (Attn_Backbone.forward_tokens(last_slot_only=True)).
+# Entries of their own, not block_fused: they do a quarter of a full launch's row work, and bench.py's roofline pass credits every
+# block_fused call with x.numel() // C tokens.
+def block_fused_last_supported(C_: int, n_head: int, hidden: int, Lq: int) -> bool:
+    return bool(L.lib().tante_block_fused_last_supported(C_, n_head, hidden, Lq))
+
+
+def block_fused_last(x: torch.Tensor, block_stream: torch.Tensor, C_: int, n_head: int, hidden: int, seq: L.Seq, causal: bool,
+                     eps: float, tprop: Optional[torch.Tensor] = None):
+    """The T letter (L = 4) writing only the rows at slot 3 of its sequences (tante_block_fused_last); tprop as in block_fused."""
+    _dev(x, block_stream, tprop)
+    L.check(L.lib().tante_block_fused_last(_p(x), _p(block_stream), C_, n_head, hidden, C.byref(seq), int(causal), eps, _p(tprop), _stream()),
+            "tante_block_fused_last")
+    return x
+
+
+def block_fused_subgrid(x: torch.Tensor, row0: int, block_stream: torch.Tensor, C_: int, n_head: int, hidden: int, seq: L.Seq,
+                        causal: bool, eps: float):
+    """The fused block on the tokens `seq` reaches from row `row0` of x (tante_block_fused on a base pointer x + row0 C)."""
+    _dev(x, block_stream)
+    if x.dtype != torch.float32 or row0 < 0 or row0 >= x.numel() // C_:
+        raise RuntimeError("block_fused_subgrid: fp32 stream and a row inside it")
+    L.check(L.lib().tante_block_fused(x.data_ptr() + row0 * C_ * 4, _p(block_stream), C_, n_head, hidden, C.byref(seq), int(causal), eps,
+                                      _stream()), "tante_block_fused")
     return x
 
 

@@ -58,6 +58,9 @@ class TanteMetadata:
 HEAD_MULTI = _O.register("TANTE_HEAD_MULTI", True, __name__, "HEAD_MULTI")      # every Taylor order's derivative head in one launch
 HEAD_STREAMS = _O.register("TANTE_HEAD_STREAMS", True, __name__, "HEAD_STREAMS")  # ... reading each order's own stream buffer (no row copies)
 HEAD_ENC = _O.register("TANTE_HEAD_ENC", True, __name__, "HEAD_ENC")          # ... and re-encoding the predicted frame in the same launch (head_enc.hip)
+# the last Taylor order's backbone finishes only the rows of time slot T - 1, the one slot the head reads (Attn_Backbone.forward_tokens
+# (last_slot_only=True)): its last T letter writes those rows alone, the H / W letters after it run on the slot-(T - 1) planes
+LAST_SLOT = _O.register("TANTE_LAST_SLOT", True, __name__, "LAST_SLOT")
 
 
 def _check_patch_cfg(patch_scale, overlap_ratio):
@@ -612,13 +615,16 @@ class TANTE(nn.Module):
         # ... or not copied at all: every later backbone writes a stream buffer of its own (its first launch, the H + W propagator pass,
         # runs out of place: tante_axis_hw_oop), so the earlier orders' streams stay intact for the head.  TANTE_HEAD_STREAMS=0: copies.
         streams = tail_fused or (multi_head and HEAD_STREAMS and all(b.takes_x_in(compute) for b in self.blocks[1:self.taylor_order]))
+        # the last order's stream is read at slot T - 1 only (by the one head launch): its backbone may leave the other slots unfinished
+        slot_only = LAST_SLOT and self.deg and multi_head and self.output_length == 1 and not torch.is_grad_enabled()
         for i in range(self.taylor_order):
+            ls = slot_only and i + 1 == self.taylor_order
             if streams and i > 0:
                 x_prev, x = x, torch.empty_like(x)
-                self.blocks[i].forward_tokens(x, B, compute, x_in=x_prev)
+                self.blocks[i].forward_tokens(x, B, compute, x_in=x_prev, last_slot_only=ls)
             else:
                 self.blocks[i].forward_tokens(x, B, compute, film_src=(enc_cache + (film,)) if (enc_cache is not None and i == 0) else None,
-                                              film_frames=film_frames if i == 0 else None)  # l.146 (chained)
+                                              film_frames=film_frames if i == 0 else None, last_slot_only=ls)  # l.146 (chained)
             if self.deg:
                 if multi_head:
                     if i + 1 < self.taylor_order:
