@@ -11,11 +11,14 @@ Launch: `python bench.py --gpus N` with WORLD_SIZE unset spawns the N ranks ITSE
 any GPU call) and prints rank 0's line; under torchrun (RANK / LOCAL_RANK / WORLD_SIZE set) it is one of the ranks.  It fails loudly
 when --gpus disagrees with WORLD_SIZE or with the number of visible GPUs.
 
-Also reported on the same JSON line:
+A plain run does only what the headline figure needs: set up, warm up, time the steps, write --dump-outputs, print the line.
+With --full the same JSON line also reports (each leg still switched off by its --no-* flag):
   roofline      dominant kernel (LayerNorm-fused projection GEMM, bf16 MFMA) algorithmic FLOP/s vs the dense
                 bf16 peak, timed with HIP events around each of its launches in an instrumented pass
   cpu_baseline  the CPU oracle (oracle/tante_oracle.py, kind "port") timed on this box's host cores on a bounded
                 sample of the same workload (rank 0, N=1 only)
+  train         the cfg3 train step (configs/tante_trl.yaml), weak and strong (cfg2 runs only)
+  workloads     compact legs of cfg2 at other batches, cfg4 and cfg5 (cfg2 runs, rank 0, N=1 only)
 """
 import argparse
 import json
@@ -47,6 +50,9 @@ def parse():
     p.add_argument("--config", default=os.path.join(ROOT, "configs", "tante_am.yaml"))
     p.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: workload.batch_size)")
     p.add_argument("--dtype", default=None, choices=["bf16", "fp32"])
+    p.add_argument("--full", action="store_true", help="also run the legs the headline figure does not need: the roofline pass, the train-step "
+                                                         "leg, the CPU baseline and the compact side workloads (off: a plain run stops after "
+                                                         "the headline leg's timed steps and --dump-outputs)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-roofline", action="store_true")
     p.add_argument("--no-train", action="store_true", help="skip the train-step leg (configs/tante_trl.yaml)")
@@ -596,7 +602,7 @@ def main():
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
 
-    leg = rollout_leg(args.config, args.batch, args.dtype, args.steps, args.warmup, dev, rank, world, dist, not args.no_roofline,
+    leg = rollout_leg(args.config, args.batch, args.dtype, args.steps, args.warmup, dev, rank, world, dist, args.full and not args.no_roofline,
                       graph=True if args.graph else (False if (args.no_graph or world > 1) else "auto"),      # (multi-rank runs: eager unless asked)
                       reps=args.reps, dump_dir=args.dump_outputs if rank == 0 else None)
     if leg["dumped"] is not None:
@@ -616,7 +622,7 @@ def main():
             torch.cuda.synchronize()
 
     train = None
-    if not args.no_train and kind == "tante" and os.path.basename(args.config) == "tante_am.yaml":
+    if args.full and not args.no_train and kind == "tante" and os.path.basename(args.config) == "tante_am.yaml":
         # second leg of the metric: train-step samples/sec on cfg3 (TRL-2D shaped fields, 4-step BPTT, MSE + clip + AdamW, one summed
         # all-reduce of the flat gradient bucket per step when N > 1), weak (8 samples per GPU) and strong (global batch 64)
         tcfg = tante_amd.load_config(os.path.join(ROOT, "configs", "tante_trl.yaml"))
@@ -680,7 +686,7 @@ def main():
             train["strong"] = {"scaling": "strong", **strong}
 
     cpu = None
-    if not args.no_cpu_baseline and rank == 0 and world == 1 and kind not in ("cvit", "fno"):      # (cfg4: the `workloads` object's own CPU leg)
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1 and kind not in ("cvit", "fno"):      # (cfg4: the `workloads` object's own CPU leg)
         from oracle import tante_oracle as O
         mk = cfg["model"]
         ocfg = O.TanteCfg(mk["in_T"], D, res, taylor_order=mk.get("taylor_order", 1), frame_interval=mk.get("frame_interval", 1.0),
@@ -734,7 +740,7 @@ def main():
                "gpu_over_cpu": round(value / legs[best]["value"], 1)}
 
     workloads = None
-    if (not args.no_workloads and rank == 0 and world == 1 and kind == "tante" and os.path.basename(args.config) == "tante_am.yaml"):
+    if (args.full and not args.no_workloads and rank == 0 and world == 1 and kind == "tante" and os.path.basename(args.config) == "tante_am.yaml"):
         # The other BASELINE configurations, compact, in the driver's own run (round-3 verdict item 7): cfg2 at B = 1 (eager and as ONE
         # captured graph), cfg4 at B = 1 / 4 with its whole-forward fraction and a CPU leg, cfg5 with its HBM roofline.  Short legs.
         del model, batch, leg
@@ -794,7 +800,7 @@ def main():
                  "fno": "rollout frames/sec (fwd), models.FNO (configs/fno.yaml model block) on 512x512x8"}[kind]
         out = {"metric": title, "value": round(value, 2), "unit": "frames/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic", "full": args.full,
                "config": {"workload": os.path.basename(args.config), "fields": D, "resolution": list(res), "batch_per_gpu": B,
                           "n_steps_input": T_in, "n_steps_rollout": n_steps, "taylor_order": cfg["model"].get("taylor_order", 1),
                           "attn_axes": cfg["model"].get("attn_axes"), "parallelism": f"batch-sharded x{world} (no collective)",

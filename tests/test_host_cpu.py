@@ -646,3 +646,34 @@ def test_train_tail_references_match_the_oracles():
     ds = [torch.randn(B, 1, D, 4, 4, generator=g) for _ in range(3)]
     want = torch.cat([inp[:, -1:] + sum(d * TO.taylor_coeff(i, dt, k + 1) for k, d in enumerate(ds)) for i in range(1, n_out + 1)], 1)
     assert rel(R.ref_taylor(inp, dt, n_out, ds), want) < 1e-5
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_bench_side_legs_run_only_with_full(monkeypatch, capsys, full):
+    """A plain `bench.py` run times the headline leg and prints its line; the roofline pass (and the train, CPU-baseline and side-workload
+    legs, switched off here by their own flags: they need a GPU) run only with --full.  The headline leg is stubbed: no GPU here."""
+    import json
+    import sys
+    import bench
+    asked = []
+
+    def leg(config, batch, dtype, steps, warmup, dev, rank, world, dist, want_roofline, graph=False, reps=1, dump_dir=None):
+        asked.append((want_roofline, graph, reps, dump_dir))
+        return {"value": 1e4, "elapsed": 0.064, "roofline": {"frac": 0.3, "avg_launch_us": 35.0} if want_roofline else None, "model": None,
+                "batch": None, "cfg": {"model": {"taylor_order": 3, "attn_axes": "THW-THW-THW"}}, "wl": {}, "kind": "tante", "B": 8,
+                "n_steps": 8, "T_in": 4, "res": (256, 256), "D": 11, "dtype": "bf16", "graph": "off", "timing": {}, "dumped": None}
+    for var in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "TANTE_ALL_ON_GPU0"):
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.setattr(bench, "rollout_leg", leg)
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 1)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    argv = ["bench.py", "--gpus", "1", "--steps", "10", "--warmup", "3"]
+    if full:
+        argv += ["--full", "--no-train", "--no-cpu-baseline", "--no-workloads"]
+    monkeypatch.setattr(sys, "argv", argv)
+    bench.main()
+    out = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert asked == [(full, "auto", 7, None)]
+    assert out["full"] is full and out["value"] == 1e4 and out["ms_per_step"] == 6.4 and out["steps"] == 10 and out["warmup"] == 3
+    assert (out["roofline"] is not None) is full and out["roofline_frac"] == (0.3 if full else None)
+    assert out["train"] is None and out["cpu_baseline"] is None and out["workloads"] is None

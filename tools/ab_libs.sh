@@ -4,7 +4,7 @@
 # selected through TANTE_LIB (tante_amd/_lib.py): the product library tante_amd/lib/libtante_hip.so is never overwritten.  "product" names it.
 set -u
 # AB_ARGS: bench.py arguments of the runs (default: the cfg2 rollout leg alone)
-AB_ARGS=${AB_ARGS:---steps 8 --warmup 3 --no-cpu-baseline --no-train --no-workloads}
+AB_ARGS=${AB_ARGS:---full --steps 8 --warmup 3 --no-cpu-baseline --no-train --no-workloads}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 for i in 1 2 3; do
   for v in "$@"; do

@@ -12,7 +12,7 @@ for i in $(seq $ROUNDS); do
     elif [ "$v" == "off" ]; then lib=$R/tante_amd/lib/libtante_hip.so; extra="TANTE_TRAIN_FUSED_BLOCK_BWD=0"
     else lib=$R/tools/_ab/lib_$v.so; fi
     [ -f "$lib" ] || { echo "missing $lib" >&2; exit 1; }
-    env $extra TANTE_LIB=$lib timeout -k 10 200 python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-workloads --no-roofline --reps 1 ${AB_ARGS:-} 2>/dev/null | python3 -c "
+    env $extra TANTE_LIB=$lib timeout -k 10 200 python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-workloads --no-roofline --reps 1 ${AB_ARGS:-} 2>/dev/null | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); t=d['train']; print('$v', 'train ms', t['ms_per_step'], 'strong ms', (t.get('strong') or {}).get('ms_per_step'))"
   done

@@ -11,7 +11,7 @@ for c in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY
          "SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_VMEM SQ_WAVES SQ_INSTS_VMEM SQ_VALU_MFMA_COEXEC_CYCLES SQ_LDS_UNALIGNED_STALL SQ_LDS_ADDR_CONFLICT" \
          "GRBM_GUI_ACTIVE GRBM_COUNT" "FETCH_SIZE" "WRITE_SIZE"; do
   n=$(echo $c | tr ' ' '_' | cut -c1-40)
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$n -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --no-train > /dev/null 2> $OUT/$n.err
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$n -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --no-train > /dev/null 2> $OUT/$n.err
 done
 cd $R && python3 - <<PY
 import csv, glob, json, collections
