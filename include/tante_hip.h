@@ -372,6 +372,24 @@ int tante_attention_masked(const void* qkv, void* o, int dtype, int C, int n_hea
 int tante_attention_masked_bwd(const void* qkv, const void* dO, void* dqkv, int dtype, int C, int n_head, int Bp, int L, int causal,
                                const float* attn_mask, int64_t mask_bstride, const float* key_padding_mask, float* stats, void* stream);
 
+/* ---- flash attention over sequences of any length, with dropout (attn_flash.hip; ABI 14) --------------------------------------------
+ * The same function as tante_attention_dropout / tante_attention_bwd (nn.MultiheadAttention(dropout = p)'s core in train() mode,
+ * attn_backbone.py:47-48, 59-83, over the regroupings of attn_backbone.py:148-189), for the sequences those refuse: a forward and a
+ * backward that walk the keys in tiles on the matrix cores (bf16: v_mfma_f32_16x16x32_bf16; fp32: v_mfma_f32_16x16x4_f32), any L.
+ * Head dim 32 only (C = 32 n_head); dtype TANTE_F32 or TANTE_BF16; anything else is refused with -2 (tante_attention_flash_supported).
+ * The dropout mask is dropout_keep(seed, (((s n_head + h) L + l) L + j), p): tante_attention_dropout's, so either forward pairs with
+ * either backward.  The seed is used as given: these kernels do NOT read the device seed word of tante_set_seed_mix.
+ * stats: tante_attention_flash_stats_floats(n_head, seq) floats = 2 per (sequence, head, query): the forward writes
+ * log2-sum-exp2 of the scaled scores to [row * 2] (stats may be NULL: inference); the backward reads it and uses [row * 2 + 1] as
+ * scratch for delta = dO . O.  o is the forward's output for the same (qkv, p, seed).  dqkv (tokens, 3C) = (dq | dk | dv), plain sums in
+ * a fixed order (two launches: a query-stationary pass for delta and dq, a key-stationary pass for dk and dv): deterministic. */
+int64_t tante_attention_flash_stats_floats(int n_head, const TanteSeq* seq);
+int tante_attention_flash_supported(int dtype, int C, int n_head, int L);
+int tante_attention_flash(const void* qkv, void* o, float* stats, int dtype, int C, int n_head, const TanteSeq* seq, int causal,
+                          float p_drop, uint64_t seed, void* stream);
+int tante_attention_flash_bwd(const void* qkv, const void* o, const void* dO, float* stats, void* dqkv, int dtype, int C, int n_head,
+                              const TanteSeq* seq, int causal, float p_drop, uint64_t seed, void* stream);
+
 /* ---- the token-local tail of a rollout call in ONE launch (head_enc.hip; bf16, C = 256, D <= 16, Hp Wp % 16 == 0) -----------------
  * tante_head_enc_fused: every Taylor order's derivative head + the Taylor sum (as tante_head_fused_multi_streams: rows[k] = the residual
  * stream backbone k left, addressed by (a_n0, a_s1, a_s0, a_off), a_n0 % 16 == 0) and, when enc_stream != NULL, the RE-ENCODING of the

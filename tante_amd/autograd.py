@@ -16,6 +16,7 @@ from torch.autograd import Function
 from . import _lib as L
 from . import options as _O
 from . import kernels as K
+from . import attn_flash as FA
 
 _DT = {torch.float32: L.F32, torch.bfloat16: L.BF16}
 
@@ -1017,6 +1018,13 @@ class AttentionFn(Function):
             return o
         o = torch.empty(qkv.shape[0], Cc, dtype=qkv.dtype, device=qkv.device)
         seed = next_seed() if p_drop > 0 else 0
+        if p_drop > 0 and FA.forward_route(seq.L, float(p_drop), True) == FA.FWD_FLASH:
+            # sequences past tante_attention_dropout's 256 tokens: the flash forward, whose row statistics the flash backward reads
+            stats = FA.new_stats(qkv, n_head, seq)
+            FA.forward(qkv, o, stats, Cc, n_head, seq, causal, float(p_drop), seed)
+            ctx.save_for_backward(qkv, o, stats)
+            ctx.seq, ctx.C, ctx.nh, ctx.causal, ctx.p, ctx.seed = seq, Cc, n_head, causal, float(p_drop), seed
+            return o
         if p_drop > 0:
             L.check(L.lib().tante_attention_dropout(qkv.data_ptr(), o.data_ptr(), _DT[qkv.dtype], Cc, n_head, C.byref(seq), int(causal),
                                                     float(p_drop), seed, _s()), "attention_dropout")
@@ -1028,11 +1036,23 @@ class AttentionFn(Function):
 
     @staticmethod
     def backward(ctx, do):
-        (qkv,) = ctx.saved_tensors
+        saved = ctx.saved_tensors
+        qkv = saved[0]
         do = do.contiguous().to(qkv.dtype)
         dqkv = torch.empty_like(qkv)
         q = ctx.seq
-        if q.L > 128 and ctx.p == 0.0 and q.n_s0 == 1 and q.S1 == q.L and q.n_l0 >= q.L and q.P0 == 1:
+        route = FA.backward_route(q.L, ctx.p, FA.seq_is_dense(q), FA.supported(_DT[qkv.dtype], ctx.C, ctx.nh, q.L), FA.ATTN_FLASH)
+        if route == FA.BWD_FLASH:
+            # what tante_attention_bwd refuses (L > 128 with dropout, or strided): the flash backward.  It reads the flash forward's output
+            # and row statistics; when another kernel ran the forward (128 < L <= 256, or p = 0) they are recomputed here, same seed
+            if len(saved) == 3:
+                o, stats = saved[1], saved[2]
+            else:
+                o, stats = torch.empty_like(do), FA.new_stats(qkv, ctx.nh, q)
+                FA.forward(qkv, o, stats, ctx.C, ctx.nh, q, ctx.causal, ctx.p, ctx.seed)
+            FA.backward(qkv, o, do, stats, dqkv, ctx.C, ctx.nh, q, ctx.causal, ctx.p, ctx.seed)
+            return dqkv, None, None, None, None, None, None
+        if route == FA.BWD_MASKED:
             # dense sequences past the MFMA backward's length (the channel letter 'C' over 256 channels, 'L' over a 16 x 16 patch grid):
             # the lane-per-row recomputing backward (tante_attention_masked_bwd with no masks)
             stats = torch.empty(q.nseq * ctx.nh * q.L * 3, dtype=torch.float32, device=qkv.device)

@@ -11,6 +11,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
+from . import attn_flash as FA
 
 _DT = {torch.float32: L.F32, torch.bfloat16: L.BF16}
 COMPUTE = {"fp32": L.F32, "float32": L.F32, "bf16": L.BF16, "bfloat16": L.BF16}
@@ -228,6 +229,8 @@ def attention(qkv: torch.Tensor, o: torch.Tensor, C_: int, n_head: int, seq: L.S
     _dev(qkv, o)
     if qkv.dtype != o.dtype:
         raise RuntimeError("qkv and o must share a dtype")
+    if FA.ATTN_FLASH and FA.forward_route(seq.L, 0.0, FA.supported(_DT[qkv.dtype], C_, n_head, seq.L), FA.ATTN_FLASH) == FA.FWD_FLASH:
+        return FA.forward(qkv, o, None, C_, n_head, seq, causal)      # A/B route (off by default): attn_flash.py
     L.check(L.lib().tante_attention(_p(qkv), _p(o), _DT[qkv.dtype], C_, n_head, C.byref(seq), int(causal), _stream()),
             "tante_attention")
     return o
