@@ -1343,11 +1343,24 @@ class DeconvFn(Function):
             cols = K.im2col(d, False, n_img, Cout, Hi * P, Wi * P, P, P, P, P, 0, 0, 1, torch.bfloat16)
         if ctx.needs_input_grad[0]:
             lay = L.W_DECONV_NCHW_T if nchw_out else L.W_DECONV_NHWC_T
-            pwt = _packed(W, None, comp, lay, N=Cin, K=N, P=P, C_other=Cout)
             da = torch.empty(M, Cin, dtype=a.dtype, device=a.device)
-            if cols is not None:
-                K.linear(cols, pwt, da, M=M)
+            if N > 512:
+                # contraction (Cout P P) longer than the GEMM's register-stationary limit, which the patch GEMM below would refuse: the
+                # output-gradient patches as dense (kh, kw, co) rows, then N-chunks that accumulate through the fp32 residual operand
+                # (LinearFn.backward's loop)
+                rows = K.im2col(d, nchw_out, n_img, Cout, Hi * P, Wi * P, P, P, P, P, 0, 0, 1, K.act_torch_dtype(comp))
+                W2 = W.detach().permute(0, 2, 3, 1).reshape(Cin, N)
+                acc = None
+                for c0 in range(0, N, 512):
+                    ck = min(512, N - c0)
+                    pwc = K.pack_weight(W2[:, c0:c0 + ck].contiguous(), None, comp)
+                    nxt = da if c0 + ck >= N else torch.empty(M, Cin, dtype=torch.float32, device=a.device)
+                    K.linear(rows, pwc, nxt, M=M, a_n0=M, a_s0=N, a_off=c0, residual=acc)
+                    acc = nxt
+            elif cols is not None:
+                K.linear(cols, _packed(W, None, comp, lay, N=Cin, K=N, P=P, C_other=Cout), da, M=M)
             else:
+                pwt = _packed(W, None, comp, lay, N=Cin, K=N, P=P, C_other=Cout)
                 K.patch_embed(d, pwt, da, n_img=n_img, Hin=Hi * P, Win=Wi * P, Cin=Cout, P=P, nchw=nchw_out, act=L.ACT_NONE)
             da = da.view(a.shape)
         if ctx.needs_input_grad[1]:

@@ -648,6 +648,143 @@ def test_train_tail_references_match_the_oracles():
     assert rel(R.ref_taylor(inp, dt, n_out, ds), want) < 1e-5
 
 
+def test_train_node_references_match_the_oracles():
+    """The float64 references of tests/test_hip_train_nodes.py, evaluated in float32, against the CPU oracles (oracle/tante_oracle.py,
+    which tests/golden pins to the reference model's own outputs), so a wrong reference cannot let a wrong kernel pass.  Every
+    comparison <= 1e-5 relative L2."""
+    import math
+    import test_hip_train_nodes as R
+    from oracle import tante_oracle as TO
+
+    def rel(a, b):
+        return float((a.double() - b.double()).norm() / b.double().norm())
+
+    g = torch.Generator().manual_seed(8)
+    # LayerNorm without affine = the oracle's with unit gamma and zero beta
+    x = torch.randn(37, 100, generator=g) + 2.0
+    assert rel(R.ref_ln(x, 1e-5), TO.layer_norm(x, torch.ones(100), torch.zeros(100), 1e-5)) < 1e-5
+    # linear, with and without bias, with a residual
+    a, W, b, res = torch.randn(33, 44, generator=g), torch.randn(20, 44, generator=g), torch.randn(20, generator=g), torch.randn(33, 20, generator=g)
+    assert rel(R.ref_linear(a, W, b), TO.linear(a, W, b)) < 1e-5
+    assert rel(R.ref_linear(a, W, None), TO.linear(a, W, None)) < 1e-5
+    assert rel(R.ref_linear(a, W, b, res), res + TO.linear(a, W, b)) < 1e-5
+    # activations (the bulk and the special values of the GPU test)
+    xa = R.act_inputs(2051, g, torch.float32)
+    assert rel(R.ref_act(xa, R.ACT_GELU_ERF), TO.gelu_erf(xa)) < 1e-5
+    assert rel(R.ref_act(xa, R.ACT_GELU_TANH), TO.gelu_tanh(xa)) < 1e-5
+    assert torch.equal(R.ref_act(xa, R.ACT_RELU), xa.clamp(min=0)) and R.ref_act(xa, R.ACT_NONE) is xa
+    # patch convolution and transposed convolution, kernel = stride = P, at overlap 0 (P = 2: the oracle's 'same' padding (P - 1) // 2 is 0)
+    n, Cin, Cout, H, Wd, P = 2, 6, 10, 8, 12, 2
+    xi = torch.randn(n, Cin, H, Wd, generator=g)
+    wc, bc = torch.randn(Cout, Cin, P, P, generator=g), torch.randn(Cout, generator=g)
+    want = TO.real_conv2d(xi, wc, bc, P, 0.0).permute(0, 2, 3, 1).reshape(-1, Cout)
+    assert rel(R.ref_patch_embed(xi, wc, bc, P), want) < 1e-5
+    want = TO.real_conv2d(TO.gelu_erf(xi), wc, bc, P, 0.0).permute(0, 2, 3, 1).reshape(-1, Cout)
+    assert rel(R.ref_patch_embed(xi, wc, bc, P, R.ACT_GELU_ERF), want) < 1e-5
+    Hi, Wi = 5, 7
+    rows = torch.randn(n * Hi * Wi, Cin, generator=g)
+    wt, bt = torch.randn(Cin, Cout, P, P, generator=g), torch.randn(Cout, generator=g)
+    want = TO.real_transconv2d(rows.view(n, Hi, Wi, Cin).permute(0, 3, 1, 2), wt, bt, P, 0.0)
+    assert rel(R.ref_deconv(rows, wt, bt, n, Hi, Wi, P, True), want) < 1e-5
+    assert rel(R.ref_deconv(rows, wt, bt, n, Hi, Wi, P, False), want.permute(0, 2, 3, 1)) < 1e-5
+    # the composition the nodes form in a block: x1 = x + out_proj(o), out = x1 + fc2(gelu_tanh(fc1(LN(x1)))) = transformer_block on
+    # sequences of ONE token, where softmax over a single key is 1 and the attention output o is the value projection of LN1(x)
+    C, nh, Bp = 32, 4, 19
+    w = {"ln1.weight": torch.ones(C), "ln1.bias": torch.zeros(C), "ln2.weight": torch.ones(C), "ln2.bias": torch.zeros(C),
+         "attn.in_proj_weight": torch.randn(3 * C, C, generator=g) / math.sqrt(C), "attn.in_proj_bias": torch.randn(3 * C, generator=g),
+         "attn.out_proj.weight": torch.randn(C, C, generator=g) / math.sqrt(C), "attn.out_proj.bias": torch.randn(C, generator=g),
+         "mlp.0.weight": torch.randn(4 * C, C, generator=g) / math.sqrt(C), "mlp.0.bias": torch.randn(4 * C, generator=g),
+         "mlp.2.weight": torch.randn(C, 4 * C, generator=g) / math.sqrt(4 * C), "mlp.2.bias": torch.randn(C, generator=g)}
+    xb = torch.randn(Bp, 1, C, generator=g)
+    want = TO.transformer_block(w, xb, nh).reshape(Bp, C)
+    x0 = xb.reshape(Bp, C)
+    o = R.ref_linear(R.ref_ln(x0, 1e-5), w["attn.in_proj_weight"][2 * C:], w["attn.in_proj_bias"][2 * C:])
+    x1 = R.ref_branch_out(o, w["attn.out_proj.weight"], w["attn.out_proj.bias"], x0, R.ACT_NONE)
+    hpre = R.ref_linear(R.ref_ln(x1, 1e-5), w["mlp.0.weight"], w["mlp.0.bias"])
+    got = R.ref_branch_out(hpre, w["mlp.2.weight"], w["mlp.2.bias"], x1, R.ACT_GELU_TANH)
+    assert rel(got, want) < 1e-5
+    # dropout: with every element kept and p = 0 the restated mask is the identity; a mask scales what it keeps by 1 / (1 - p)
+    y = torch.randn(8, 9, generator=g)
+    assert torch.equal(R.ref_dropout(y, torch.ones(8, 9), 0.0), y) and R.ref_dropout(y, None, 0.0) is y
+    keep = (torch.rand(8, 9, generator=g) > 0.5).float()
+    assert rel(R.ref_dropout(y, keep, 0.5), keep * y * 2.0) < 1e-6
+
+
+def test_train_node_bars_reject_near_misses():
+    """For every node of tests/test_hip_train_nodes.py a WRONG float64 result of the kind its kernels are able to produce, measured the way
+    the GPU test measures (relative L2, max-norm): the distance from the right result exceeds TWICE the bar -- the largest one -- the GPU
+    test applies to that tensor, in at least one of the two norms (a GPU comparison fails when either norm exceeds its bar).  So the bars
+    see these errors; had one fallen inside, the inputs would have to change, not the bar."""
+    import math
+    import test_hip_train_nodes as R
+    from conftest import rel_err, max_rel
+
+    def seen(wrong, right, bar, what):
+        r, m = rel_err(wrong.detach(), right.detach()), max_rel(wrong.detach(), right.detach())
+        assert r > 2 * bar[0] or m > 2 * bar[1], f"{what}: rel {r:.3e} max {m:.3e} inside twice the bar {bar}"
+        return r, m
+
+    g = torch.Generator().manual_seed(9)
+    f64 = torch.float64
+    # LayerNorm backward: dx = rstd (g - mean(g) - xhat mean(g xhat)) + gskip, at the widest row the GPU test has (the term shrinks as 1 / sqrt(C))
+    M, C = 37, 768
+    x = torch.randn(M, C, generator=g, dtype=f64).requires_grad_()
+    G, Gs = torch.randn(M, C, generator=g, dtype=f64), torch.randn(M, C, generator=g, dtype=f64)
+    xh = R.ref_ln(x, 1e-5)
+    xh.backward(G)
+    rstd = (x.detach().var(-1, unbiased=False, keepdim=True) + 1e-5).rsqrt()
+    no_proj = rstd * (G - G.mean(-1, keepdim=True))
+    assert rel_err(no_proj - rstd * xh.detach() * (G * xh.detach()).mean(-1, keepdim=True), x.grad) < 1e-12      # (the formula is the right one)
+    seen(no_proj, x.grad, R.LARGE_MEAN_BAR, "LayerNorm backward without the mean(g xhat) term")
+    seen(x.grad, x.grad + Gs, R.LARGE_MEAN_BAR, "LayerNorm backward without gskip")
+    # GELU: erf where tanh is meant, on the GPU test's bulk inputs, at the fp32 bar
+    xa = R.act_inputs(2048, g, f64)[len(R.ACT_SPECIAL):]
+    seen(R.ref_act(xa, R.ACT_GELU_ERF), R.ref_act(xa, R.ACT_GELU_TANH), R.F32_BAR, "GELU erf for tanh")
+    xa = xa.clone().requires_grad_()
+    (d_tanh,) = torch.autograd.grad(R.ref_act(xa, R.ACT_GELU_TANH).sum(), xa)
+    (d_erf,) = torch.autograd.grad(R.ref_act(xa, R.ACT_GELU_ERF).sum(), xa)
+    seen(d_erf, d_tanh, R.F32_BAR, "GELU erf derivative for tanh")
+    # dropout at the GPU test's smallest p > 0: another seed's mask; no 1 / (1 - p)
+    p = 0.1
+    y, res = torch.randn(64, 33, generator=g, dtype=f64), torch.randn(64, 33, generator=g, dtype=f64)
+    keep = (torch.rand(64, 33, generator=torch.Generator().manual_seed(1)) >= p).double()
+    keep1 = (torch.rand(64, 33, generator=torch.Generator().manual_seed(2)) >= p).double()
+    right = res + R.ref_dropout(y, keep, p)
+    seen(res + R.ref_dropout(y, keep1, p), right, R.BF16_BAR, "dropout mask of seed + 1")
+    seen(res + keep * y, right, R.BF16_BAR, "dropout without 1 / (1 - p)")
+    seen(keep * y, R.ref_dropout(y, keep, p), R.BF16_BAR, "dropout backward without 1 / (1 - p)")
+    # LinearFn: a K-chunked product that misses its ragged last chunk (1100 = 512 + 512 + 76); dgrad that misses the last chunk of N
+    a, W = torch.randn(300, 1100, generator=g, dtype=f64), torch.randn(96, 1100, generator=g, dtype=f64) / math.sqrt(1100)
+    seen(R.ref_linear(a[:, :1024], W[:, :1024]), R.ref_linear(a, W), R.BF16_BAR, "K chunks without the ragged last one")
+    dy, W2 = torch.randn(257, 1100, generator=g, dtype=f64), torch.randn(1100, 64, generator=g, dtype=f64) / 8.0
+    seen(dy[:, :1024] @ W2[:1024], dy @ W2, R.BF16_BAR, "dgrad without the ragged last chunk of N")
+    # one weight used twice: dW from one use; a slot overwritten instead of added to
+    a1, a2 = torch.randn(4096, 256, generator=g, dtype=f64), torch.randn(4096, 256, generator=g, dtype=f64)
+    g1, g2 = torch.randn(4096, 256, generator=g, dtype=f64), torch.randn(4096, 256, generator=g, dtype=f64)
+    dW = g1.t() @ a1 + g2.t() @ a2
+    seen(g1.t() @ a1, dW, R.BF16_BAR, "dW from one of two BPTT uses")
+    fill = R.randn((256, 256), g, scale=R.SLOT_FILL).double()      # (the pre-fill of test_hip_train_nodes.param)
+    seen(dW - fill, dW, R.BF16_BAR, "a slot overwritten (read back as gradient = slot - pre-fill)")
+    seen(2 * dW, dW, R.BF16_BAR, "a slot added to twice")
+    # the smallest gradient that meets the same pre-fill: the 77 x 20 x 44 case
+    dW_small = torch.randn(77, 20, generator=g, dtype=f64).t() @ torch.randn(77, 44, generator=g, dtype=f64)
+    seen(dW_small - R.randn((20, 44), g, scale=R.SLOT_FILL).double(), dW_small, R.BF16_BAR, "a small slot overwritten")
+    # db from the wrong axis (a square dy, so that the shapes agree)
+    dsq = torch.randn(256, 256, generator=g, dtype=f64)
+    seen(dsq.sum(1), dsq.sum(0), R.BF16_BAR, "db from the wrong axis")
+    # conv weight gradient with (kh, kw) swapped
+    xi = torch.randn(2, 6, 16, 24, generator=g, dtype=f64)
+    wc = (torch.randn(10, 6, 2, 2, generator=g, dtype=f64) / 5.0).requires_grad_()
+    Gc = torch.randn(2 * 8 * 12, 10, generator=g, dtype=f64)
+    (R.ref_patch_embed(xi, wc, None, 2) * Gc).sum().backward()
+    seen(wc.grad.transpose(-1, -2), wc.grad, R.BF16_BAR, "patch-conv dW with (kh, kw) swapped")
+    ar = torch.randn(2 * 5 * 7, 10, generator=g, dtype=f64)
+    wt = (torch.randn(10, 6, 4, 4, generator=g, dtype=f64) / 3.0).requires_grad_()
+    Gt = torch.randn(2, 6, 20, 28, generator=g, dtype=f64)
+    (R.ref_deconv(ar, wt, None, 2, 5, 7, 4, True) * Gt).sum().backward()
+    seen(wt.grad.transpose(-1, -2), wt.grad, R.BF16_BAR, "deconv dW with (kh, kw) swapped")
+
+
 @pytest.mark.parametrize("full", [False, True])
 def test_bench_side_legs_run_only_with_full(monkeypatch, capsys, full):
     """A plain `bench.py` run times the headline leg and prints its line; the roofline pass (and the train, CPU-baseline and side-workload
