@@ -8,7 +8,7 @@ evaluates with torch so that their gradients come for free.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch.autograd import Function
@@ -196,12 +196,9 @@ def reset_backward_state(after: bool = False):
     callback of THIS backward pass is queued"; a backward pass that raises (OOM, a kernel error, KeyboardInterrupt) drops its
     callbacks, so the flag is keyed to the graph task and additionally cleared here: train_step* call this before and -- in a
     finally -- after every loss.backward(), so operands recorded by a dead pass can never reach a later step's gradient slots."""
-    _DEFER["pending"].clear()
+    _reset_recorded()
     _FOLD_PENDING.clear()
     _drop_frame_accumulators()
-    _DEFER["bytes"] = 0
-    _DEFER["armed"] = False
-    _DEFER["task"] = -1
     _SIDE["armed"] = False
     _SIDE["task"] = -1
     if _SIDE["stream"] is not None:
@@ -236,96 +233,101 @@ def _wgrad_workspace(device) -> torch.Tensor:
 WGRAD_JOBS = _O.register("TANTE_WGRAD_JOBS_PER_LAUNCH", 4, __name__, "WGRAD_JOBS")      # weights per shared launch (1: one launch per weight)
 
 
-def _flush_wgrads(slot: Optional[torch.Tensor] = None):
-    pend = _DEFER["pending"]
-    keys = [k for k in pend if slot is None or k[0] == slot.data_ptr()]
-    if slot is None and WGRAD_JOBS > 1 and len(keys) > 1:
-        # the end-of-pass flush: consecutive recorded weights (the four of a block sit next to each other) as the jobs of one launch
-        ents = [pend.pop(k) for k in keys]
-        dev = ents[0][0].device
-        ws = _wgrad_workspace(dev)
-        i = 0
-        while i < len(ents):
-            grp = ents[i: i + WGRAD_JOBS]
-            if any(e[5] != grp[0][5] or e[0].device != dev for e in grp):      # mixed compute modes / devices: one at a time
-                grp = grp[:1]
-            i += len(grp)
-            jobs = (L.WgradJob * len(grp))()
-            keep = []
-            for jb, (gW, gb, M, N, Kk, comp, lay, uses) in zip(jobs, grp):
-                n = len(uses)
-                U = (L.RowMat * n)(*[_rm_linear(dy) for dy, _ in uses])
-                V = (L.RowMat * n)(*[_rm_linear(a) for _, a in uses])
-                keep.append((U, V))
-                jb.U, jb.V, jb.n_seg, jb.R, jb.I, jb.J = U, V, n, M, N, Kk
-                jb.dW, jb.dbias = gW.data_ptr(), None if gb is None else gb.data_ptr()
-                jb.layout, jb.P, jb.C_other, jb.swap = lay[0], lay[1], lay[2], int(lay[3])
-            L.check(L.lib().tante_wgrad_jobs_ws(jobs, len(grp), grp[0][5], ws.data_ptr(), ws.numel(), _s()), "tante_wgrad_jobs")
-        keys = []
-    for k in keys:
-        gW, gb, M, N, Kk, comp, lay, uses = pend.pop(k)
-        n = len(uses)
-        U = (L.RowMat * n)(*[_rm_linear(dy) for dy, _ in uses])
-        V = (L.RowMat * n)(*[_rm_linear(a) for _, a in uses])
-        layout, P, Co, swap = lay
-        ws = _wgrad_workspace(gW.device)
-        L.check(L.lib().tante_wgrad_multi_ws(C.byref(U), C.byref(V), n, M, N, Kk, gW.data_ptr(), None if gb is None else gb.data_ptr(), layout, P,
-                                             Co, int(swap), comp, 1, ws.data_ptr(), ws.numel(), _s()), "tante_wgrad_multi")
-    if slot is None:
-        _DEFER["armed"] = False
-        _DEFER["task"] = -1
-        _DEFER["bytes"] = 0
+class PendingWgrad(NamedTuple):
+    """One recorded weight: dW[N x K] (and db) += over `uses`, a list of (dy, a) operand pairs of M dense bf16 rows each."""
+    gW: torch.Tensor
+    gb: Optional[torch.Tensor]
+    M: int
+    N: int
+    K: int
+    comp: int
+    lay: tuple      # (output layout, P, C_other, swap) as in tante_wgrad
+    uses: list
 
 
-_FOLD_PENDING = []      # folds whose backward waits for the end of the pass: (acc buffer, GW, Gb, W, gamma, beta, dW, db, dgamma, dbeta, N, K)
+class PendingFold(NamedTuple):
+    """One FoldFn backward that waits for the end of the pass: accumulators (GW, Gb: views of acc_buf) -> the four gradient slots."""
+    acc_buf: torch.Tensor
+    GW: torch.Tensor
+    Gb: torch.Tensor
+    W: torch.Tensor
+    gamma: torch.Tensor
+    beta: torch.Tensor
+    dW: torch.Tensor
+    db: Optional[torch.Tensor]
+    dgamma: torch.Tensor
+    dbeta: torch.Tensor
+    N: int
+    K: int
 
 
-def _flush_folds():
-    """The recorded FoldFn backwards as ONE launch (tante_fold_bwd_multi), after the weight-gradient launches that fill their accumulators."""
-    if not _FOLD_PENDING:
+_FOLD_PENDING = []      # PendingFold records of this backward pass
+HOLD_FLUSH = [False]         # True: the engine callback leaves the recorded work alone (train.GraphedTrainStep flushes in a graph of its own)
+FLUSH_DRIVER = [None]        # callable() that runs the end-of-pass flush itself (train.py: flush_plan + flush_run around the all-reduce calls)
+
+
+def _reset_recorded(armed: bool = False, task: int = -1):
+    """Drop the recorded weights; 'armed' / 'task': the engine's end-of-pass callback of that backward pass is queued."""
+    _DEFER["pending"].clear()
+    _DEFER["bytes"] = 0
+    _DEFER["armed"], _DEFER["task"] = armed, task
+
+
+def _wgrad_groups(entries, per_launch: Optional[int] = None):
+    """Recorded weights -> the launch groups: consecutive ones in recording order (the four of a block sit next to each other), at most
+    WGRAD_JOBS each; weights on different devices do not share a launch."""
+    per_launch = max(1, WGRAD_JOBS if per_launch is None else per_launch)
+    groups, i = [], 0
+    while i < len(entries):
+        grp = entries[i: i + per_launch]
+        if any(e.gW.device != grp[0].gW.device for e in grp):
+            grp = grp[:1]
+        i += len(grp)
+        groups.append(grp)
+    return groups
+
+
+def _launch_group(grp):
+    """The weights of one group as the jobs of ONE tante_wgrad_jobs_ws call (a single job runs as tante_wgrad_multi_ws there)."""
+    ws = _wgrad_workspace(grp[0].gW.device)
+    jobs = (L.WgradJob * len(grp))()
+    keep = []      # the operand arrays the jobs point to, alive until the call returns
+    for jb, e in zip(jobs, grp):
+        n = len(e.uses)
+        U = (L.RowMat * n)(*[_rm_linear(dy) for dy, _ in e.uses])
+        V = (L.RowMat * n)(*[_rm_linear(a) for _, a in e.uses])
+        keep.append((U, V))
+        jb.U, jb.V, jb.n_seg, jb.R, jb.I, jb.J = U, V, n, e.M, e.N, e.K
+        jb.dW, jb.dbias = e.gW.data_ptr(), None if e.gb is None else e.gb.data_ptr()
+        jb.layout, jb.P, jb.C_other, jb.swap = e.lay[0], e.lay[1], e.lay[2], int(e.lay[3])
+    L.check(L.lib().tante_wgrad_jobs_ws(jobs, len(grp), grp[0].comp, ws.data_ptr(), ws.numel(), _s()), "tante_wgrad_jobs")
+
+
+def _launch_folds(folds):
+    """FoldFn backwards as ONE launch (tante_fold_bwd_multi), after the weight-gradient launches that fill their accumulators."""
+    if not folds:
         return
     if _SIDE["stream"] is not None:      # the accumulators are written by weight-gradient kernels on the side stream
         torch.cuda.current_stream().wait_stream(_SIDE["stream"])
-    n = len(_FOLD_PENDING)
-    arr = (L.Fold * n)()
-    for f, (buf, GW, Gb, W, gamma, beta, dW, db, dg, dbt, N, Kk) in zip(arr, _FOLD_PENDING):
-        f.GW, f.Gb, f.W, f.gamma, f.beta = GW.data_ptr(), Gb.data_ptr(), W.data_ptr(), gamma.data_ptr(), beta.data_ptr()
-        f.dW, f.db, f.dgamma, f.dbeta = dW.data_ptr(), None if db is None else db.data_ptr(), dg.data_ptr(), dbt.data_ptr()
-        f.N, f.K = N, Kk
-    L.check(L.lib().tante_fold_bwd_multi(C.byref(arr), n, 1, _s()), "tante_fold_bwd_multi")
-    for ent in _FOLD_PENDING:
-        _FOLD_DIRTY.pop(id(ent[0]), None)      # the kernel left the accumulators zeroed
-    _FOLD_PENDING.clear()
+    arr = (L.Fold * len(folds))()
+    for f, p in zip(arr, folds):
+        f.GW, f.Gb, f.W, f.gamma, f.beta = p.GW.data_ptr(), p.Gb.data_ptr(), p.W.data_ptr(), p.gamma.data_ptr(), p.beta.data_ptr()
+        f.dW, f.db, f.dgamma, f.dbeta = p.dW.data_ptr(), None if p.db is None else p.db.data_ptr(), p.dgamma.data_ptr(), p.dbeta.data_ptr()
+        f.N, f.K = p.N, p.K
+    L.check(L.lib().tante_fold_bwd_multi(C.byref(arr), len(folds), 1, _s()), "tante_fold_bwd_multi")
+    for p in folds:
+        _FOLD_DIRTY.pop(id(p.acc_buf), None)      # the kernel left the accumulators zeroed
 
 
-PRE_FLUSH_HOOK = [None]      # callable() run before the end-of-pass flush (train.py: the early part of the gradient all-reduce)
-HOLD_FLUSH = [False]         # True: the engine callback leaves the recorded work alone (train.GraphedTrainStep flushes in a graph of its own)
-
-
-def flush_write_range(bucket: torch.Tensor):
-    """(first element, end element) of `bucket` (a flat gradient buffer) that the pending flush will write: the deferred linears' weight /
-    bias slots and the folds' four outputs, as far as they are views of the bucket (the folded weights' own accumulators are private
-    buffers).  None when the flush writes nothing inside it."""
-    base, esz = bucket.data_ptr(), bucket.element_size()
-    end = base + bucket.numel() * esz
-    lo, hi = None, 0
-
-    def add(t):
-        nonlocal lo, hi
-        if t is None:
-            return
-        a = t.data_ptr()
-        if a < base or a >= end:
-            return
-        lo = a if lo is None else min(lo, a)
-        hi = max(hi, a + t.numel() * t.element_size())
-    for ent in _DEFER["pending"].values():
-        add(ent[0])
-        add(ent[1])
-    for ent in _FOLD_PENDING:
-        for t in ent[6:10]:
-            add(t)
-    return None if lo is None else ((lo - base) // esz, (min(hi, end) - base) // esz)
+def _flush_wgrads(slot: Optional[torch.Tensor] = None):
+    """A partial flush in the middle of a pass: the recorded uses of the weight whose accumulator is `slot`, each entry a launch of its
+    own -- or, without one, every recorded weight in the usual groups.  The folds and the queued end-of-pass callback stay as they are."""
+    pend = _DEFER["pending"]
+    ents = [pend.pop(k) for k in [k for k in pend if slot is None or k[0] == slot.data_ptr()]]
+    for grp in _wgrad_groups(ents, None if slot is None else 1):
+        _launch_group(grp)
+    if slot is None:
+        _DEFER["bytes"] = 0
 
 
 # ---- the end-of-pass flush in SEGMENTS (round 6: the data-parallel all-reduce pipelined against it, dist.GradAllReduce) ------------------
@@ -334,26 +336,15 @@ def flush_write_range(bucket: torch.Tensor):
 # launch.  In segments, every fold runs right behind the launch group that fills its accumulator, so a block's whole span of the bucket is
 # final when its group is: the spans of the first segments travel while the later segments still compute.
 def _pending_groups():
-    ents = list(_DEFER["pending"].values())
-    groups = []
-    if WGRAD_JOBS > 1 and len(ents) > 1:
-        i = 0
-        while i < len(ents):
-            grp = ents[i: i + WGRAD_JOBS]
-            if any(e[5] != grp[0][5] or e[0].device != grp[0][0].device for e in grp):
-                grp = grp[:1]
-            i += len(grp)
-            groups.append(grp)
-    else:
-        groups = [[e] for e in ents]
-    # fold f is ready behind the last group that writes its accumulator (group -1: nothing pending writes it)
+    groups = _wgrad_groups(list(_DEFER["pending"].values()))
+    # fold f is ready behind the last group that writes its accumulator (group 0 when nothing pending writes it)
     ready = {}
     for fi, f in enumerate(_FOLD_PENDING):
-        last = -1
+        last = 0
         for gi, grp in enumerate(groups):
-            if any(e[0].data_ptr() == f[1].data_ptr() for e in grp):
+            if any(e.gW.data_ptr() == f.GW.data_ptr() for e in grp):
                 last = gi
-        ready.setdefault(max(last, 0), []).append(fi)
+        ready.setdefault(last, []).append(fi)
     return groups, ready
 
 
@@ -369,7 +360,7 @@ def flush_plan(bucket: torch.Tensor, segments: int):
     groups, ready = _pending_groups()
     if not groups and not _FOLD_PENDING:
         return None
-    fold_acc = {f[1].data_ptr() for f in _FOLD_PENDING}
+    fold_acc = {f.GW.data_ptr() for f in _FOLD_PENDING}
     base, esz, n = bucket.data_ptr(), bucket.element_size(), bucket.numel()
     owner = {}      # (lo, hi) -> the LAST segment that writes it
     bounds = _segment_bounds(len(groups), segments)
@@ -385,15 +376,16 @@ def flush_plan(bucket: torch.Tensor, segments: int):
         owner[(lo, min(n, lo + t.numel()))] = seg
     for gi, grp in enumerate(groups):
         for e in grp:
-            if e[0].data_ptr() not in fold_acc:
-                add(e[0], seg_of(gi))
-                add(e[1], seg_of(gi))
+            if e.gW.data_ptr() not in fold_acc:
+                add(e.gW, seg_of(gi))
+                add(e.gb, seg_of(gi))
         for fi in ready.get(gi, ()):
-            for t in _FOLD_PENDING[fi][6:10]:
+            f = _FOLD_PENDING[fi]
+            for t in (f.dW, f.db, f.dgamma, f.dbeta):
                 add(t, seg_of(gi))
     if not groups:
         for f in _FOLD_PENDING:
-            for t in f[6:10]:
+            for t in (f.dW, f.db, f.dgamma, f.dbeta):
                 add(t, 0)
     n_seg = len(bounds) - 1
     segs = [[] for _ in range(n_seg)]
@@ -417,79 +409,30 @@ def flush_plan(bucket: torch.Tensor, segments: int):
 
 
 def flush_steps(segments: int):
-    """Generator form of the flush: every next() launches one segment (its launch groups, each followed by the folds it completes) and
-    yields the segment's index; exhausting it resets the recorded state.  (train.GraphedTrainStep captures each next() as a graph.)"""
+    """Generator form of the flush: every next() launches one segment and yields its index.  One segment is the plain flush: every group,
+    then the folds as ONE launch; with more, each group is followed at once by the folds it completes.  The last segment also resets the
+    recorded state.  (train.GraphedTrainStep captures each next() as a graph.)"""
     groups, ready = _pending_groups()
     bounds = _segment_bounds(len(groups), segments)
     n_seg = len(bounds) - 1
-    eager = n_seg > 1
     for s in range(n_seg):
         for gi in range(bounds[s], bounds[s + 1]):
             _launch_group(groups[gi])
-            if eager and ready.get(gi):
-                _launch_folds([_FOLD_PENDING[fi] for fi in ready[gi]])
-        if s == n_seg - 1:      # the last segment also resets the recorded state (before its yield: the caller may never come back)
-            _DEFER["pending"].clear()
-            _DEFER["armed"], _DEFER["task"], _DEFER["bytes"] = False, -1, 0
-            if eager:
-                if not groups:
-                    _launch_folds(list(_FOLD_PENDING))
-                _FOLD_PENDING.clear()
-            else:
-                _flush_folds()
+            if n_seg > 1:
+                _launch_folds([_FOLD_PENDING[fi] for fi in ready.get(gi, ())])
+        if s == n_seg - 1:      # (before the yield: the caller may never come back)
+            _reset_recorded()
+            if n_seg == 1:
+                _launch_folds(list(_FOLD_PENDING))
+            _FOLD_PENDING.clear()
         yield s
 
 
 def flush_run(segments: int, on_segment=None):
-    """Run the pending flush in `segments` segments (flush_plan's partition), calling on_segment(s) behind each.  One segment is the plain
-    flush: the folds as ONE launch at the end."""
+    """Run the pending flush in `segments` segments (flush_plan's partition), calling on_segment(s) behind each."""
     for s in flush_steps(segments):
         if on_segment is not None:
             on_segment(s)
-
-
-def _launch_group(grp):
-    dev = grp[0][0].device
-    ws = _wgrad_workspace(dev)
-    if WGRAD_JOBS > 1 and len(_DEFER["pending"]) > 1:
-        jobs = (L.WgradJob * len(grp))()
-        keep = []
-        for jb, (gW, gb, M, N, Kk, comp, lay, uses) in zip(jobs, grp):
-            n = len(uses)
-            U = (L.RowMat * n)(*[_rm_linear(dy) for dy, _ in uses])
-            V = (L.RowMat * n)(*[_rm_linear(a) for _, a in uses])
-            keep.append((U, V))
-            jb.U, jb.V, jb.n_seg, jb.R, jb.I, jb.J = U, V, n, M, N, Kk
-            jb.dW, jb.dbias = gW.data_ptr(), None if gb is None else gb.data_ptr()
-            jb.layout, jb.P, jb.C_other, jb.swap = lay[0], lay[1], lay[2], int(lay[3])
-        L.check(L.lib().tante_wgrad_jobs_ws(jobs, len(grp), grp[0][5], ws.data_ptr(), ws.numel(), _s()), "tante_wgrad_jobs")
-        return
-    for gW, gb, M, N, Kk, comp, lay, uses in grp:
-        n = len(uses)
-        U = (L.RowMat * n)(*[_rm_linear(dy) for dy, _ in uses])
-        V = (L.RowMat * n)(*[_rm_linear(a) for _, a in uses])
-        layout, P, Co, swap = lay
-        L.check(L.lib().tante_wgrad_multi_ws(C.byref(U), C.byref(V), n, M, N, Kk, gW.data_ptr(), None if gb is None else gb.data_ptr(), layout, P,
-                                             Co, int(swap), comp, 1, ws.data_ptr(), ws.numel(), _s()), "tante_wgrad_multi")
-
-
-def _launch_folds(folds):
-    if not folds:
-        return
-    if _SIDE["stream"] is not None:
-        torch.cuda.current_stream().wait_stream(_SIDE["stream"])
-    n = len(folds)
-    arr = (L.Fold * n)()
-    for f, (buf, GW, Gb, W, gamma, beta, dW, db, dg, dbt, N, Kk) in zip(arr, folds):
-        f.GW, f.Gb, f.W, f.gamma, f.beta = GW.data_ptr(), Gb.data_ptr(), W.data_ptr(), gamma.data_ptr(), beta.data_ptr()
-        f.dW, f.db, f.dgamma, f.dbeta = dW.data_ptr(), None if db is None else db.data_ptr(), dg.data_ptr(), dbt.data_ptr()
-        f.N, f.K = N, Kk
-    L.check(L.lib().tante_fold_bwd_multi(C.byref(arr), n, 1, _s()), "tante_fold_bwd_multi")
-    for ent in folds:
-        _FOLD_DIRTY.pop(id(ent[0]), None)
-
-
-FLUSH_DRIVER = [None]        # callable() that runs the end-of-pass flush itself (train.py: flush_plan + flush_run around the all-reduce calls)
 
 
 def flush_deferred_wgrads(force: bool = False):
@@ -497,14 +440,10 @@ def flush_deferred_wgrads(force: bool = False):
     if HOLD_FLUSH[0] and not force:
         return
     if FLUSH_DRIVER[0] is not None:
-        _join_side()
+        _join_side()                     # (weight gradients issued on the side stream, when that option is on, are part of "final")
         FLUSH_DRIVER[0]()
         return
-    if PRE_FLUSH_HOOK[0] is not None:
-        _join_side()                     # (weight gradients issued on the side stream, when that option is on, are part of "final")
-        PRE_FLUSH_HOOK[0]()
-    _flush_wgrads(None)
-    _flush_folds()
+    flush_run(1)
 
 
 def _defer_wgrad(gW, gb, dy, a, M, N, Kk, comp, lay=(L.W_LINEAR, 0, 0, False)) -> bool:
@@ -520,19 +459,15 @@ def _defer_wgrad(gW, gb, dy, a, M, N, Kk, comp, lay=(L.W_LINEAR, 0, 0, False)) -
             torch.autograd.Variable._execution_engine.queue_callback(flush_deferred_wgrads)
         except RuntimeError:          # not inside a backward pass: nothing would flush it
             return False
-        _DEFER["pending"].clear()     # leftovers of a backward pass that died half-way must not leak into this one
-        _DEFER["bytes"] = 0
-        _DEFER["armed"], _DEFER["task"] = True, task
+        _reset_recorded(True, task)   # leftovers of a backward pass that died half-way must not leak into this one
     key = (gW.data_ptr(), M, N, Kk, comp, lay)
     ent = _DEFER["pending"].get(key)
     if ent is None:
-        ent = _DEFER["pending"][key] = (gW, gb, M, N, Kk, comp, lay, [])
-    ent[7].append((dy, a))
+        ent = _DEFER["pending"][key] = PendingWgrad(gW, gb, M, N, Kk, comp, lay, [])
+    ent.uses.append((dy, a))
     _DEFER["bytes"] += dy.numel() * dy.element_size() + a.numel() * a.element_size()
     if _DEFER["bytes"] > int(DEFER_MAX_GB * 2 ** 30):      # a very large model / batch: do not sit on more activations than this
-        armed, task = _DEFER["armed"], _DEFER["task"]
-        _flush_wgrads(None)
-        _DEFER["armed"], _DEFER["task"] = armed, task                # the engine callback is still queued for the rest of this backward pass
+        _flush_wgrads()                  # (the engine callback stays queued for the rest of this backward pass)
     return True
 
 
@@ -626,7 +561,7 @@ class FoldFn(Function):
             # (flush_deferred_wgrads, the engine's end-of-pass callback that the recorded uses queued)
             slots = [_grad_slot(q) for q in ctx.params]
             if all(g is not None for g, q in zip(slots, ctx.params) if q is not None):
-                _FOLD_PENDING.append((ctx.acc_buf, GW, Gb, W, gamma, beta, slots[0], slots[1], slots[2], slots[3], N, Kk))
+                _FOLD_PENDING.append(PendingFold(ctx.acc_buf, GW, Gb, W, gamma, beta, *slots, N, Kk))
                 return None, None, None, None, None
         _flush_wgrads(GW)                    # the recorded uses of this folded weight run now, as one launch
         if _SIDE["stream"] is not None:      # the accumulators are written by weight-gradient kernels on the side stream

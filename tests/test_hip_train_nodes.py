@@ -801,3 +801,138 @@ def test_colsum_scalar_forms_and_accumulation(dev, outer, Cc, off):
     got = A.colsum(xd, outer, Cc, 1, into=into)
     assert got is into
     close(into.double().cpu() - fill.double(), ref, tag + " into", bar=F32_BAR, floor=floor)
+
+
+# ---- the end-of-pass flush: one graph, every way of running it ---------------------------------------------------------------------------
+FL_N, FL_M, FL_USES, FL_FOLDED = 128, 64, 2, (1, 4)
+FL_ENTRIES = WGRAD_ENTRIES + ("tante_fold_bwd_multi", "tante_fold_bwd", "tante_fold_bwd_clear")
+FL_KINDS = ("W", "b", "gamma", "beta")
+_FL_DATA = {}
+
+
+def _flush_graph_data():
+    """CPU-seeded inputs of the flush graph and its float64 gradients, computed once: six 128 x 128 linears with biases, weights 1 and 4
+    behind a LayerNorm fold (We = W diag(gamma), be = b + W beta), every weight used twice on 64 rows of its own; the loss is
+    sum(y * G) over the twelve uses.  layout: (weight, kind, offset, shape) of every parameter in the flat buffers."""
+    if _FL_DATA:
+        return _FL_DATA
+    N = FL_N
+    g = torch.Generator().manual_seed(2024)
+    layout, off, vals = [], 0, {}
+    for i in range(6):
+        for kind, shape in [("W", (N, N)), ("b", (N,))] + ([("gamma", (N,)), ("beta", (N,))] if i in FL_FOLDED else []):
+            layout.append((i, kind, off, shape))
+            vals[(i, kind)] = {"W": lambda: randn(shape, g, scale=1.0 / math.sqrt(N)).to(torch.bfloat16).float(),
+                               "gamma": lambda: randn(shape, g, scale=0.25, shift=1.0)}.get(kind, lambda: randn(shape, g))()
+            off += math.prod(shape)
+    a = {(i, u): randn((FL_M, N), g, torch.bfloat16) for i in range(6) for u in range(FL_USES)}
+    G = {k: randn((FL_M, N), g, torch.bfloat16) for k in a}
+    fill = randn((off,), g, scale=SLOT_FILL)
+    p64 = {k: v.double().requires_grad_() for k, v in vals.items()}
+    loss = 0.0
+    for (i, u), au in a.items():
+        W, b = p64[(i, "W")], p64[(i, "b")]
+        if i in FL_FOLDED:
+            W, b = W * p64[(i, "gamma")][None, :], b + W @ p64[(i, "beta")]
+        loss = loss + (ref_linear(au.double(), W, b) * G[(i, u)].double()).sum()
+    loss.backward()
+    ref = torch.cat([p64[(i, kind)].grad.flatten() for i, kind, _, _ in layout])
+    _FL_DATA.update(layout=layout, n=off, vals=vals, a=a, G=G, fill=fill, ref=ref)
+    return _FL_DATA
+
+
+def _flush_graph_run(dev, spy, driver=None):
+    """One backward of the graph from the same inputs -> (the flat gradient buffer, calls per library entry).  Parameters and their
+    pre-filled .grad are views of flat buffers; a folded pair is wired as train_forward._folded does.  What run_backward does, with the
+    state looked at BEFORE its closing reset (which would empty the lists and zero the accumulators whatever the flush left)."""
+    L, A, _ = _lib_mods()
+    d = _flush_graph_data()
+    flat_p, flat_g = torch.empty(d["n"], device=dev), d["fill"].to(dev)
+    P = {}
+    for i, kind, off, shape in d["layout"]:
+        n = math.prod(shape)
+        flat_p[off: off + n] = d["vals"][(i, kind)].flatten().to(dev)
+        p = P[(i, kind)] = torch.nn.Parameter(flat_p[off: off + n].view(shape))
+        p.grad = flat_g[off: off + n].view(shape)
+    terms = []
+    for i in range(6):
+        W, b = P[(i, "W")], P[(i, "b")]
+        if i in FL_FOLDED:
+            W, b, gw, gb = A.FoldFn.apply(W, b, P[(i, "gamma")], P[(i, "beta")])
+            W._tante_grad, b._tante_grad = gw, gb
+        for u in range(FL_USES):
+            y = A.LinearFn.apply(d["a"][(i, u)].to(dev), W, b, None, L.BF16, torch.bfloat16)
+            terms.append(functional(y, d["G"][(i, u)].to(dev)))
+    loss = torch.stack(terms).sum()
+    before = dict(spy.n)
+    A.reset_backward_state()
+    A.FLUSH_DRIVER[0] = driver
+    try:
+        loss.backward()
+        torch.cuda.synchronize()
+        assert not A._DEFER["pending"] and not A._DEFER["armed"] and not A._FOLD_PENDING and not A._FOLD_DIRTY
+        for i in FL_FOLDED:
+            assert not bool(P[(i, "W")]._tante_fold_acc.any()), f"fold accumulator of weight {i} not left zeroed"
+    finally:
+        A.FLUSH_DRIVER[0] = None
+        A.reset_backward_state(after=True)
+    return flat_g, {e: spy.n[e] - before[e] for e in spy.n}
+
+
+def _flush_kind(flat, kind):
+    d = _flush_graph_data()
+    return torch.cat([flat[off: off + math.prod(shape)] for _, k, off, shape in d["layout"] if k == kind])
+
+
+def _flush_close(flat_g, tag):
+    """pre-fill + gradient in every slot, per kind of parameter, at the fp32 bar (exact bf16 cotangents, 2 x 64 terms; the fold's outputs
+    are fp32 products and 128-term sums of the accumulated gradients)."""
+    d = _flush_graph_data()
+    got = flat_g.detach().double().cpu() - d["fill"].double()
+    for kind in FL_KINDS:
+        close(_flush_kind(got, kind), _flush_kind(d["ref"], kind), f"flush graph {tag} d{kind}", bar=F32_BAR)
+
+
+def test_flush_paths_agree(dev, monkeypatch):
+    """The same backward run by the engine callback alone, by a FLUSH_DRIVER that calls flush_run(1), by one that calls flush_run(2), and
+    with one weight per launch.  Recording order is the reverse of the forward's: groups (5, 4, 3, 2) and (1, 0), a fold behind each.
+    * callback, flush_run(1), flush_run(2): 2 shared launches; the folds as one launch, one launch, two launches; on_segment(0), (1).
+      The weight and bias slots are equal bit for bit (the shared launches sum their split-R partials in a fixed order, and the fold
+      kernel's dW / db have one writer per element).  dgamma / dbeta are NOT compared bit for bit: the fold kernel adds the partial
+      column sums of its 128 / 16 = 8 row slabs onto the slot with atomics, in the order the workgroups happen to arrive.
+    * one weight per launch: 6 launches, one fold launch.
+    Every run meets the fp32 bar against float64 in every slot and leaves no recorded state and zeroed accumulators behind."""
+    _, A, _ = _lib_mods()
+    spy = Spy(monkeypatch, entries=FL_ENTRIES)
+    g1, n1 = _flush_graph_run(dev, spy)
+    g2, n2 = _flush_graph_run(dev, spy, driver=lambda: A.flush_run(1))
+    segs = []
+    g3, n3 = _flush_graph_run(dev, spy, driver=lambda: A.flush_run(2, on_segment=segs.append))
+    with _with_option("TANTE_WGRAD_JOBS_PER_LAUNCH", 1):
+        g4, n4 = _flush_graph_run(dev, spy)
+    for tag, gr in (("callback", g1), ("flush_run(1)", g2), ("flush_run(2)", g3), ("one per launch", g4)):
+        _flush_close(gr, tag)
+    for kind in FL_KINDS:
+        same = [torch.equal(_flush_kind(g1, kind), _flush_kind(o, kind)) for o in (g2, g3)]
+        print(f"flush graph d{kind}: callback == flush_run(1) {same[0]}, == flush_run(2) {same[1]}")
+    for kind in ("W", "b"):
+        exact(_flush_kind(g2, kind), _flush_kind(g1, kind), f"flush graph d{kind}: flush_run(1) against the callback")
+        exact(_flush_kind(g3, kind), _flush_kind(g1, kind), f"flush graph d{kind}: flush_run(2) against the callback")
+    assert segs == [0, 1]
+    for n, groups, folds in ((n1, 2, 1), (n2, 2, 1), (n3, 2, 2), (n4, 6, 1)):
+        assert n["tante_wgrad_multi_ws"] + n["tante_wgrad_jobs_ws"] == groups and n["tante_fold_bwd_multi"] == folds, n
+        assert n["tante_wgrad_ws"] == n["tante_fold_bwd"] == n["tante_fold_bwd_clear"] == 0, n
+    assert spy.deferred == [True] * (4 * 6 * FL_USES)
+
+
+def test_flush_overflow_in_the_middle_of_a_pass(dev, monkeypatch):
+    """TANTE_WGRAD_DEFER_MAX_GB at two and a half uses' operands (a use records 2 x 64 x 128 bf16 values = 32 KiB): every third of the
+    twelve uses runs what is recorded so far, so most weights' two uses land in different launches.  The folds still wait for the end of
+    the pass and run once; the slots hold pre-fill + gradient; nothing is left behind."""
+    spy = Spy(monkeypatch, entries=FL_ENTRIES)
+    with _with_option("TANTE_WGRAD_DEFER_MAX_GB", 2.5 * (2 * FL_M * FL_N * 2) / 2 ** 30):
+        g5, n5 = _flush_graph_run(dev, spy)
+    _flush_close(g5, "overflow")
+    assert n5["tante_wgrad_multi_ws"] + n5["tante_wgrad_jobs_ws"] == 4 and n5["tante_fold_bwd_multi"] == 1, n5
+    assert n5["tante_wgrad_ws"] == n5["tante_fold_bwd"] == n5["tante_fold_bwd_clear"] == 0, n5
+    assert spy.deferred == [True] * (6 * FL_USES)

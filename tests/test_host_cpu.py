@@ -452,6 +452,90 @@ def test_set_option_reaches_host_and_library_switches():
         assert "environ" not in src.replace('environ.get("RANK"', ""), f
 
 
+def test_flush_plan_partitions_the_bucket_by_launch_group():
+    """autograd.flush_plan and the grouping of recorded weights read only data_ptr(), numel() and device: six recorded 128 x 128 weights
+    (one without a bias slot) over a flat fp32 bucket, two of them the private accumulators of folds whose four outputs (one without
+    a bias slot) lie in the bucket.  Four per launch: groups of 4 and 2; every bucket element in exactly one of early / segs[i]; a
+    weight's slots in its group's segment, a fold's outputs in the segment of the group that writes its accumulator.  One per launch:
+    six groups of one, three segments of two."""
+    import tante_amd
+    from tante_amd import autograd as A
+    N = Kk = 128
+    W, V = N * Kk, N
+    bucket = torch.zeros(100 + 6 * (W + 3 * V) + 50)
+    pos = [100]                      # the first 100 and the last 50 elements belong to nothing recorded
+
+    def carve(n, shape=None):
+        t = bucket[pos[0]: pos[0] + n]
+        pos[0] += n
+        return t if shape is None else t.view(shape)
+    ents, folds, written, gaps = [], [], [], [(0, 100)]      # written: (view of the bucket, index of the weight whose group finalises it)
+    for i in range(6):
+        if i in (1, 4):
+            acc = torch.zeros(W + V)
+            gW, gb = acc[:W].view(N, Kk), acc[W:]
+            dg, dbt, dW = carve(V), carve(V), carve(W, (N, Kk))
+            db = carve(V) if i == 1 else None
+            folds.append(A.PendingFold(acc, gW, gb, torch.zeros(N, Kk), torch.ones(Kk), torch.zeros(Kk), dW, db, dg, dbt, N, Kk))
+            written += [(t, i) for t in (dg, dbt, dW, db) if t is not None]
+        else:
+            gW = carve(W, (N, Kk))
+            gb = carve(V) if i != 3 else None
+            written += [(t, i) for t in (gW, gb) if t is not None]
+        if i in (3, 4):              # the bias slot nothing writes: final before the flush starts
+            gaps.append((pos[0], pos[0] + V))
+            pos[0] += V
+        ents.append(A.PendingWgrad(gW, gb, 64, N, Kk, A.L.BF16, (A.L.W_LINEAR, 0, 0, False), [(None, None)] * 2))
+    gaps.append((pos[0], pos[0] + 50))
+    n = pos[0] + 50
+    bucket = bucket[:n]
+    base = bucket.data_ptr()
+
+    def owners(plan):
+        early, segs = plan
+        got = torch.full((n,), -2)
+        for tag, ranges in [(-1, early)] + list(enumerate(segs)):
+            assert ranges == sorted(ranges)
+            for lo, hi in ranges:
+                assert 0 <= lo < hi <= n and bool((got[lo:hi] == -2).all()), (tag, lo, hi)      # in no list twice
+                got[lo:hi] = tag
+        assert bool((got != -2).all())                                                            # in one list at least
+        return got
+
+    def expected(seg_of_weight):
+        want = torch.full((n,), -1)
+        for t, i in written:
+            lo = (t.data_ptr() - base) // 4
+            want[lo: lo + t.numel()] = seg_of_weight[i]
+        return want
+    saved = dict(A._DEFER["pending"]), list(A._FOLD_PENDING), tante_amd.get_option("TANTE_WGRAD_JOBS_PER_LAUNCH")
+    try:
+        A._DEFER["pending"].clear()
+        A._DEFER["pending"].update({(e.gW.data_ptr(), e.M, e.N, e.K, e.comp, e.lay): e for e in ents})
+        A._FOLD_PENDING[:] = folds
+        tante_amd.set_option("TANTE_WGRAD_JOBS_PER_LAUNCH", 4)
+        groups = A._wgrad_groups(list(A._DEFER["pending"].values()))
+        assert [len(g) for g in groups] == [4, 2] and [e for g in groups for e in g] == ents
+        assert A._pending_groups() == (groups, {0: [0], 1: [1]})
+        for segments, n_seg, seg_of_weight in [(1, 1, [0] * 6), (2, 2, [0, 0, 0, 0, 1, 1]), (3, 2, [0, 0, 0, 0, 1, 1])]:
+            plan = A.flush_plan(bucket, segments)
+            assert len(plan[1]) == n_seg and plan[0] == gaps, (segments, plan[0], gaps)
+            assert torch.equal(owners(plan), expected(seg_of_weight)), segments
+        assert A.flush_plan(bucket, 2)[1][1] == [(pos[0] - 2 * W - 4 * V, pos[0] - W - 2 * V), (pos[0] - W - V, pos[0])]      # fold 1's three, weight 5's two
+        tante_amd.set_option("TANTE_WGRAD_JOBS_PER_LAUNCH", 1)
+        groups = A._wgrad_groups(list(A._DEFER["pending"].values()))
+        assert groups == [[e] for e in ents]
+        assert A._pending_groups()[1] == {1: [0], 4: [1]}
+        plan = A.flush_plan(bucket, 3)
+        assert len(plan[1]) == 3 and plan[0] == gaps
+        assert torch.equal(owners(plan), expected([0, 0, 1, 1, 2, 2]))
+    finally:
+        A._DEFER["pending"].clear()
+        A._DEFER["pending"].update(saved[0])
+        A._FOLD_PENDING[:] = saved[1]
+        tante_amd.set_option("TANTE_WGRAD_JOBS_PER_LAUNCH", saved[2])
+
+
 def _split_allreduce_worker(rank, world, port, q):
     import os
     import torch
