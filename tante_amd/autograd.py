@@ -818,6 +818,16 @@ class BranchOutFn(Function):
         return dpre, dW, db, dout, None, None, None, None
 
 
+def _wgrads_into_slots(uses, M: int):
+    """The weight gradients of these (W, b, dy, a) uses over M bf16 rows, each added into the gradient slots of its W and b: recorded for
+    the shared launches at the end of the backward pass (_defer_wgrad), else launched now."""
+    for W, b, dy, a in uses:
+        gW, gb = _grad_slot(W), _grad_slot(b)
+        N, Kk = W.shape
+        if not _defer_wgrad(gW, gb, dy, a, M, N, Kk, L.BF16):
+            wgrad(_rm_linear(dy), _rm_linear(a), M, N, Kk, (N, Kk), L.BF16, device=a.device, with_bias=True, into=gW, db_into=gb)
+
+
 class BlockTailFn(Function):
     """out = x1 + drop(fc2(gelu(fc1'(LN2(x1))))), x1 = xs + drop(out_proj(o)) -- the tail of a TransformerBlock behind its attention --
     as ONE node.  Forward is always precomputed (tante_block_fused_train produced `out` and every saved tensor); backward is one launch
@@ -840,11 +850,7 @@ class BlockTailFn(Function):
         M, Cc = o.shape
         t = K.block_tail_bwd(dout, hpre, xh2, st2, bwd_stream, Cc, hpre.shape[1], ctx.p, ctx.seed_out, ctx.seed_mlp)
         Wo, bo, w1f, b1f, W2, b2 = ctx.params
-        for W, b, dy, a in ((W2, b2, t["dy2"], act), (w1f, b1f, t["dhpre"], xh2), (Wo, bo, t["dy1"], o)):
-            gW, gb = _grad_slot(W), _grad_slot(b)
-            N, Kk = W.shape
-            if not _defer_wgrad(gW, gb, dy, a, M, N, Kk, L.BF16):
-                wgrad(_rm_linear(dy), _rm_linear(a), M, N, Kk, (N, Kk), L.BF16, device=a.device, with_bias=True, into=gW, db_into=gb)
+        _wgrads_into_slots(((W2, b2, t["dy2"], act), (w1f, b1f, t["dhpre"], xh2), (Wo, bo, t["dy1"], o)), M)
         return t["do"], t["dx1"], None, None, None, None, None, None, None, None, None, None
 
 
@@ -881,11 +887,7 @@ class BlockFn(Function):
             M, Cc = xh1.shape
             t = K.block_bwd_fused(dout, xh1, st1, hpre, xh2, st2, bwd_stream, ctx.fwd_stream, ctx.head_stream, Cc, n_head, hpre.shape[1], seq,
                                   causal, p, seeds)
-            for W, b, dy, a in ((W2, b2, t["dy2"], act), (w1f, b1f, t["dhpre"], xh2), (Wo, bo, t["dy1"], o), (w_in, b_in, t["dqkv"], xh1)):
-                gW, gb = _grad_slot(W), _grad_slot(b)
-                N, Kk = W.shape
-                if not _defer_wgrad(gW, gb, dy, a, M, N, Kk, L.BF16):
-                    wgrad(_rm_linear(dy), _rm_linear(a), M, N, Kk, (N, Kk), L.BF16, device=a.device, with_bias=True, into=gW, db_into=gb)
+            _wgrads_into_slots(((W2, b2, t["dy2"], act), (w1f, b1f, t["dhpre"], xh2), (Wo, bo, t["dy1"], o), (w_in, b_in, t["dqkv"], xh1)), M)
             return (t["dx"],) + (None,) * 18
         tail = NS(saved_tensors=(o, hpre, xh2, st2, act, bwd_stream), params=(Wo, bo, w1f, b1f, W2, b2), p=p, seed_out=seeds[1], seed_mlp=seeds[2])
         r = BlockTailFn.backward(tail, dout)
@@ -893,11 +895,7 @@ class BlockFn(Function):
         dqkv = AttentionFn.backward(NS(saved_tensors=(qkv,), seq=seq, C=x.shape[1], nh=n_head, causal=causal, p=p, seed=seeds[0]), d_o)[0]
         if ctx.head_stream is not None and dqkv.dtype == torch.bfloat16:
             # q | k | v data gradient + LayerNorm1 backward + skip gradient: ONE launch (two GEMM launches and a LayerNorm backward otherwise)
-            M, N = dqkv.shape
-            gW, gb = _grad_slot(w_in), _grad_slot(b_in)
-            if not _defer_wgrad(gW, gb, dqkv, xh1, M, N, xh1.shape[1], L.BF16):
-                wgrad(_rm_linear(dqkv), _rm_linear(xh1), M, N, xh1.shape[1], (N, xh1.shape[1]), L.BF16, device=xh1.device, with_bias=True,
-                      into=gW, db_into=gb)
+            _wgrads_into_slots(((w_in, b_in, dqkv, xh1),), dqkv.shape[0])
             dx = K.block_head_bwd(dqkv, xh1, st1, dx1.contiguous(), ctx.head_stream, x.shape[1])
             return (dx,) + (None,) * 18
         dxh = LinearFn.backward(NS(saved_tensors=(xh1, w_in_s), compute=compute, has_bias=True, has_res=False, params=(w_in, b_in),

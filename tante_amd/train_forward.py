@@ -7,14 +7,18 @@ detach), the tape being torch.autograd's.
 """
 from __future__ import annotations
 
+import ctypes as C
+import math
+from typing import NamedTuple, Optional
+
 import torch
 
 from . import _lib as L
 from . import options as _O
 from . import kernels as K
 from . import stages as S
-from .autograd import (EncTailFn, TailCfg, TailFn, FilmTableFn, ActFn, AttentionFn, BlockFn, BlockTailFn, block_tail_ready, AxisHWFn, AxisMlpFn, BranchOutFn, DeconvFn, DropoutAddFn, FilmPosFn, FilmPosFramesFn, FoldFn, LayerNormFn, LayerNormSkipFn, LinearFn, PatchEmbedFn, RtReduceFn,
-                       TaylorFn)
+from .autograd import (EncTailFn, TailCfg, TailFn, FilmTableFn, ActFn, AttentionFn, BlockFn, BlockTailFn, block_tail_ready, AxisHWFn, AxisMlpFn, BranchOutFn, DeconvFn, DropoutAddFn, FilmPosFn, FilmPosFramesFn, FoldFn, LayerNormFn, LayerNormSkipFn, LinearFn, MaskedAttentionFn,
+                       PatchEmbedFn, RtReduceFn, TaylorFn, _grad_slot, next_seed)
 
 
 _FOLDS = None   # (id(ln), id(W)) -> (W diag(gamma), b + W beta) while a fold_scope is open
@@ -38,23 +42,31 @@ class fold_scope:
         return False
 
 
+def _scoped(key, make):
+    """make() kept under `key` for as long as the open fold scope lives; without a scope nothing is kept: make() per call."""
+    if _FOLDS is None:
+        return make()
+    if _FOLDS.get(key) is None:
+        _FOLDS[key] = make()
+    return _FOLDS[key]
+
+
 def _folded(lin_w, lin_b, ln, pre=None):
     """LayerNorm affine folded into the consumer: (W diag(gamma), b + W beta) -- parameter-sized torch expressions whose
     autograd distributes the gradients back to W, b, gamma, beta.  pre: the pair already computed (prepare_blocks)."""
     if _FOLDS is None or not torch.is_grad_enabled():
         return lin_w * ln.weight[None, :], lin_b + lin_w @ ln.bias
-    key = (id(ln), id(lin_w))
-    hit = _FOLDS.get(key)
-    if hit is None:
+
+    def fold():
         we, be, gw, gb = FoldFn.apply(lin_w, lin_b, ln.weight, ln.bias, pre)
         we._tante_grad, be._tante_grad = gw, gb       # the weight-gradient kernels of every use accumulate here
-        hit = _FOLDS[key] = (we, be)
-    return hit
+        return we, be
+    return _scoped((id(ln), id(lin_w)), fold)
 
 
 FUSED_TRAIN_FORWARD = _O.register("TANTE_TRAIN_FUSED", True, __name__, "FUSED_TRAIN_FORWARD")
 FUSED_TAIL_BACKWARD = _O.register("TANTE_TRAIN_FUSED_BWD", True, __name__, "FUSED_TAIL_BACKWARD")
-BLOCK_RECORDS = _O.register("TANTE_TRAIN_BLOCK_RECORDS", True, __name__, "BLOCK_RECORDS")   # per-scope prepared record of a block (host time)
+BLOCK_RECORDS = _O.register("TANTE_TRAIN_BLOCK_RECORDS", True, __name__, "BLOCK_RECORDS")   # per-scope BlockPlan of a block (host time)
 FUSED_ENC_ACT = _O.register("TANTE_TRAIN_FUSED_ENC_ACT", True, __name__, "FUSED_ENC_ACT")   # encoder GELUs inside the next stage's node
 FUSED_AXIS_HW = _O.register("TANTE_TRAIN_FUSED_AXIS", True, __name__, "FUSED_AXIS_HW")     # H + W propagators' training forward in one launch
 FUSED_HEAD_BACKWARD = _O.register("TANTE_TRAIN_FUSED_HEAD_BWD", True, __name__, "FUSED_HEAD_BACKWARD")   # q|k|v dgrad + LayerNorm1 backward in one launch
@@ -79,19 +91,17 @@ def tail_train_cfg(model, B: int, compute: int, want_z: bool):
         return None
     if tuple(enc.P) != (2, 2, 2) or enc.overlap != 0.0 or list(enc.chans) != [D, 64, 128, 256] or not K.tail_supported(model.C, D, model.H_p, model.W_p):
         return None
-    key = ("tail", id(model))
-    rec = _FOLDS.get(key)
-    if rec is None:
-        from .autograd import _grad_slot
+
+    def pack():
         ep = [q for i in range(3) for q in (getattr(enc, f"enc_conv_{i + 1}").conv.weight, getattr(enc, f"enc_conv_{i + 1}").conv.bias)]
         dps = [[q for i in range(3) for q in (getattr(d, f"dec_conv_{i + 1}").deconv.weight, getattr(d, f"dec_conv_{i + 1}").deconv.bias)]
                for d in decs]
         ok = all(q is not None and q.requires_grad and _grad_slot(q) is not None for q in ep + [q for dp in dps for q in dp])
-        rec = _FOLDS[key] = (ep, dps, K.pack_tail(ep, D, False), [K.pack_tail(dp, D, True) for dp in dps]) if ok else False
+        return (ep, dps, K.pack_tail(ep, D, False), [K.pack_tail(dp, D, True) for dp in dps]) if ok else False
+    rec = _scoped(("tail", id(model)), pack)
     if rec is False:
         return None
     ep, dps, es, dss = rec
-    import math
     coefs = [float(model.frame_interval) ** (k + 1) / math.factorial(k + 1) for k in range(model.taylor_order)]
     return TailCfg(B, model.T, model.H_p, model.W_p, model.C, D, coefs, dps, dss, ep, es, want_z)
 
@@ -102,20 +112,70 @@ BATCH_PREP = _O.register("TANTE_TRAIN_BATCH_PREP", True, __name__, "BATCH_PREP")
 FILM_TABLE_HIP = _O.register("TANTE_TRAIN_FILM_TABLE_HIP", True, __name__, "FILM_TABLE_HIP")   # FiLM tables + their backward as two HIP launches     # folds and backward fragment streams of all blocks in two launches
 
 
+def _fused_forward_ok(blk, Lq: int, compute: int) -> bool:
+    """tante_block_fused_train computes this block over sequences of Lq tokens (that x is fp32 and contiguous is the call's to check)."""
+    return bool(FUSED_TRAIN_FORWARD and compute == L.BF16 and blk.fused and blk.ln1.eps == blk.ln2.eps
+                and K.block_fused_train_supported(blk.embed_dim, blk.n_head, blk.hidden, Lq))
+
+
+def _tail_one_node(*weights) -> bool:
+    """The block behind its attention is ONE node whose backward is ONE launch (tante_block_tail_bwd), which needs a slot per weight."""
+    return bool(FUSED_TAIL_BACKWARD and torch.is_grad_enabled() and block_tail_ready(*weights))
+
+
+def _head_stream_ok(blk, w_in) -> bool:
+    """q | k | v data gradient + LayerNorm1 backward in one launch (tante_block_head_bwd), from a stream of the folded in-projection."""
+    return bool(FUSED_HEAD_BACKWARD and tuple(w_in.shape) == (3 * blk.embed_dim, blk.embed_dim) and blk.hidden == blk.embed_dim)
+
+
+class BlockPlan(NamedTuple):
+    """How block_train runs one block for one (L, causal, compute): decided once per fold scope (= per rollout graph), read by name."""
+    params: tuple                              # the eight parameters BlockFn takes: in-projection and fc1 LayerNorm-folded
+    fwd_stream: Optional[torch.Tensor]         # tante_block_fused_train's weight stream (fused_forward)
+    tail_stream: Optional[torch.Tensor]        # tante_block_tail_bwd's transposed fragments (fused_tail)
+    head_stream: Optional[torch.Tensor]        # tante_block_head_bwd's (one_node, where _head_stream_ok)
+    eps: float
+    fused_forward: bool                        # one launch computes the block and stores what the backward pass reads
+    fused_tail: bool                           # the tail behind the attention is one node
+    one_node: bool                             # ... and so is the whole block (BlockFn): the folded in-projection has its slots too
+    one_launch_bwd: bool                       # BlockFn's backward is tante_block_bwd_fused, which recomputes q | k | v
+    need_x1: bool                              # not fused_tail: only the per-operator tail reads the fp32 residual after the attention half
+    need_qkv: bool                             # not one_launch_bwd: only the three-launch backward reads the packed projection
+
+
+def _plan_block(blk, Lq: int, causal: bool, compute: int, x_ok: bool) -> BlockPlan:
+    """The plan of `blk`, its weights folded and its streams packed (both through the fold scope: once per rollout graph, or per call
+    without one).  x_ok: the call's x is fp32 and contiguous, and unmasked -- what the fused forward takes."""
+    a, m, E = blk.attn, blk.mlp, blk.embed_dim
+    w_in, b_in = _folded(a.in_proj_weight, a.in_proj_bias, blk.ln1)
+    w1, b1 = _folded(m[0].weight, m[0].bias, blk.ln2)
+    params = (w_in, b_in, a.out_proj.weight, a.out_proj.bias, w1, b1, m[2].weight, m[2].bias)
+    fused = x_ok and _fused_forward_ok(blk, Lq, compute)
+    tail = fused and _tail_one_node(*params[2:])
+    node = tail and block_tail_ready(w_in, b_in)
+    head = node and _head_stream_ok(blk, w_in)
+    # the whole backward in one launch: needs both transposed-fragment streams and every gradient slot
+    one = bool(head and FUSED_BLOCK_BACKWARD and _FOLDS is not None and K.block_bwd_fused_supported(E, blk.n_head, blk.hidden, Lq, causal))
+    wd = w_in.detach()
+    return BlockPlan(params,
+                     _scoped(("fs_stream", id(blk)), lambda: K.pack_block_train(params, E, blk.hidden)) if fused else None,
+                     _scoped(("bt_stream", id(blk)), lambda: K.pack_block_tail_bwd(m[2].weight, w1, a.out_proj.weight, E, blk.hidden)) if tail else None,
+                     _scoped(("bh_stream", id(blk)), lambda: K.pack_block_tail_bwd(wd[0:E], wd[E:2 * E], wd[2 * E:3 * E], E, blk.hidden)) if head else None,
+                     blk.ln1.eps, fused, tail, node, one, not tail, not one)
+
+
 def prepare_blocks(model, compute: int):
     """Once per fold scope (= per rollout graph), before the first block runs: the LayerNorm folds of EVERY block in one launch
     (tante_fold_fwd_multi), their two backward fragment streams in another (tante_pack_block_tail_bwd_multi) and the forward kernel's weight
-    streams in a third (tante_pack_block_train_multi), left in the scope under the keys block_train looks up -- per block these were five
-    launches of ~4.7 us of latency each, 45 per train step.  Blocks that will not
-    take the fused one-node path are left to block_train."""
+    streams in a third (tante_pack_block_train_multi), left in the scope under the keys _folded and _plan_block look up -- per block these
+    were five launches of ~4.7 us of latency each, 45 per train step.  Blocks that will not take the fused one-node path are left to
+    block_train."""
     if _FOLDS is None or not BATCH_PREP or not torch.is_grad_enabled():
         return
     key = ("prepared", id(model))
     if key in _FOLDS:
         return
     _FOLDS[key] = True
-    if not (FUSED_TRAIN_FORWARD and FUSED_TAIL_BACKWARD and compute == L.BF16):
-        return
     todo = []
     for bb in getattr(model, "blocks", ()):
         if not hasattr(bb, "attn_axes"):
@@ -127,20 +187,17 @@ def prepare_blocks(model, compute: int):
             a, m = blk.attn, blk.mlp
             if (id(blk.ln1), id(a.in_proj_weight)) in _FOLDS or (id(blk.ln2), id(m[0].weight)) in _FOLDS:
                 continue
-            if not (blk.fused and blk.ln1.eps == blk.ln2.eps and blk.hidden == blk.embed_dim and a.in_proj_bias is not None
-                    and K.block_fused_train_supported(blk.embed_dim, blk.n_head, blk.hidden, K.make_seq(axis, 1, bb.T, bb.H, bb.W).L)
-                    and block_tail_ready(a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias, m[0].weight, m[0].bias,
-                                         m[2].weight, m[2].bias, blk.ln1.weight, blk.ln1.bias, blk.ln2.weight, blk.ln2.bias)):
-                continue
-            todo.append(blk)
+            # (the folds do not exist yet: their accumulators will, so the slots of what they are folded from stand in for them)
+            if (a.in_proj_bias is not None and _fused_forward_ok(blk, K.make_seq(axis, 1, bb.T, bb.H, bb.W).L, compute)
+                    and _tail_one_node(a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias, m[0].weight, m[0].bias,
+                                       m[2].weight, m[2].bias, blk.ln1.weight, blk.ln1.bias, blk.ln2.weight, blk.ln2.bias)):
+                todo.append(blk)
     if len(todo) < 2:
         return
-    import ctypes as C
     dev = todo[0].attn.in_proj_weight.device
-    pairs = []
-    for blk in todo:
-        pairs.append((blk.attn.in_proj_weight, blk.attn.in_proj_bias, blk.ln1))
-        pairs.append((blk.mlp[0].weight, blk.mlp[0].bias, blk.ln2))
+    E, hidden = todo[0].embed_dim, todo[0].hidden
+    new_stream = lambda nbytes: torch.empty(nbytes, dtype=torch.uint8, device=dev)      # noqa: E731
+    pairs = [q for blk in todo for q in ((blk.attn.in_proj_weight, blk.attn.in_proj_bias, blk.ln1), (blk.mlp[0].weight, blk.mlp[0].bias, blk.ln2))]
     arr = (L.FoldFwd * len(pairs))()
     outs = []
     for f, (W, b, ln) in zip(arr, pairs):
@@ -150,32 +207,50 @@ def prepare_blocks(model, compute: int):
         outs.append((we, be))
     L.check(L.lib().tante_fold_fwd_multi(C.byref(arr), len(pairs), K._stream()), "tante_fold_fwd_multi")
     folded = [_folded(W, b, ln, pre=o) for (W, b, ln), o in zip(pairs, outs)]
-    nbytes = L.lib().tante_block_tail_bwd_stream_bytes(todo[0].embed_dim, todo[0].hidden)
-    mats = (L.Mat3 * (2 * len(todo)))()
+    nbytes = L.lib().tante_block_tail_bwd_stream_bytes(E, hidden)
+    jobs = []      # (a, b, c, dst) of tante_pack_block_tail_bwd_multi: the tail's stream of every block, and the head's where it gets one
     for i, blk in enumerate(todo):
-        E = blk.embed_dim
         w_in, w1 = folded[2 * i][0].detach(), folded[2 * i + 1][0].detach()
-        bst = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        hst = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        t, h = mats[2 * i], mats[2 * i + 1]
-        t.a, t.b, t.c, t.dst = blk.mlp[2].weight.data_ptr(), w1.data_ptr(), blk.attn.out_proj.weight.data_ptr(), bst.data_ptr()
-        h.a, h.b, h.c, h.dst = w_in[0:E].data_ptr(), w_in[E:2 * E].data_ptr(), w_in[2 * E:3 * E].data_ptr(), hst.data_ptr()
-        _FOLDS[("bt_stream", id(blk))] = bst
-        _FOLDS[("bh_stream", id(blk))] = hst
-    L.check(L.lib().tante_pack_block_tail_bwd_multi(C.byref(mats), 2 * len(todo), todo[0].embed_dim, todo[0].hidden, K._stream()),
-            "tante_pack_block_tail_bwd_multi")
-    # ... and the forward kernel's weight streams in a third
-    sbytes = L.lib().tante_block_stream_bytes(todo[0].embed_dim, todo[0].hidden)
+        bst = _FOLDS[("bt_stream", id(blk))] = new_stream(nbytes)
+        jobs.append((blk.mlp[2].weight, w1, blk.attn.out_proj.weight, bst))
+        if _head_stream_ok(blk, w_in):
+            hst = _FOLDS[("bh_stream", id(blk))] = new_stream(nbytes)
+            jobs.append((w_in[0:E], w_in[E:2 * E], w_in[2 * E:3 * E], hst))
+    mats = (L.Mat3 * len(jobs))()
+    for mat, job in zip(mats, jobs):
+        mat.a, mat.b, mat.c, mat.dst = (t.data_ptr() for t in job)
+    L.check(L.lib().tante_pack_block_tail_bwd_multi(C.byref(mats), len(jobs), E, hidden, K._stream()), "tante_pack_block_tail_bwd_multi")
+    sbytes = L.lib().tante_block_stream_bytes(E, hidden)
     bw = (L.BlockWeights * len(todo))()
     for i, blk in enumerate(todo):
         (w_in, b_in), (w1, b1) = folded[2 * i], folded[2 * i + 1]
-        st = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+        st = _FOLDS[("fs_stream", id(blk))] = new_stream(sbytes)
         e = bw[i]
         e.in_w, e.in_b, e.out_w, e.out_b = w_in.data_ptr(), b_in.data_ptr(), blk.attn.out_proj.weight.data_ptr(), blk.attn.out_proj.bias.data_ptr()
         e.fc1_w, e.fc1_b, e.fc2_w, e.fc2_b = w1.data_ptr(), b1.data_ptr(), blk.mlp[2].weight.data_ptr(), blk.mlp[2].bias.data_ptr()
         e.block_stream = st.data_ptr()
-        _FOLDS[("fs_stream", id(blk))] = st
-    L.check(L.lib().tante_pack_block_train_multi(C.byref(bw), len(todo), todo[0].embed_dim, todo[0].hidden, K._stream()), "tante_pack_block_train_multi")
+    L.check(L.lib().tante_pack_block_train_multi(C.byref(bw), len(todo), E, hidden, K._stream()), "tante_pack_block_train_multi")
+
+
+def _block_chain(blk, plan: BlockPlan, x, seq, causal: bool, p: float, compute: int, t=None, seeds=(0, 0, 0), masks=None):
+    """The block operator by operator: LayerNormSkip -> Linear -> Attention -> BranchOut -> LayerNormSkip -> Linear -> BranchOut.
+    t: what the fused forward saved -- the nodes then launch nothing in forward and only record what their backward reads, with the
+    dropout `seeds` the forward drew (without t every node draws its own).  masks: the masked attention node (no dropout there)."""
+    adt = K.act_torch_dtype(compute)
+    w_in, b_in, Wo, bo, w1, b1, W2, b2 = plan.params
+    f = t is not None
+    xh, xs = LayerNormSkipFn.apply(x, blk.ln1.eps, adt, (t["xh1"], t["st1"]) if f else None)      # xs: x as the skip operand, whose gradient LN's backward adds
+    qkv = LinearFn.apply(xh, w_in, b_in, None, compute, adt, t["qkv"] if f else None)
+    if masks is not None:
+        o = MaskedAttentionFn.apply(qkv, blk.embed_dim, blk.n_head, seq.nseq, seq.L, causal, masks[0], masks[1])
+    else:
+        o = AttentionFn.apply(qkv, seq, blk.embed_dim, blk.n_head, causal, p, (t["o"], seeds[0]) if f else None)
+    if f and plan.fused_tail:      # the rest as ONE autograd node whose backward is ONE launch (tante_block_tail_bwd)
+        return BlockTailFn.apply(o, xs, Wo, bo, w1, b1, W2, b2, t, plan.tail_stream, p, seeds)
+    x1 = BranchOutFn.apply(o, Wo, bo, xs, L.ACT_NONE, p, compute, (t["x1"], None, seeds[1]) if f else None)      # x + drop(out_proj(o))
+    xh2, x1s = LayerNormSkipFn.apply(x1, blk.ln2.eps, adt, (t["xh2"], t["st2"]) if f else None)
+    hpre = LinearFn.apply(xh2, w1, b1, None, compute, adt, t["hpre"] if f else None)
+    return BranchOutFn.apply(hpre, W2, b2, x1s, L.ACT_GELU_TANH, p, compute, (t["out"], t["act"], seeds[2]) if f else None)   # x1 + drop(fc2(gelu(hpre)))
 
 
 def block_train(blk, x: torch.Tensor, seq, causal: bool, compute: int, masks=None) -> torch.Tensor:
@@ -183,102 +258,31 @@ def block_train(blk, x: torch.Tensor, seq, causal: bool, compute: int, masks=Non
     the per-operator chain with the masked attention node."""
     BLOCK_CALLS[0] += 1
     p = blk.p_drop if blk.training else 0.0     # nn.Dropout / MHA dropout are active in train() mode only
-    if masks is not None:
-        if p > 0.0:
-            raise NotImplementedError("attn_mask / key_padding_mask under autograd with dropout > 0 in train() mode: the masked attention "
-                                      "kernels have no attention-probability dropout (the TANTE path passes `causal` only)")
-        from .autograd import MaskedAttentionFn
-        adt = K.act_torch_dtype(compute)
-        a, m = blk.attn, blk.mlp
-        w_in, b_in = _folded(a.in_proj_weight, a.in_proj_bias, blk.ln1)
-        xh, x = LayerNormSkipFn.apply(x, blk.ln1.eps, adt)
-        qkv = LinearFn.apply(xh, w_in, b_in, None, compute, adt)
-        o = MaskedAttentionFn.apply(qkv, blk.embed_dim, blk.n_head, seq.nseq, seq.L, causal, masks[0], masks[1])
-        x = BranchOutFn.apply(o, a.out_proj.weight, a.out_proj.bias, x, L.ACT_NONE, 0.0, compute)
-        w1, b1 = _folded(m[0].weight, m[0].bias, blk.ln2)
-        xh2, x = LayerNormSkipFn.apply(x, blk.ln2.eps, adt)
-        hpre = LinearFn.apply(xh2, w1, b1, None, compute, adt)
-        return BranchOutFn.apply(hpre, m[2].weight, m[2].bias, x, L.ACT_GELU_TANH, 0.0, compute)
-    # Every later call of this block inside one rollout graph (the BPTT steps) takes the record its first call left in the fold scope:
-    # folded weights, the three fragment streams, the decision for the one-node path: the module attribute chains, fold / stream look-ups
-    # and accumulator checks below are ~60 us of host time per block call (the step is GPU-bound on the bench box, with ~2 ms of margin).
-    rec = _FOLDS.get(("blk_rec", id(blk), seq.L, compute)) if (_FOLDS is not None and BLOCK_RECORDS and torch.is_grad_enabled()) else None
-    if rec is not None and x.dtype == torch.float32 and x.is_contiguous():
-        from .autograd import next_seed
-        seeds = (next_seed(), next_seed(), next_seed()) if p > 0.0 else (0, 0, 0)
-        t = K.block_fused_train(x.detach(), rec[8], blk.embed_dim, blk.n_head, blk.hidden, seq, causal, rec[11], p, seeds, need_x1=False,
-                                need_qkv=not rec[12])
-        BLOCK_CALLS[1] += 1
-        return BlockFn.apply(x, *rec[:8], t, rec[9], seq, blk.n_head, causal, p, seeds, compute, rec[10], rec[8] if rec[12] else None)
-    adt = K.act_torch_dtype(compute)
-    a, m = blk.attn, blk.mlp
-    w_in, b_in = _folded(a.in_proj_weight, a.in_proj_bias, blk.ln1)
-    if (FUSED_TRAIN_FORWARD and compute == L.BF16 and blk.fused and blk.ln1.eps == blk.ln2.eps and x.dtype == torch.float32 and x.is_contiguous()
-            and K.block_fused_train_supported(blk.embed_dim, blk.n_head, blk.hidden, seq.L)):
-        # ONE launch computes the block and stores what the backward pass reads; the autograd nodes below launch nothing in forward
-        from .autograd import next_seed
-        seeds = (next_seed(), next_seed(), next_seed()) if p > 0.0 else (0, 0, 0)
-        w1, b1 = _folded(m[0].weight, m[0].bias, blk.ln2)
-        # the kernel's weight stream is packed from the folded tensors, once per fold scope (= once per rollout graph: BPTT calls share it)
-        key = ("fs_stream", id(blk))
-        stream = _FOLDS.get(key) if _FOLDS is not None else None
-        if stream is None:
-            stream = K.pack_block_train((w_in, b_in, a.out_proj.weight, a.out_proj.bias, w1, b1, m[2].weight, m[2].bias), blk.embed_dim, blk.hidden)
-            if _FOLDS is not None:
-                _FOLDS[key] = stream
-        fused_tail = (FUSED_TAIL_BACKWARD and torch.is_grad_enabled()
-                      and block_tail_ready(a.out_proj.weight, a.out_proj.bias, w1, b1, m[2].weight, m[2].bias))
-        # the whole backward in one launch: needs both transposed-fragment streams and every gradient slot (decided here: the forward then
-        # skips the packed projection, which only the three-launch attention backward reads)
-        fused_bwd = (fused_tail and FUSED_BLOCK_BACKWARD and FUSED_HEAD_BACKWARD and _FOLDS is not None and block_tail_ready(w_in, b_in)
-                     and w_in.shape == (3 * blk.embed_dim, blk.embed_dim)
-                     and K.block_bwd_fused_supported(blk.embed_dim, blk.n_head, blk.hidden, seq.L, causal))
-        t = K.block_fused_train(x.detach(), stream, blk.embed_dim, blk.n_head, blk.hidden, seq, causal, blk.ln1.eps, p, seeds,
-                                need_x1=not fused_tail, need_qkv=not fused_bwd)
-        if fused_tail:
-            # the block behind its attention as ONE autograd node whose backward is ONE launch (tante_block_tail_bwd)
-            key = ("bt_stream", id(blk))
-            bstream = _FOLDS.get(key) if _FOLDS is not None else None
-            if bstream is None:
-                bstream = K.pack_block_tail_bwd(m[2].weight, w1, a.out_proj.weight, blk.embed_dim, blk.hidden)
-                if _FOLDS is not None:
-                    _FOLDS[key] = bstream
-            if block_tail_ready(w_in, b_in):
-                hstream = None
-                if FUSED_HEAD_BACKWARD and w_in.shape == (3 * blk.embed_dim, blk.embed_dim) and blk.hidden == blk.embed_dim:
-                    key = ("bh_stream", id(blk))
-                    hstream = _FOLDS.get(key) if _FOLDS is not None else None
-                    if hstream is None:      # the three 256-row blocks of the folded in-projection weight, transposed into fragments
-                        E = blk.embed_dim
-                        wd = w_in.detach()
-                        hstream = K.pack_block_tail_bwd(wd[0:E], wd[E:2 * E], wd[2 * E:3 * E], E, blk.hidden)
-                        if _FOLDS is not None:
-                            _FOLDS[key] = hstream
-                if _FOLDS is not None:
-                    _FOLDS[("blk_rec", id(blk), seq.L, compute)] = (w_in, b_in, a.out_proj.weight, a.out_proj.bias, w1, b1, m[2].weight, m[2].bias,
-                                                                    stream, bstream, hstream, blk.ln1.eps, fused_bwd and hstream is not None)
-                BLOCK_CALLS[1] += 1
-                return BlockFn.apply(x, w_in, b_in, a.out_proj.weight, a.out_proj.bias, w1, b1, m[2].weight, m[2].bias, t, bstream, seq,
-                                     blk.n_head, causal, p, seeds, compute, hstream, stream if (fused_bwd and hstream is not None) else None)
-            xh, xs = LayerNormSkipFn.apply(x, blk.ln1.eps, adt, (t["xh1"], t["st1"]))
-            qkv = LinearFn.apply(xh, w_in, b_in, None, compute, adt, t["qkv"])
-            o = AttentionFn.apply(qkv, seq, blk.embed_dim, blk.n_head, causal, p, (t["o"], seeds[0]))
-            return BlockTailFn.apply(o, xs, a.out_proj.weight, a.out_proj.bias, w1, b1, m[2].weight, m[2].bias, t, bstream, p, seeds)
-        xh, xs = LayerNormSkipFn.apply(x, blk.ln1.eps, adt, (t["xh1"], t["st1"]))
-        qkv = LinearFn.apply(xh, w_in, b_in, None, compute, adt, t["qkv"])
-        o = AttentionFn.apply(qkv, seq, blk.embed_dim, blk.n_head, causal, p, (t["o"], seeds[0]))
-        x1 = BranchOutFn.apply(o, a.out_proj.weight, a.out_proj.bias, xs, L.ACT_NONE, p, compute, (t["x1"], None, seeds[1]))
-        xh2, x1s = LayerNormSkipFn.apply(x1, blk.ln2.eps, adt, (t["xh2"], t["st2"]))
-        hpre = LinearFn.apply(xh2, w1, b1, None, compute, adt, t["hpre"])
-        return BranchOutFn.apply(hpre, m[2].weight, m[2].bias, x1s, L.ACT_GELU_TANH, p, compute, (t["out"], t["act"], seeds[2]))
-    xh, x = LayerNormSkipFn.apply(x, blk.ln1.eps, adt)      # x: the same tokens, as the skip operand whose gradient LN's backward adds
-    qkv = LinearFn.apply(xh, w_in, b_in, None, compute, adt)
-    o = AttentionFn.apply(qkv, seq, blk.embed_dim, blk.n_head, causal, p)
-    x = BranchOutFn.apply(o, a.out_proj.weight, a.out_proj.bias, x, L.ACT_NONE, p, compute)       # x + drop(out_proj(o))
-    w1, b1 = _folded(m[0].weight, m[0].bias, blk.ln2)
-    xh2, x = LayerNormSkipFn.apply(x, blk.ln2.eps, adt)
-    hpre = LinearFn.apply(xh2, w1, b1, None, compute, adt)
-    return BranchOutFn.apply(hpre, m[2].weight, m[2].bias, x, L.ACT_GELU_TANH, p, compute)           # x + drop(fc2(gelu(hpre)))
+    if masks is not None and p > 0.0:
+        raise NotImplementedError("attn_mask / key_padding_mask under autograd with dropout > 0 in train() mode: the masked attention "
+                                  "kernels have no attention-probability dropout (the TANTE path passes `causal` only)")
+    x_ok = masks is None and x.dtype == torch.float32 and x.is_contiguous()
+    # Every later call of this block inside one rollout graph (the BPTT steps) takes the plan its first call left in the fold scope: the
+    # module attribute chains, fold / stream look-ups and accumulator checks of _plan_block are ~60 us of host time per block call (the
+    # step is GPU-bound on the bench box, with ~2 ms of margin).
+    # `causal` is in the key because the one-launch backward depends on it; every caller fixes it per block, so no path changes.
+    key = ("blk_rec", id(blk), seq.L, causal, compute)
+    plan = _FOLDS.get(key) if (_FOLDS is not None and BLOCK_RECORDS and torch.is_grad_enabled()) else None
+    if plan is None:
+        plan = _plan_block(blk, seq.L, causal, compute, x_ok)
+        if _FOLDS is not None and plan.one_node:
+            _FOLDS[key] = plan
+    if not (plan.fused_forward and x_ok):
+        return _block_chain(blk, plan, x, seq, causal, p, compute, masks=masks)
+    # ONE launch computes the block and stores what the backward pass reads; the autograd nodes behind it launch nothing in forward
+    seeds = (next_seed(), next_seed(), next_seed()) if p > 0.0 else (0, 0, 0)
+    t = K.block_fused_train(x.detach(), plan.fwd_stream, blk.embed_dim, blk.n_head, blk.hidden, seq, causal, plan.eps, p, seeds,
+                            need_x1=plan.need_x1, need_qkv=plan.need_qkv)
+    if not plan.one_node:
+        return _block_chain(blk, plan, x, seq, causal, p, compute, t, seeds)
+    BLOCK_CALLS[1] += 1
+    return BlockFn.apply(x, *plan.params, t, plan.tail_stream, seq, blk.n_head, causal, p, seeds, compute, plan.head_stream,
+                         plan.fwd_stream if plan.one_launch_bwd else None)
 
 
 def backbone_train(bb, x: torch.Tensor, B: int, compute: int) -> torch.Tensor:
@@ -431,9 +435,7 @@ def tante_train_forward(model, inp: torch.Tensor, compute: int, out_T=1, z_win=N
     # film(x, t) = x * (1 + scale(t)) + shift(t) with t = the window's fixed time stamps: the two tables are the same for every call of a
     # rollout graph, so they are built once per fold scope (like the folded LayerNorm weights) -- four tiny torch Linear layers, their
     # activations and their backward were ~150 launches of ~4.5 us per train step when rebuilt in each of the four BPTT calls
-    key = ("film_tables", id(model))
-    tabs = _FOLDS.get(key) if _FOLDS is not None else None
-    if tabs is None:
+    def film_tables():
         te = model.t_encode
         sc, sh = te.condition_to_scale, te.condition_to_shift
         if FILM_TABLE_HIP and T <= 8 and C_ % 16 == 0:
@@ -442,17 +444,12 @@ def tante_train_forward(model, inp: torch.Tensor, compute: int, out_T=1, z_win=N
             fa, fb, acc = FilmTableFn.apply(tsec, model.t_emb.view(T, C_), sc[0].weight, sc[0].bias, sc[2].weight, sc[2].bias,
                                             sh[0].weight, sh[0].bias, sh[2].weight, sh[2].bias)
             fa._tante_grad, fb._tante_grad = acc[0], acc[1]
-        else:
-            t = model.t_seq.to(inp.device, torch.float32)[:, None]
-            fa = (1.0 + sc(t)).contiguous()                     # (T, C)
-            fb = (sh(t) + model.t_emb.view(T, C_)).contiguous()
-        tabs = (fa, fb)
-        if _FOLDS is not None:
-            _FOLDS[key] = tabs
-    fa, fb = tabs
+            return fa, fb
+        t = model.t_seq.to(inp.device, torch.float32)[:, None]
+        return (1.0 + sc(t)).contiguous(), (sh(t) + model.t_emb.view(T, C_)).contiguous()      # (T, C) each
+    fa, fb = _scoped(("film_tables", id(model)), film_tables)
     s_view = model.s_emb.view(HW, C_)
     if FILM_TABLE_HIP:      # s_emb's gradient slot, for the kernel to add into (the rollout's calls share the parameter)
-        from .autograd import _grad_slot
         gs = _grad_slot(model.s_emb)
         if gs is not None:
             s_view._tante_grad = gs.view(HW, C_)

@@ -417,6 +417,152 @@ def test_fused_training_forward_equals_unfused(dev, letter, B, T, H, W, p, monke
         assert max_rel(a_, b_) < 4e-2, (k, max_rel(a_, b_))
 
 
+# ---------------------------------------------------------------------------------------------------
+# which launches a block_train call makes, setting by setting (train_forward.BlockPlan), and prepare_blocks' batched ones
+# ---------------------------------------------------------------------------------------------------
+PATH_ENTRIES = ("tante_block_fused_train", "tante_block_bwd_fused", "tante_block_tail_bwd", "tante_block_head_bwd", "tante_attention_bwd",
+                "tante_layernorm_fwd", "tante_layernorm_bwd", "tante_layernorm_affine", "tante_layernorm_affine_bwd",
+                "tante_pack_block_train", "tante_pack_block_tail_bwd")
+# per block call, forward + backward: (block_fused_train, block_bwd_fused, block_tail_bwd, block_head_bwd, attention_bwd, LayerNorm forwards,
+# LayerNorm backwards); then what a first call packs: (pack_block_train, pack_block_tail_bwd)
+PATH_COUNTS = {"one launch": ((1, 1, 0, 0, 0, 0, 0), (1, 2)), "three launches": ((1, 0, 1, 1, 1, 0, 0), (1, 2)),
+               "tail + operators": ((1, 0, 1, 0, 1, 0, 1), (1, 1)), "forward only": ((1, 0, 0, 0, 1, 0, 2), (1, 0)),
+               "operators": ((0, 0, 0, 0, 1, 2, 2), (0, 0))}
+PATH_PATTERNS = [("T", 2, 4, 2, 2, True), ("T", 1, 5, 2, 2, False), ("H", 1, 1, 24, 2, False), ("W", 1, 1, 1, 48, True)]   # ..., one-launch backward
+
+
+def _path_of(fused, scope, one_launch):
+    if not fused:
+        return "operators"
+    if not scope or fused is True:         # without a scope the folded weights have no accumulators: no one-node tail
+        return "forward only"
+    return {"block": "one launch" if one_launch else "three launches", "tail": "three launches", "tail_nohead": "tail + operators"}[fused]
+
+
+def _block_train_paths(dev, letter, B, T, H, W, one_launch, p, monkeypatch, affine):
+    """One fused-shape block under the five switch settings of test_fused_training_forward_equals_unfused, twice in one fold scope (the
+    two calls share one backward pass, as a rollout's calls do: a fold scope holds one graph), same seeds for both calls: the library
+    entries each call reaches are the path's (literals, read off block_train and the nodes' backward), the second call packs nothing, and
+    its y and x.grad are the first call's bit for bit.  The same kernels on the same inputs give the same bits: BLOCK_RECORDS off against
+    on, and -- for the two settings whose path does not depend on the scope -- no scope against one; parameter gradients of such pairs
+    at this file's bar for same-kernel pairs (1e-3; in_proj 2e-2: the shared weight-gradient kernels add in arrival order).
+    affine: LayerNorm weights and biases away from (1, 0).  Then the runs with and without a scope do NOT see the same inputs: inside a
+    scope the fold is FoldFn's kernel (tante_fold_fwd), without one it is two torch expressions (W * gamma, b + W @ beta) that sum the
+    bias's 256 terms in another order, so the folded bias differs in its last bits and a bf16 rounding of q | k | v or fc1 flips here
+    and there (measured: y equal or ~1e-4 apart, dx up to 3.8e-4 of its largest entry, before and after the BlockPlan refactor alike).
+    That pair is held to this file's bar for bf16 pairs of different arithmetic, 2e-2; with the affine at (1, 0) both folds are exact
+    (W, b), the inputs are the same, and the pair is held bit for bit."""
+    import contextlib
+    import tante_amd
+    from tante_amd import autograd as A, train_forward as TF, kernels as Kk, _lib as L
+    from test_hip_train_nodes import Spy
+    torch.manual_seed(7)
+    blk = tante_amd.TransformerBlock(256, 8, mlp_ratio=1.0, dropout=p).to(dev).train()
+    with torch.no_grad():
+        for ln in (blk.ln1, blk.ln2) if affine else ():
+            ln.weight.add_(0.2 * torch.randn_like(ln.weight))
+            ln.bias.add_(0.2 * torch.randn_like(ln.bias))
+        blk.attn.in_proj_bias.add_(0.2 * torch.randn_like(blk.attn.in_proj_bias))
+        blk.attn.out_proj.bias.add_(0.2 * torch.randn_like(blk.attn.out_proj.bias))
+    causal = letter == "T"
+    seq = Kk.make_seq(letter, B, T, H, W)
+    assert Kk.block_bwd_fused_supported(256, 8, 256, seq.L, causal) == one_launch
+    n = B * T * H * W
+    x0 = (torch.randn(n, 256, generator=torch.Generator().manual_seed(n)) * 1.3 + 0.2).to(dev)
+    w = torch.randn(n, 256, generator=torch.Generator().manual_seed(n + 1)).to(dev)
+    opt = tante_amd.FlatAdamW(blk.parameters(), lr=1e-3)
+    spy = Spy(monkeypatch, entries=PATH_ENTRIES)
+
+    def counts():
+        c = spy.n
+        return (c["tante_block_fused_train"], c["tante_block_bwd_fused"], c["tante_block_tail_bwd"], c["tante_block_head_bwd"],
+                c["tante_attention_bwd"], c["tante_layernorm_fwd"] + c["tante_layernorm_affine"],
+                c["tante_layernorm_bwd"] + c["tante_layernorm_affine_bwd"], c["tante_pack_block_train"], c["tante_pack_block_tail_bwd"])
+
+    def run(fused, scope, records):
+        monkeypatch.setattr(TF, "BLOCK_RECORDS", records)
+        want, packs = PATH_COUNTS[_path_of(fused, scope, one_launch)]
+        opt.zero_grad()
+        xs, ys, calls0 = [], [], list(TF.BLOCK_CALLS)
+        with (TF.fold_scope() if scope else contextlib.nullcontext()):
+            for call in range(2):
+                A._SEED[0] = 1000
+                c0 = counts()
+                x = x0.clone().requires_grad_(True)
+                y = TF.block_train(blk, x, seq, causal, L.BF16)
+                got = tuple(a - b for a, b in zip(counts(), c0))
+                fwd_want = (want[0], 0, 0, 0, 0, want[5], 0) + (packs if (call == 0 or not scope) else (0, 0))
+                assert got == fwd_want, (fused, scope, records, call, got, fwd_want)
+                xs.append(x)
+                ys.append(y)
+            c0 = counts()
+            A.run_backward(((ys[0] + ys[1]) * w).sum())
+            got = tuple(a - b for a, b in zip(counts(), c0))
+            bwd_want = (0,) + tuple(2 * k for k in want[1:5]) + (0, 2 * want[6], 0, 0)
+            assert got == bwd_want, (fused, scope, records, got, bwd_want)
+        one_node = 2 if _path_of(fused, scope, one_launch) in ("one launch", "three launches", "tail + operators") else 0      # BlockFn applied
+        assert [TF.BLOCK_CALLS[0] - calls0[0], TF.BLOCK_CALLS[1] - calls0[1]] == [2, one_node], (fused, scope, records)
+        assert torch.equal(ys[0], ys[1]) and torch.equal(xs[0].grad, xs[1].grad), (fused, scope, records)
+        return ys[0].detach().clone(), xs[0].grad.clone(), {k: v.grad.detach().clone() for k, v in blk.named_parameters()}
+
+    def same(a, b, what):
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), what
+        for k in a[2]:
+            e = max_rel(a[2][k].cpu(), b[2][k].cpu())
+            assert e < 1e-3 or "in_proj" in k and e < 2e-2, (what, k, e)
+    for fused in ("block", "tail", "tail_nohead", True, False):
+        monkeypatch.setattr(TF, "FUSED_TRAIN_FORWARD", bool(fused))
+        monkeypatch.setattr(TF, "FUSED_TAIL_BACKWARD", fused in ("block", "tail", "tail_nohead"))
+        monkeypatch.setattr(TF, "FUSED_HEAD_BACKWARD", fused in ("block", "tail"))
+        monkeypatch.setattr(TF, "FUSED_BLOCK_BACKWARD", fused == "block")
+        on = run(fused, True, True)
+        same(on, run(fused, True, False), (fused, "BLOCK_RECORDS off"))
+        bare = run(fused, False, True)
+        if fused in (True, False):
+            ey, ex = max_rel(on[0].cpu(), bare[0].cpu()), max_rel(on[1].cpu(), bare[1].cpu())
+            eg = {k: max_rel(on[2][k].cpu(), bare[2][k].cpu()) for k in on[2]}
+            print(f"{letter} L={seq.L} p={p} fused={fused} affine={affine}: scope vs none, y {ey:.3e}, dx {ex:.3e}, worst parameter gradient "
+                  f"{max(eg, key=eg.get)} {max(eg.values()):.3e}")
+            if affine:
+                assert ey < 2e-2 and ex < 2e-2, (fused, "no fold scope", ey, ex)
+            else:
+                same(on, bare, (fused, "no fold scope"))
+
+
+@pytest.mark.parametrize("affine", [True, False], ids=["affine", "unit_affine"])
+@pytest.mark.parametrize("p", [0.0, 0.25])
+@pytest.mark.parametrize("letter,B,T,H,W,one_launch", PATH_PATTERNS)
+def test_block_train_paths_by_launch_count(dev, letter, B, T, H, W, one_launch, p, affine, monkeypatch):
+    _block_train_paths(dev, letter, B, T, H, W, one_launch, p, monkeypatch, affine)
+
+
+def test_prepare_blocks_batches_the_folds_and_packs(dev, monkeypatch):
+    """A model with two eligible blocks (T and H, C = 256, 8 heads): one training forward inside a fold scope folds and packs for both in
+    three launches (tante_fold_fwd_multi, tante_pack_block_tail_bwd_multi, tante_pack_block_train_multi) and no single-block pack; with
+    BATCH_PREP off block_train packs them itself, three streams per block, and the output is the same bit for bit."""
+    import tante_amd
+    from tante_amd import train_forward as TF, _lib as L
+    from test_hip_train_nodes import Spy
+    md = tante_amd.TanteMetadata(n_fields=2, spatial_resolution=(16, 16))
+    torch.manual_seed(5)
+    m = tante_amd.TANTE(in_T=4, dset_metadata=md, taylor_order=1, attn_axes="TH", n_head=8, embed_dim=256, patch_scale=8,
+                        dropout=0.0).to(dev).train().set_compute("bf16")
+    opt = tante_amd.FlatAdamW(m.parameters(), lr=1e-3)
+    opt.zero_grad()
+    inp = torch.randn(1, 4, 2, 16, 16, generator=torch.Generator().manual_seed(6)).to(dev)
+    entries = ("tante_fold_fwd_multi", "tante_pack_block_tail_bwd_multi", "tante_pack_block_train_multi", "tante_fold_fwd",
+               "tante_pack_block_train", "tante_pack_block_tail_bwd")
+    spy = Spy(monkeypatch, entries=entries)
+    outs = []
+    for batched, want in ((True, (1, 1, 1, 0, 0, 0)), (False, (0, 0, 0, 4, 2, 4))):
+        monkeypatch.setattr(TF, "BATCH_PREP", batched)
+        c0 = dict(spy.n)
+        with TF.fold_scope():
+            outs.append(TF.tante_train_forward(m, inp, L.BF16).detach().clone())
+        assert tuple(spy.n[e] - c0[e] for e in entries) == want, (batched, spy.n)
+    assert torch.equal(outs[0], outs[1])
+
+
 @pytest.mark.parametrize("M", [48 * 5, 64 * 3 + 17, 4096])
 def test_block_head_bwd_against_float64(dev, M):
     """tante_block_head_bwd: dx = dx1 + rstd (dxh - mean(dxh) - xh mean(dxh xh)), dxh = dqkv W, against float64 on the bf16-rounded

@@ -898,3 +898,163 @@ def test_bench_side_legs_run_only_with_full(monkeypatch, capsys, full):
     assert out["full"] is full and out["value"] == 1e4 and out["ms_per_step"] == 6.4 and out["steps"] == 10 and out["warmup"] == 3
     assert (out["roofline"] is not None) is full and out["roofline_frac"] == (0.3 if full else None)
     assert out["train"] is None and out["cpu_baseline"] is None and out["workloads"] is None
+
+
+# ---- how block_train runs a block: the decisions, with every launch stubbed --------------------------------------------------------
+CHAIN = ("LayerNormSkipFn", "LinearFn", "AttentionFn", "BranchOutFn", "LayerNormSkipFn", "LinearFn", "BranchOutFn")
+# switch setting -> (FUSED_TRAIN_FORWARD, FUSED_TAIL_BACKWARD, FUSED_HEAD_BACKWARD, FUSED_BLOCK_BACKWARD), as test_fused_training_forward_equals_unfused sets them
+PLAN_SWITCHES = {"block": (True, True, True, True), "tail": (True, True, True, False), "tail_nohead": (True, True, False, False),
+                 True: (True, False, False, False), False: (False, False, False, False)}
+# (nodes applied, (need_x1, need_qkv) of the forward launch or None, BlockFn's (tail, head, forward) streams or None, packs of a first call)
+PLAN_PLAIN = (CHAIN, None, None, ())
+PLAN_SAVED = (CHAIN, (True, True), None, ("fs",))                      # the chain over the fused forward's saved tensors
+PLAN_3 = (("BlockFn",), (False, True), ("bt", "bh", None), ("fs", "bt", "bh"))
+# (setting, scope open and gradient slots present, the library has the one-launch backward for (L, causal)) -> what a call does
+PLAN_WANT = {("block", True, True): (("BlockFn",), (False, False), ("bt", "bh", "fs"), ("fs", "bt", "bh")),
+             ("block", True, False): PLAN_3, ("tail", True, True): PLAN_3, ("tail", True, False): PLAN_3,
+             ("tail_nohead", True, True): (("BlockFn",), (False, True), ("bt", None, None), ("fs", "bt")),
+             ("tail_nohead", True, False): (("BlockFn",), (False, True), ("bt", None, None), ("fs", "bt")),
+             (True, True, True): PLAN_SAVED, (True, True, False): PLAN_SAVED, (False, True, True): PLAN_PLAIN, (False, True, False): PLAN_PLAIN,
+             ("block", False, True): PLAN_SAVED, ("block", False, False): PLAN_SAVED, ("tail", False, True): PLAN_SAVED,
+             ("tail", False, False): PLAN_SAVED, ("tail_nohead", False, True): PLAN_SAVED, ("tail_nohead", False, False): PLAN_SAVED,
+             (True, False, True): PLAN_SAVED, (True, False, False): PLAN_SAVED, (False, False, True): PLAN_PLAIN, (False, False, False): PLAN_PLAIN}
+PLAN_SEQS = [("T", 2, 4, 2, 2), ("T", 1, 5, 2, 2), ("H", 1, 1, 24, 2), ("W", 1, 1, 1, 48)]      # (L, causal) = (4, yes), (5, yes), (24, no), (48, no)
+
+
+class _BlockTrainStubs:
+    """block_train on CPU tensors: the fold, the pack and forward wrappers and every node's apply replaced by recorders (names that
+    train_forward reaches through their modules and classes, so the same stubs serve any arrangement of the code inside it)."""
+
+    def __init__(self, monkeypatch, blk, in_proj_slots=True):
+        from tante_amd import autograd as A, kernels as K, train_forward as TF
+        self.TF, self.tags, self.log = TF, {}, []
+
+        def folded(w, b, ln, pre=None):
+            if TF._FOLDS is None or not torch.is_grad_enabled():
+                return w.detach() * 1.0, b.detach() * 1.0
+            key = (id(ln), id(w))
+            if key not in TF._FOLDS:
+                we, be = w.detach().clone(), b.detach().clone()
+                if in_proj_slots or ln is not blk.ln1:
+                    we._tante_grad, be._tante_grad = torch.zeros_like(we), torch.zeros_like(be)
+                TF._FOLDS[key] = (we, be)
+            return TF._FOLDS[key]
+
+        def slot(q):      # autograd._grad_slot without its is_cuda test
+            g = None if q is None else getattr(q, "_tante_grad", None)
+            return q.grad if (g is None and isinstance(q, torch.nn.Parameter)) else g
+
+        def stream(tag):
+            t = torch.zeros(1)
+            self.tags[id(t)] = (tag, t)
+            self.log.append(("pack", tag))
+            return t
+
+        def forward(x, st, C_, n_head, hidden, seq, causal, eps, p, seeds, need_x1=True, need_qkv=True):
+            self.log.append(("forward", self.tag(st), need_x1, need_qkv, tuple(seeds)))
+            t = {k: torch.zeros(1) for k in ("out", "xh1", "qkv", "o", "xh2", "hpre", "act", "st1", "x1", "st2")}
+            t["x1"], t["qkv"] = (t["x1"] if need_x1 else None), (t["qkv"] if need_qkv else None)
+            return t
+        monkeypatch.setattr(TF, "_folded", folded)
+        monkeypatch.setattr(A, "_grad_slot", slot)
+        monkeypatch.setattr(K, "pack_block_train", lambda params, C_, hidden: stream("fs"))
+        monkeypatch.setattr(K, "pack_block_tail_bwd", lambda a, b, c, C_, hidden: stream("bh" if a.shape[0] == C_ and a._base is not None else "bt"))
+        monkeypatch.setattr(K, "block_fused_train", forward)
+        monkeypatch.setattr(K, "block_bwd_fused_supported", lambda C_, nh, hidden, Lq, causal: (Lq, bool(causal)) in ((4, True), (48, False)))
+        for name in ("LayerNormSkipFn", "LinearFn", "AttentionFn", "MaskedAttentionFn", "BranchOutFn", "BlockTailFn", "BlockFn"):
+            def apply(*a, _n=name):
+                self.log.append(("node", _n, a))
+                out = torch.zeros(1)
+                return (out, a[0]) if _n == "LayerNormSkipFn" else out
+            monkeypatch.setattr(getattr(A, name), "apply", apply)
+
+    def tag(self, t):
+        return None if t is None else self.tags[id(t)][0]
+
+    def call(self, blk, x, seq, causal, masks=None):
+        """One block_train call -> (nodes, forward launch, BlockFn streams, packs, seeds drawn, BLOCK_CALLS deltas, chain saw saved tensors)."""
+        from tante_amd import autograd as A, _lib as L
+        self.log.clear()
+        s0, c0 = A._SEED[0], list(self.TF.BLOCK_CALLS)
+        self.TF.block_train(blk, x, seq, causal, L.BF16, masks)
+        nodes = [e for e in self.log if e[0] == "node"]
+        fwd = [e for e in self.log if e[0] == "forward"]
+        assert len(fwd) <= 1
+        bf = [e[2] for e in nodes if e[1] == "BlockFn"]
+        streams = (self.tag(bf[0][10]), self.tag(bf[0][17]), self.tag(bf[0][18])) if bf else None
+        if fwd and fwd[0][4] != (0, 0, 0):
+            assert len(set(fwd[0][4])) == 3                           # three different seeds, in the order they were drawn
+        saved = [len(e[2]) > 3 and e[2][3] is not None for e in nodes if e[1] == "LayerNormSkipFn"]
+        return (tuple(e[1] for e in nodes), fwd[0][2:4] if fwd else None, streams, tuple(e[1] for e in self.log if e[0] == "pack"),
+                A._SEED[0] - s0, (self.TF.BLOCK_CALLS[0] - c0[0], self.TF.BLOCK_CALLS[1] - c0[1]), saved)
+
+
+def _plan_block_and_x(p):
+    import tante_amd
+    torch.manual_seed(3)
+    blk = tante_amd.TransformerBlock(256, 8, mlp_ratio=1.0, dropout=p).train()
+    return blk, torch.zeros(48, 256, requires_grad=True)
+
+
+@pytest.mark.parametrize("p", [0.25, 0.0])
+@pytest.mark.parametrize("setting", list(PLAN_SWITCHES), ids=str)
+def test_block_train_decisions(monkeypatch, setting, p):
+    """What block_train does with one fused-shape block, as a table over the five switch settings x fold scope open / closed x block
+    records on / off x gradient slots present / absent x four (L, causal), two consecutive calls each: the node applied, the forward
+    launch's need_x1 / need_qkv, the streams BlockFn gets, both BLOCK_CALLS counters, the seeds drawn, and what is packed when (in a
+    scope: by the first call only; without one: by every call).  The one-launch backward exists for (4, causal) and (48, not), not for
+    (5, causal) and (24, not).  Expected values: literals read off the code before the BlockPlan refactor, on which this test passes too."""
+    import contextlib
+    from tante_amd import kernels as K, train_forward as TF
+    blk, x = _plan_block_and_x(p)
+    stubs = _BlockTrainStubs(monkeypatch, blk)
+    for name, on in zip(("FUSED_TRAIN_FORWARD", "FUSED_TAIL_BACKWARD", "FUSED_HEAD_BACKWARD", "FUSED_BLOCK_BACKWARD"), PLAN_SWITCHES[setting]):
+        monkeypatch.setattr(TF, name, on)
+    for scope in (True, False):
+        for records in (True, False):
+            monkeypatch.setattr(TF, "BLOCK_RECORDS", records)
+            for slots in (True, False):
+                for q in blk.parameters():
+                    q.grad = torch.zeros_like(q) if slots else None
+                for pattern in PLAN_SEQS:
+                    seq, causal = K.make_seq(*pattern), pattern[0] == "T"
+                    avail = (seq.L, causal) in ((4, True), (48, False))
+                    nodes, fwd, streams, packs = PLAN_WANT[(setting, scope and slots, avail)]
+                    with (TF.fold_scope() if scope else contextlib.nullcontext()):
+                        for call in range(2):
+                            got = stubs.call(blk, x, seq, causal)
+                            case = (scope, records, slots, pattern, call)
+                            assert got[:3] == (nodes, fwd, streams), (case, got)
+                            assert got[3] == (packs if (call == 0 or not scope) else ()), (case, got)
+                            assert got[4] == (3 if (fwd is not None and p > 0.0) else 0), (case, got)
+                            assert got[5] == (1, 1 if nodes == ("BlockFn",) else 0), (case, got)
+                            assert got[6] == ([] if nodes == ("BlockFn",) else [fwd is not None] * 2), (case, got)
+    assert TF._FOLDS is None
+
+
+def test_block_train_decisions_off_the_table(monkeypatch):
+    """The edges of block_train beside the table: a folded in-projection without accumulators ends the chain in BlockTailFn; an x that is
+    not contiguous takes the plain chain, also when the block's record is in the scope; masks take the chain with the masked attention
+    node and refuse dropout."""
+    from tante_amd import kernels as K, train_forward as TF
+    seq = K.make_seq("T", 2, 4, 2, 2)
+    blk, x = _plan_block_and_x(0.25)
+    for q in blk.parameters():
+        q.grad = torch.zeros_like(q)
+    with monkeypatch.context() as mp:
+        stubs = _BlockTrainStubs(mp, blk, in_proj_slots=False)
+        with TF.fold_scope():
+            for call in range(2):
+                got = stubs.call(blk, x, seq, True)
+                assert got == (CHAIN[:3] + ("BlockTailFn",), (False, True), None, ("fs", "bt") if call == 0 else (), 3, (1, 0), [True]), got
+    stubs = _BlockTrainStubs(monkeypatch, blk)
+    strided = torch.zeros(32, 512)[:, :256].requires_grad_(True)
+    with TF.fold_scope():
+        assert stubs.call(blk, strided, seq, True) == (CHAIN, None, None, (), 0, (1, 0), [False, False])
+        assert stubs.call(blk, x, seq, True)[:2] == (("BlockFn",), (False, False))
+        assert stubs.call(blk, strided, seq, True) == (CHAIN, None, None, (), 0, (1, 0), [False, False])
+        with pytest.raises(NotImplementedError, match="attn_mask / key_padding_mask under autograd with dropout > 0"):
+            stubs.call(blk, x, seq, True, masks=(None, None))
+        blk.eval()
+        masked = CHAIN[:2] + ("MaskedAttentionFn",) + CHAIN[3:]
+        assert stubs.call(blk, x, seq, True, masks=(None, None)) == (masked, None, None, (), 0, (1, 0), [False, False])
