@@ -40,8 +40,10 @@ class LinearWarmupCosineAnnealingLR:
                  last_epoch: int = -1):
         self.optimizer, self.warmup_epochs, self.max_epochs = optimizer, warmup_epochs, max_epochs
         self.warmup_start_lr, self.eta_min = warmup_start_lr, eta_min
-        groups = getattr(optimizer, "param_groups", None)
-        self.base_lrs = [g["lr"] for g in groups] if groups else [optimizer.lr]
+        # FlatAdamW keeps its rate in `.lr` and REBUILDS param_groups on every access (optim.py): an entry written into that list is lost,
+        # so an optimizer that has `.lr` is driven through it
+        self._own_lr = hasattr(optimizer, "lr")
+        self.base_lrs = [optimizer.lr] if self._own_lr else [g["lr"] for g in optimizer.param_groups]
         self.last_epoch = last_epoch
         self.step()
 
@@ -52,12 +54,11 @@ class LinearWarmupCosineAnnealingLR:
     def step(self) -> None:
         self.last_epoch += 1
         lrs = self.get_last_lr()
-        groups = getattr(self.optimizer, "param_groups", None)
-        if groups:
-            for g, lr in zip(groups, lrs):
-                g["lr"] = lr
-        else:
+        if self._own_lr:
             self.optimizer.lr = lrs[0]
+        else:
+            for g, lr in zip(self.optimizer.param_groups, lrs):
+                g["lr"] = lr
 
 
 # ---- CViT query-point harness ---------------------------------------------------------------------------------------------------

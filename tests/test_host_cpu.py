@@ -869,6 +869,161 @@ def test_train_node_bars_reject_near_misses():
     seen(wt.grad.transpose(-1, -2), wt.grad, R.BF16_BAR, "deconv dW with (kh, kw) swapped")
 
 
+def _harness_step_sequence(R, case):
+    """The six-step sequence of tests/test_hip_harness_step.py for one of its cases: the start buckets and per step (gradient, keyword
+    arguments of the step functions)."""
+    gen = torch.Generator().manual_seed(101)
+    w0 = R.adam_weights(gen)
+    return w0, [(R.adam_grad(gen, norm), R.adam_case_args(case, k)) for k, norm in enumerate(R.ADAM_NORMS)]
+
+
+def test_harness_step_adamw_reference_matches_torch():
+    """The float64 restatement of tests/test_hip_harness_step.py (clip_grad_norm_ + AdamW on the flat bucket) over its six-step sequence
+    against torch.optim.AdamW in float64 driven by torch.nn.utils.clip_grad_norm_ on the same parameters (one of them complex), to 1e-12;
+    also with clip_grad_value_ in front and with a per-step lr."""
+    import test_hip_harness_step as R
+    live = R.adam_live_mask()
+    for name in ("a-grad_scale1", "c-lr_per_step", "f-clip_grad_value"):
+        case = R.ADAM_CASES[name]
+        w0, seq = _harness_step_sequence(R, case)
+        params = [torch.nn.Parameter(v.clone().to(torch.complex128 if v.is_complex() else torch.float64)) for v in R._param_views(w0)]
+        h = R.ADAM_HYPER
+        opt = torch.optim.AdamW(params, lr=h["lr"], betas=h["betas"], eps=h["eps"], weight_decay=h["weight_decay"])
+        p, m, v = w0.double(), torch.zeros_like(w0, dtype=torch.float64), torch.zeros_like(w0, dtype=torch.float64)
+        for k, (g, kw) in enumerate(seq):
+            for q, gv in zip(params, R._param_views(g)):
+                q.grad = gv.clone().to(q.dtype)
+            if "clip_value" in case:
+                torch.nn.utils.clip_grad_value_([q for q in params if not q.is_complex()], case["clip_value"])
+                c = params[-1].grad      # (clip_grad_value_ clamps real tensors: the complex one through its (re, im) view)
+                torch.view_as_real(c).clamp_(-case["clip_value"], case["clip_value"])
+            torch.nn.utils.clip_grad_norm_(params, h["max_norm"])
+            opt.param_groups[0]["lr"] = kw["lr"]
+            opt.step()
+            p, m, v = R.ref_adamw_step(p, m, v, g, k + 1, clip_value=case.get("clip_value"), **kw)
+            got = torch.cat([torch.view_as_real(q.detach()).reshape(-1) if q.is_complex() else q.detach().reshape(-1) for q in params])
+            assert float((got - p[live]).abs().max()) <= 1e-12, (name, k)
+            assert not p[~live].any()
+
+
+def test_harness_step_metric_references_match_the_oracles():
+    """ref_metric_sums / ref_metrics of tests/test_hip_harness_step.py in float64 against the oracle's metrics (which tests/golden pins to
+    the reference's) on one small case, 1e-12 relative; the five sums against their definitions."""
+    import test_hip_harness_step as R
+    from oracle import tante_oracle as TO
+
+    def rel(a, b):
+        return float((a.double() - b.double()).norm() / b.double().norm())
+
+    gen = torch.Generator().manual_seed(10)
+    x, y = torch.randn(2, 3, 6, 5, 4, generator=gen, dtype=torch.float64) + 3.0, torch.randn(2, 3, 6, 5, 4, generator=gen, dtype=torch.float64) + 3.0
+    m = R.ref_metrics(x, y)
+    assert rel(m["MSE"], TO.mse(x, y)) < 1e-12 and rel(m["RMSE"], TO.mse(x, y).sqrt()) < 1e-12
+    assert rel(m["NMSE"], TO.nmse(x, y)) < 1e-12 and rel(m["NRMSE"], TO.nmse(x, y).sqrt()) < 1e-12
+    assert rel(m["VMSE"], TO.nmse(x, y, mode="std")) < 1e-12 and rel(m["VRMSE"], TO.vrmse(x, y)) < 1e-12
+    assert rel(m["L2RE"], TO.l2re(x, y)) < 1e-12
+    assert rel(m["NNMSE"], TO.nnmse(x, y)) < 1e-12 and rel(m["NNMSE_std"], TO.nnmse(x, y, mode="std")) < 1e-12
+    assert rel(R.ref_metrics(x, y, 0.3)["NMSE"], TO.nmse(x, y, 0.3)) < 1e-12
+    s = R.ref_metric_sums(x, y)
+    n = 30
+    assert s.shape == (2, 3, 4, 5)
+    assert rel(s[..., 0] / n, TO.mse(x, y)) < 1e-12 and rel(s[..., 1], (y * y).sum((2, 3))) < 1e-12 and rel(s[..., 2], y.sum((2, 3))) < 1e-12
+    piv = y[:, :, :1, :1]
+    assert rel(s[..., 3], ((y - piv) ** 2).sum((2, 3))) < 1e-12 and rel(s[..., 4], (y - piv).sum((2, 3))) < 1e-12
+    # the shifted moments give the variance whatever the pivot: z2 - z1^2 / n = sum (y - mean)^2
+    assert rel((s[..., 3] - s[..., 4] ** 2 / n) / (n - 1), y.var(dim=(2, 3), unbiased=True)) < 1e-10
+    # the fields of the GPU test: frame means 1e3 apart between (b, t) pairs, 7e3 apart between channels, spread 1
+    xf, yf = R.metric_fields(3, (33, 20), gen)
+    mean = yf.double().mean(dim=(2, 3))
+    assert float((mean[0, 1] - mean[0, 0] - 1e3).abs().max()) < 1.0 and float((mean[..., 1] - mean[..., 0] - 7e3).abs().max()) < 1.0
+    assert 0.8 < float(yf.double().std(dim=(2, 3)).min()) and float(yf.double().std(dim=(2, 3)).max()) < 1.2
+
+
+def test_harness_step_bars_reject_single_mutations():
+    """The fp32 restatement of adamw_kernel (tests/test_hip_harness_step.py::kernel_adamw_step32), measured the way the GPU test measures
+    (per step, restarted from the fp32 state, max |p - p_ref| / max |update_ref| against the float64 reference): unmutated it meets the
+    1e-4 bar on every case's hyper-parameters, and each of six single mutations lands OUTSIDE TWICE the bar within the six steps (with
+    grad_scale = 0.5, so that ignoring it is a mutation).  So the bar sees these defects."""
+    import test_hip_harness_step as R
+
+    def worst(case, mutation):
+        w0, seq = _harness_step_sequence(R, case)
+        p, m, v = w0, torch.zeros_like(w0), torch.zeros_like(w0)
+        out = 0.0
+        for k, (g, kw) in enumerate(seq):
+            pr, _, _ = R.ref_adamw_step(p, m, v, g, k + 1, **kw)
+            pm, _, _ = R.kernel_adamw_step32(p, m, v, g, k + 1, mutation=mutation, **kw)
+            out = max(out, R.update_ratio(pm, pr, p))
+            p, m, v = R.kernel_adamw_step32(p, m, v, g, k + 1, **kw)      # the state advances unmutated, as on the GPU
+        return out
+
+    for name in ("a-grad_scale1", "b-grad_scale0.5", "c-lr_per_step", "d-max_norm0-stale_sumsq"):
+        r = worst(R.ADAM_CASES[name], None)
+        assert r <= R.UPDATE_BAR, (name, r)
+    for mutation in R.ADAM_MUTATIONS:
+        r = worst(R.ADAM_CASES["b-grad_scale0.5"], mutation)
+        assert r > 2 * R.UPDATE_BAR, f"{mutation}: {r:.3e} inside twice the bar"
+
+
+def test_lr_schedule_function_and_scheduler_match_the_reference_row():
+    """tante_amd.warmup_cosine_lr and the scheduler object stepped per epoch against all 41 values of g10's lr_schedule row (the
+    reference's scheduler run past max_epochs), 1e-12 relative -- on an optimizer that exposes .lr, on one that exposes param_groups, and
+    on one shaped like FlatAdamW, whose param_groups is rebuilt from .lr on every access."""
+    import types
+    import tante_amd
+    from tante_amd.harness import LinearWarmupCosineAnnealingLR
+    lrs = load_golden("g10_metrics")["lr_schedule"].numpy()
+    assert len(lrs) == 41
+    for e in range(41):
+        assert abs(tante_amd.warmup_cosine_lr(e, 5e-5, 2, 34, 5e-6, 5e-6) - lrs[e]) <= 1e-12 * lrs[e], e
+
+    class FlatLike:
+        def __init__(self):
+            self.lr = 5e-5
+
+        @property
+        def param_groups(self):
+            return [{"params": [], "lr": self.lr}]
+
+    plain = types.SimpleNamespace(lr=5e-5)
+    torch_opt = torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=5e-5)
+    flat = FlatLike()
+    for opt, read in ((plain, lambda: plain.lr), (torch_opt, lambda: torch_opt.param_groups[0]["lr"]), (flat, lambda: flat.lr)):
+        sch = LinearWarmupCosineAnnealingLR(opt, warmup_epochs=2, max_epochs=34, warmup_start_lr=5e-6, eta_min=5e-6)
+        for e in range(41):
+            assert abs(read() - lrs[e]) <= 1e-12 * lrs[e] and abs(sch.get_last_lr()[0] - lrs[e]) <= 1e-12 * lrs[e], (type(opt).__name__, e, read())
+            sch.step()
+
+
+def test_metric_sums_dispatch_constants_match_the_source():
+    """tests/test_hip_harness_step.py names in every case id the kernel and loop form that tante_metric_sums reaches, from the dispatch
+    rule restated there.  The rule's numbers are read out of train.hip here, so that a change of the per-pixel threshold, its chunk, the
+    four-pixel loop or the generic kernel's chunking fails THIS test instead of leaving the ids silently wrong."""
+    import test_hip_harness_step as R
+    src = open(os.path.join(ROOT, "tante_amd", "csrc", "train.hip")).read()
+    m = re.search(r"if \(\(C == 4 \|\| C == 2 \|\| C == 1\) && HW >= (\d+)\)", src)
+    assert m and int(m.group(1)) == R.PX_MIN_HW and R.PX_CHANNELS == (1, 2, 4)
+    m = re.search(r"const long pchunk = (\d+);", src)
+    assert m and int(m.group(1)) == R.PX_CHUNK
+    m = re.search(r"long chunks = \(HW \* C \+ (\d+) \* (\d+) - 1\) / \((\d+) \* (\d+)\);", src)
+    assert m and int(m.group(1)) * int(m.group(2)) == int(m.group(3)) * int(m.group(4)) == R.GENERIC_ELEMS_PER_BLOCK
+    assert "for (; s + 768 < s1; s += 1024)" in src and "for (; s < s1; s += 256)" in src and "(256 % C) == 0" in src
+    assert R.sums_form(4, 4095).startswith("generic-fixedc") and R.sums_form(4, 4096) == "px4-hw4096-1chunks-last4096[unroll4+tail0]"
+    assert R.sums_form(2, 4097).endswith("last1[unroll0+tail1]") and R.sums_form(1, 16 * 331).endswith("last1200[unroll1+tail1]")
+    assert R.sums_form(16, 3001) == "generic-fixedc-C16-hw3001-3chunks-last999" and R.sums_form(7, 660).startswith("generic-varc")
+    # every form has a case: both generic channel paths with one and with several chunks, the per-pixel kernel at 1, 2 and 4 channels
+    # with only four-pixel trips, only scalar trips, and both
+    ids = [c.id for c in R.METRIC_CASES]
+    for want in ("generic-fixedc-C8-hw1073-1chunks", "generic-fixedc-C16-hw3000-3chunks", "generic-varc-C3", "generic-varc-C7", "generic-fixedc-C4-hw4095"):
+        assert any(i.startswith(want) for i in ids), want
+    for C in (1, 2, 4):
+        for want in ("last4096[unroll4+tail0]", "last1[unroll0+tail1]", "last1024[unroll1+tail0]", "last1200[unroll1+tail1]", "last809[unroll1+tail3]"):
+            assert any(i.startswith(f"px{C}-") and want in i for i in ids), (C, want)
+    for kernel in ("generic", "px"):
+        for lay in ("cl", "cf", "slice", "copy"):
+            assert any(i.startswith(kernel) and i.endswith("-" + lay) for i in ids), (kernel, lay)
+
+
 @pytest.mark.parametrize("full", [False, True])
 def test_bench_side_legs_run_only_with_full(monkeypatch, capsys, full):
     """A plain `bench.py` run times the headline leg and prints its line; the roofline pass (and the train, CPU-baseline and side-workload
