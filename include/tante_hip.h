@@ -389,6 +389,21 @@ int tante_attention_flash(const void* qkv, void* o, float* stats, int dtype, int
                           float p_drop, uint64_t seed, void* stream);
 int tante_attention_flash_bwd(const void* qkv, const void* o, const void* dO, float* stats, void* dqkv, int dtype, int C, int n_head,
                               const TanteSeq* seq, int causal, float p_drop, uint64_t seed, void* stream);
+/* The flash kernels under nn.MultiheadAttention's masks, on DENSE sequences (token b * L + l): the function of tante_attention_masked /
+ * tante_attention_masked_bwd (the reference's TransformerBlock.forward(x, key_padding_mask, attn_mask, causal), attn_backbone.py:59-72)
+ * on the matrix cores, with the probability dropout of attn_backbone.py:47-48.  The arguments of the pair above with (Bp, L) in place of
+ * the descriptor, and the masks as tante_attention_masked takes them: attn_mask additive fp32, (L, L) shared (mask_bstride 0) or
+ * (Bp * n_head, L, L) (mask_bstride L * L), 16-byte aligned; key_padding_mask additive fp32 (Bp, L); either may be NULL; -inf blocks a
+ * key (+inf is not a mask value).  Masks get no gradient.  The dropout mask index is the unmasked pair's.  With both masks NULL these run
+ * the unmasked kernels on the dense descriptor: the same bits.  A query whose keys are ALL blocked gets o = NaN (torch's softmax of such
+ * a row, and tante_attention_masked's), lse2 = -inf, dq = 0, and adds nothing to dk and dv.  Added without moving the ABI number: see
+ * ABI_VERSION in tante_amd/_lib.py. */
+int tante_attention_flash_masked(const void* qkv, void* o, float* stats, int dtype, int C, int n_head, int Bp, int L, int causal,
+                                 const float* attn_mask, int64_t mask_bstride, const float* key_padding_mask, float p_drop, uint64_t seed,
+                                 void* stream);
+int tante_attention_flash_masked_bwd(const void* qkv, const void* o, const void* dO, float* stats, void* dqkv, int dtype, int C, int n_head,
+                                     int Bp, int L, int causal, const float* attn_mask, int64_t mask_bstride, const float* key_padding_mask,
+                                     float p_drop, uint64_t seed, void* stream);
 
 /* ---- the token-local tail of a rollout call in ONE launch (head_enc.hip; bf16, C = 256, D <= 16, Hp Wp % 16 == 0) -----------------
  * tante_head_enc_fused: every Taylor order's derivative head + the Taylor sum (as tante_head_fused_multi_streams: rows[k] = the residual

@@ -29,6 +29,7 @@ import torch.nn as nn
 # brings the separate launch back (A/B timing, tests).
 from . import _lib as L
 from . import kernels as K
+from . import attn_flash as FA
 from . import options as _O
 
 FUSE_TPROP = _O.register("TANTE_FUSE_TPROP", True, __name__, "FUSE_TPROP")
@@ -267,7 +268,7 @@ class TransformerBlock(nn.Module):
         return am, kp
 
     def _forward_masked(self, x: torch.Tensor, Bp: int, Lq: int, causal: bool, compute: int, key_padding_mask, attn_mask) -> torch.Tensor:
-        """The unfused block with the masked attention kernel (tante_attention_masked)."""
+        """The unfused block with the masked attention kernel (tante_attention_masked; the masked flash forward where masked_route says so)."""
         C_ = self.embed_dim
         dev = x.device
         am, kp = self._masks(dev, Bp, Lq, causal, key_padding_mask, attn_mask)
@@ -277,7 +278,10 @@ class TransformerBlock(nn.Module):
         qkv = torch.empty(n_tok, 3 * C_, dtype=adt, device=dev)
         K.linear(x, pk["qkv"], qkv, M=n_tok, ln=True, ln_eps=self.ln1.eps)
         o = torch.empty(n_tok, C_, dtype=adt, device=dev)
-        K.attention_masked(qkv, o, C_, self.n_head, Bp, Lq, causal, am, kp)
+        if FA.masked_route(Lq, 0.0, FA.supported(L.BF16 if adt == torch.bfloat16 else L.F32, C_, self.n_head, Lq), FA.ATTN_FLASH) == FA.MASKED_FLASH:
+            FA.forward(qkv, o, None, C_, self.n_head, K.dense_seq(Bp, Lq), causal, 0.0, 0, am, kp)      # TANTE_ATTN_FLASH (off by default)
+        else:
+            K.attention_masked(qkv, o, C_, self.n_head, Bp, Lq, causal, am, kp)
         K.linear(o, pk["out"], x, M=n_tok, residual=x)
         h = torch.empty(n_tok, self.hidden, dtype=adt, device=dev)
         K.linear(x, pk["fc1"], h, M=n_tok, ln=True, ln_eps=self.ln2.eps, act=L.ACT_GELU_TANH)

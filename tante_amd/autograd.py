@@ -1025,6 +1025,34 @@ class MaskedAttentionFn(Function):
         return dqkv, None, None, None, None, None, None, None
 
 
+class MaskedFlashAttentionFn(Function):
+    """MaskedAttentionFn on the flash kernels (csrc/attn_flash.hip, masked form), WITH attention-probability dropout: the operator through
+    which attn_mask / key_padding_mask and dropout > 0 run together.  Masks as MaskedAttentionFn takes them (additive fp32, no gradient);
+    p: dropout probability; seed: the dropout seed, None = next_seed().  The forward saves o and the row statistics for the backward."""
+
+    @staticmethod
+    def forward(ctx, qkv, Cc, n_head, Bp, Lq, causal, attn_mask, key_padding_mask, p=0.0, seed=None):
+        seq = K.dense_seq(Bp, Lq)
+        p = float(p)
+        seed = 0 if p <= 0 else (next_seed() if seed is None else int(seed))
+        o = torch.empty(qkv.shape[0], Cc, dtype=qkv.dtype, device=qkv.device)
+        stats = FA.new_stats(qkv, n_head, seq)
+        FA.forward(qkv, o, stats, Cc, n_head, seq, causal, p, seed, attn_mask, key_padding_mask)
+        ctx.save_for_backward(qkv, o, stats)
+        ctx.a = (Cc, n_head, seq, bool(causal), p, seed)
+        ctx.masks = (attn_mask, key_padding_mask)      # constants (no gradient): kept alive for the backward launch
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, stats = ctx.saved_tensors
+        Cc, nh, seq, causal, p, seed = ctx.a
+        do = do.contiguous().to(qkv.dtype)
+        dqkv = torch.empty_like(qkv)
+        FA.backward(qkv, o, do, stats, dqkv, Cc, nh, seq, causal, p, seed, *ctx.masks)
+        return (dqkv,) + (None,) * 9
+
+
 class DropoutAddFn(Function):
     """out = res + dropout_p(y)   (x + self.drop(y), attn_backbone.py:81-82)."""
 

@@ -26,6 +26,21 @@
 // and walks 32 queries to stay there; with two key tiles its fragments alone would be 224 registers.  The 96-byte (fp32: 144-byte) rows keep the
 // transposing reads of the four 16-lane groups on different banks, as in attention.hip.
 //
+// The masked form (template parameter MASKED; the unmasked instantiations compile to the code they had): attn_mask / key_padding_mask as
+// tante_attention_masked takes them, dense sequences only.  The kernels work on scores in the log2 domain (s c2), so a finite mask
+// value enters as mask * log2(e); a -inf entry of either mask never enters a sum -- it makes the key INVALID, like the causal and
+// kj < L tests (no -inf - (-inf) is ever formed).  lse2, the recomputed P of both backward passes and delta all include the mask; the
+// dropout keep-mask index does not change; masks get no gradient.  Mask reads: a mask entry is used by exactly one lane, so an LDS image
+// of the attn_mask tile would buy no reuse, only a second copy and a barrier -- the reads are direct.  In the query-stationary passes a
+// lane reads four consecutive keys of its query's mask row (one 16-byte load when L % 4 == 0); over a 64-key tile the 16 lanes of a
+// group cover 256 contiguous bytes of the row, two whole 128-byte lines.  The key-stationary pass reads a key column (dword loads; 16
+// lanes cover 64 contiguous bytes of one mask row, and a wave's two key tiles share the line).  key_padding_mask IS reused by every
+// query, so its 64 entries per key tile sit in LDS beside K / V (query-stationary) or in one register per key tile (key-stationary).
+// The all-blocked-row rule is tante_attention_masked's: a query whose keys are all blocked gets o = 0 * (1 / 0) = NaN (torch's softmax
+// of such a row), lse2 = -inf and delta = NaN; its dq is 0, and the key-stationary pass stages its Q / dO rows and statistics as zeros,
+// so it adds nothing to dk and dv.  Resource report of the masked instantiations (no scratch, no spills): bf16 forward 182 VGPRs, dq
+// pass 140, dk / dv pass 196 + 48; fp32 forward 214, dq pass 180, dk / dv pass 142 -- the occupancies of the unmasked forms.
+//
 // fp32 is the same structure on v_mfma_f32_16x16x4_f32 with scalar LDS fragment reads: exact fp32 products, not tuned.
 // Inline assembly: the transposing LDS reads and the wait that covers them are ONE asm statement.
 #include "common.hip.h"
@@ -40,6 +55,13 @@ constexpr int FA_BQ = 4 * 16 * FA_QT;
 
 __device__ __forceinline__ long fa_token(const TanteSeq& q, int s, int l) {
   return (long)(s / q.n_s0) * q.S1 + (long)(s % q.n_s0) * q.S0 + (long)(l / q.n_l0) * q.P1 + (long)(l % q.n_l0) * q.P0;
+}
+
+// the masked form addresses dense sequences only (token = s L + l): no descriptor arithmetic there
+template <bool DENSE>
+__device__ __forceinline__ long fa_tok(const TanteSeq& q, int s, int l) {
+  if constexpr (DENSE) return (long)s * q.L + l;
+  else return fa_token(q, s, l);
 }
 
 // two transposing reads + their wait in one statement (the result cannot be consumed before the wait)
@@ -185,15 +207,40 @@ __device__ __forceinline__ f32x4 fa_keep_keys(unsigned long long seed, unsigned 
   return k;
 }
 
+// ---- the masked form ----------------------------------------------------------------------------------------------------------------
+// nn.MultiheadAttention's attn_mask / key_padding_mask as tante_attention_masked takes them (additive fp32; -inf blocks a key), on DENSE
+// sequences (token = s L + l).  The unmasked kernels carry an empty FaMask and none of this code.
+template <bool MASKED>
+struct FaMask {};
+template <>
+struct FaMask<true> {
+  const float* am;      // (L, L) with bstride 0, or (nseq n_head, L, L) with bstride L L; may be null
+  long bstride;
+  const float* kpm;     // (nseq, L); may be null
+};
+constexpr float FA_LOG2E = 1.4426950408889634f;
+
+// attn_mask entries of the keys kj0 .. kj0 + 3 (kj0 % 4 == 0) of one query's mask row: one 16-byte load when L % 4 == 0.  Addresses past
+// the row's end are clamped into it: those keys are invalid whatever is read.
+__device__ __forceinline__ f32x4 fa_mask_keys(const float* __restrict__ row, int kj0, int L, bool aligned) {
+  if (aligned) return *(const f32x4*)(row + min(kj0, L - 4));
+  f32x4 a;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) a[r] = row[min(kj0 + r, L - 1)];
+  return a;
+}
+
 // ---- forward ---------------------------------------------------------------------------------------------------------------------
 // grid = (ceil(L / 128) * nseq, n_head)
-template <bool F32>
+template <bool F32, bool MASKED>
 __global__ __launch_bounds__(256) void attn_flash_fwd_kernel(const void* __restrict__ qkv_, void* __restrict__ o_, float* __restrict__ stats, int C,
                                                              int n_head, TanteSeq sq, int nqb, int causal, float c2, float p_drop,
-                                                             unsigned long long seed) {
+                                                             unsigned long long seed, FaMask<MASKED> mk) {
   typedef Fa<F32> T;
   typedef typename T::elem elem;
   __shared__ __attribute__((aligned(16))) elem sm[2 * FA_BK * T::RS];
+  __shared__ __attribute__((aligned(16))) float kps[MASKED ? FA_BK : 1];      // masked: the key tile's key_padding_mask * log2(e)
+  const float cs = MASKED ? 1.0f : c2;      // masked: the scores are scaled when the mask is added, so the exponents take them as they are
   elem* Ks = sm;
   elem* Vs = sm + FA_BK * T::RS;
   const elem* qkv = (const elem*)qkv_;
@@ -212,12 +259,16 @@ __global__ __launch_bounds__(256) void attn_flash_fwd_kernel(const void* __restr
   long qtok[FA_QT];
   float m[FA_QT], lsum[FA_QT];
   f32x4 oa[FA_QT][2];
+  const float* arow[FA_QT];      // masked: the query's attn_mask row
 #pragma unroll
   for (int qt = 0; qt < FA_QT; ++qt) {
     qpos[qt] = q0 + qt * 16 + l15;
     qlive[qt] = qpos[qt] < L;
-    qtok[qt] = qlive[qt] ? fa_token(sq, s, qpos[qt]) : 0;
+    qtok[qt] = qlive[qt] ? fa_tok<MASKED>(sq, s, qpos[qt]) : 0;
     qf[qt] = qlive[qt] ? T::from_global(qkv + qtok[qt] * 3L * C + h * FA_D, kk) : T::zero_frag();
+    arow[qt] = nullptr;
+    if constexpr (MASKED)
+      if (mk.am) arow[qt] = mk.am + ((long)s * n_head + h) * mk.bstride + (long)min(qpos[qt], L - 1) * L;
     m[qt] = -INFINITY;
     lsum[qt] = 0.f;
     oa[qt][0] = oa[qt][1] = zero4;
@@ -229,9 +280,11 @@ __global__ __launch_bounds__(256) void attn_flash_fwd_kernel(const void* __restr
     __syncthreads();
     {
       const int kj = k0 + srow;
-      const elem* src = kj < L ? qkv + fa_token(sq, s, kj) * 3L * C + C + h * FA_D : nullptr;
+      const elem* src = kj < L ? qkv + fa_tok<MASKED>(sq, s, kj) * 3L * C + C + h * FA_D : nullptr;
       T::stage(Ks, srow, sc4, src);
       T::stage(Vs, srow, sc4, src ? src + C : nullptr);
+      if constexpr (MASKED)
+        if (tid < FA_BK) kps[tid] = (mk.kpm && k0 + tid < L) ? mk.kpm[(long)s * L + k0 + tid] * FA_LOG2E : 0.f;
     }
     __syncthreads();
     if (causal && k0 > wq_max) continue;      // wave-uniform: this wave's queries all precede the tile
@@ -249,26 +302,41 @@ __global__ __launch_bounds__(256) void attn_flash_fwd_kernel(const void* __restr
       unsigned vm = 0;
       float mx = -INFINITY;
 #pragma unroll
-      for (int jt = 0; jt < 4; ++jt)
+      for (int jt = 0; jt < 4; ++jt) {
+        f32x4 ma = zero4, mp = zero4;      // masked: attn_mask and key_padding_mask * log2(e) of the four keys
+        if constexpr (MASKED) {
+          if (arow[qt]) ma = fa_mask_keys(arow[qt], k0 + jt * 16 + 4 * kk, L, aligned);
+          mp = *(const f32x4*)(kps + jt * 16 + 4 * kk);
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int kj = k0 + jt * 16 + 4 * kk + r;
-          const bool valid = qlive[qt] && kj < L && (!causal || kj <= qpos[qt]);
-          vm |= (unsigned)valid << (jt * 4 + r);
-          if (valid) mx = fmaxf(mx, st[jt][r]);
+          bool valid = qlive[qt] && kj < L && (!causal || kj <= qpos[qt]);
+          if constexpr (MASKED) {
+            const float add = ma[r] * FA_LOG2E + mp[r];
+            valid = valid && add != -INFINITY;      // -inf never enters a sum: it makes the key invalid
+            // an invalid key's score IS -inf from here on (the reference point mref below is finite, so its exponential is a plain 0):
+            // no lane mask stays live across the softmax, which is what this form has no scalar registers for
+            st[jt][r] = valid ? st[jt][r] * c2 + add : -INFINITY;
+            mx = fmaxf(mx, st[jt][r]);
+          } else {
+            vm |= (unsigned)valid << (jt * 4 + r);
+            if (valid) mx = fmaxf(mx, st[jt][r]);
+          }
         }
+      }
       mx = fmaxf(mx, __shfl_xor(mx, 16));
       mx = fmaxf(mx, __shfl_xor(mx, 32));
       const float mn = fmaxf(m[qt], mx);
       const float mref = (mn == -INFINITY) ? 0.f : mn;
-      const float corr = (m[qt] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m[qt] - mref) * c2);
+      const float corr = (m[qt] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m[qt] - mref) * cs);
       m[qt] = mn;
       float ls = 0.f;
 #pragma unroll
       for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float e = ((vm >> (jt * 4 + r)) & 1) ? __builtin_amdgcn_exp2f((st[jt][r] - mref) * c2) : 0.f;
+          const float e = (MASKED || ((vm >> (jt * 4 + r)) & 1)) ? __builtin_amdgcn_exp2f((st[jt][r] - mref) * cs) : 0.f;
           st[jt][r] = e;
           ls += e;
         }
@@ -297,18 +365,20 @@ __global__ __launch_bounds__(256) void attn_flash_fwd_kernel(const void* __restr
     l += __shfl_xor(l, 32);
     if (!qlive[qt]) continue;
     T::store(o + qtok[qt] * (long)C + h * FA_D, kk, oa[qt], 1.0f / l);
-    if (stats && kk == 0) stats[(((long)s * n_head + h) * L + qpos[qt]) * 2] = m[qt] * c2 + __builtin_amdgcn_logf(l);
+    if (stats && kk == 0) stats[(((long)s * n_head + h) * L + qpos[qt]) * 2] = m[qt] * cs + __builtin_amdgcn_logf(l);
   }
 }
 
 // ---- backward, query-stationary: delta and dq ----------------------------------------------------------------------------------------
-template <bool F32>
+template <bool F32, bool MASKED>
 __global__ __launch_bounds__(256) void attn_flash_bwd_q_kernel(const void* __restrict__ qkv_, const void* __restrict__ o_, const void* __restrict__ do_,
                                                                float* __restrict__ stats, void* __restrict__ dqkv_, int C, int n_head, TanteSeq sq,
-                                                               int nqb, int causal, float scale, float c2, float p_drop, unsigned long long seed) {
+                                                               int nqb, int causal, float scale, float c2, float p_drop, unsigned long long seed,
+                                                               FaMask<MASKED> mk) {
   typedef Fa<F32> T;
   typedef typename T::elem elem;
   __shared__ __attribute__((aligned(16))) elem sm[2 * FA_BK * T::RS];
+  __shared__ __attribute__((aligned(16))) float kps[MASKED ? FA_BK : 1];
   elem* Ks = sm;
   elem* Vs = sm + FA_BK * T::RS;
   const elem* qkv = (const elem*)qkv_;
@@ -329,11 +399,15 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_q_kernel(const void* __res
   long qtok[FA_QT];
   float lse[FA_QT], delta[FA_QT];
   f32x4 dq[FA_QT][2];
+  const float* arow[FA_QT];
 #pragma unroll
   for (int qt = 0; qt < FA_QT; ++qt) {
     qpos[qt] = q0 + qt * 16 + l15;
     qlive[qt] = qpos[qt] < L;
-    qtok[qt] = qlive[qt] ? fa_token(sq, s, qpos[qt]) : 0;
+    qtok[qt] = qlive[qt] ? fa_tok<MASKED>(sq, s, qpos[qt]) : 0;
+    arow[qt] = nullptr;
+    if constexpr (MASKED)
+      if (mk.am) arow[qt] = mk.am + ((long)s * n_head + h) * mk.bstride + (long)min(qpos[qt], L - 1) * L;
     qf[qt] = gf[qt] = T::zero_frag();
     lse[qt] = 0.f;
     float d = 0.f;
@@ -359,9 +433,11 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_q_kernel(const void* __res
     __syncthreads();
     {
       const int kj = k0 + srow;
-      const elem* src = kj < L ? qkv + fa_token(sq, s, kj) * 3L * C + C + h * FA_D : nullptr;
+      const elem* src = kj < L ? qkv + fa_tok<MASKED>(sq, s, kj) * 3L * C + C + h * FA_D : nullptr;
       T::stage(Ks, srow, sc4, src);
       T::stage(Vs, srow, sc4, src ? src + C : nullptr);
+      if constexpr (MASKED)
+        if (tid < FA_BK) kps[tid] = (mk.kpm && k0 + tid < L) ? mk.kpm[(long)s * L + k0 + tid] * FA_LOG2E : 0.f;
     }
     __syncthreads();
     if (causal && k0 > wq_max) continue;
@@ -385,12 +461,24 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_q_kernel(const void* __res
           const int kj0 = k0 + jp * 32 + j * 16 + 4 * kk;
           f32x4 kp = f32x4{1.f, 1.f, 1.f, 1.f};
           if (p_drop > 0.f) kp = fa_keep_keys(seed, mrow, kj0, aligned, p_drop, ksc);
+          f32x4 ma = zero4, mp = zero4;      // masked: attn_mask and key_padding_mask * log2(e) of the four keys
+          if constexpr (MASKED) {
+            if (arow[qt]) ma = fa_mask_keys(arow[qt], kj0, L, aligned);
+            mp = *(const f32x4*)(kps + jp * 32 + j * 16 + 4 * kk);
+          }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int kj = kj0 + r;
-            const bool valid = qlive[qt] && kj < L && (!causal || kj <= qpos[qt]);
-            const float p = valid ? __builtin_amdgcn_exp2f(st[r] * c2 - lse[qt]) : 0.f;
-            ds[j][r] = p * (dp[r] * kp[r] - delta[qt]);
+            bool valid = qlive[qt] && kj < L && (!causal || kj <= qpos[qt]);
+            if constexpr (MASKED) {
+              const float add = ma[r] * FA_LOG2E + mp[r];
+              valid = valid && add != -INFINITY;
+              const float p = valid ? __builtin_amdgcn_exp2f(st[r] * c2 + add - lse[qt]) : 0.f;
+              ds[j][r] = valid ? p * (dp[r] * kp[r] - delta[qt]) : 0.f;      // a fully blocked row has delta = NaN (its o is): it gets dq = 0
+            } else {
+              const float p = valid ? __builtin_amdgcn_exp2f(st[r] * c2 - lse[qt]) : 0.f;
+              ds[j][r] = p * (dp[r] * kp[r] - delta[qt]);
+            }
           }
         }
         T::mm_t(kt, ds[0], ds[1], dq[qt]);
@@ -404,11 +492,11 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_q_kernel(const void* __res
 
 // ---- backward, key-stationary: dk and dv -------------------------------------------------------------------------------------------
 // KT 16-key tiles per wave in registers, NI 16-query tiles per LDS tile.  grid = (ceil(L / (64 KT)) * nseq, n_head)
-template <bool F32, int KT, int NI>
+template <bool F32, int KT, int NI, bool MASKED>
 __global__ __launch_bounds__(256) void attn_flash_bwd_kv_kernel(const void* __restrict__ qkv_, const void* __restrict__ do_,
                                                                 const float* __restrict__ stats, void* __restrict__ dqkv_, int C, int n_head,
                                                                 TanteSeq sq, int nkb, int causal, float scale, float c2, float p_drop,
-                                                                unsigned long long seed) {
+                                                                unsigned long long seed, FaMask<MASKED> mk) {
   typedef Fa<F32> T;
   typedef typename T::elem elem;
   constexpr int BQ = NI * 16, BKW = 64 * KT;
@@ -432,11 +520,13 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_kv_kernel(const void* __re
   bool klive[KT];
   long ktok[KT];
   f32x4 dk[KT][2], dv[KT][2];
+  float kadd[KT];      // masked: the key's key_padding_mask * log2(e); a key it blocks is not live
 #pragma unroll
   for (int kt = 0; kt < KT; ++kt) {
     kpos[kt] = kw0 + kt * 16 + l15;
     klive[kt] = kpos[kt] < L;
-    ktok[kt] = klive[kt] ? fa_token(sq, s, kpos[kt]) : 0;
+    kadd[kt] = 0.f;
+    ktok[kt] = klive[kt] ? fa_tok<MASKED>(sq, s, kpos[kt]) : 0;
     kf[kt] = vf[kt] = T::zero_frag();
     if (klive[kt]) {
       kf[kt] = T::from_global(qkv + ktok[kt] * 3L * C + C + h * FA_D, kk);
@@ -444,16 +534,34 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_kv_kernel(const void* __re
     }
     dk[kt][0] = dk[kt][1] = dv[kt][0] = dv[kt][1] = zero4;
   }
+  bool kopen[KT];      // masked: key_padding_mask leaves the key open
+  const float* amh = nullptr;      // masked: this (sequence, head)'s attn_mask
+  if constexpr (MASKED) {
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) kopen[kt] = true;
+    if (mk.am) amh = mk.am + ((long)s * n_head + h) * mk.bstride;
+    if (mk.kpm) {
+#pragma unroll
+      for (int kt = 0; kt < KT; ++kt) {
+        const float v = mk.kpm[(long)s * L + min(kpos[kt], L - 1)] * FA_LOG2E;
+        kopen[kt] = v != -INFINITY;
+        kadd[kt] = kopen[kt] ? v : 0.f;
+      }
+    }
+  }
   const int i_start = causal ? (kb * BKW / BQ) * BQ : 0;      // workgroup-uniform: queries before the first key see none of these keys
   const int srow = tid >> 2, sc4 = tid & 3;
   for (int i0 = i_start; i0 < L; i0 += BQ) {
     __syncthreads();
     if (srow < BQ) {
       const int qi = i0 + srow;
-      const long tok = qi < L ? fa_token(sq, s, qi) : 0;
-      T::stage(Qs, srow, sc4, qi < L ? qkv + tok * 3L * C + h * FA_D : nullptr);
-      T::stage(Gs, srow, sc4, qi < L ? dO + tok * (long)C + h * FA_D : nullptr);
-      if (sc4 < 2) sst[sc4 * BQ + srow] = qi < L ? stats[(((long)s * n_head + h) * L + qi) * 2 + sc4] : 0.f;
+      const long tok = qi < L ? fa_tok<MASKED>(sq, s, qi) : 0;
+      bool qrow = qi < L;
+      // masked: a query with every key blocked (lse2 = -inf; its o and delta are NaN) is staged as zeros, so it adds nothing to dk and dv
+      if constexpr (MASKED) qrow = qrow && stats[(((long)s * n_head + h) * L + qi) * 2] != -INFINITY;
+      T::stage(Qs, srow, sc4, qrow ? qkv + tok * 3L * C + h * FA_D : nullptr);
+      T::stage(Gs, srow, sc4, qrow ? dO + tok * (long)C + h * FA_D : nullptr);
+      if (sc4 < 2) sst[sc4 * BQ + srow] = qrow ? stats[(((long)s * n_head + h) * L + qi) * 2 + sc4] : 0.f;
     }
     __syncthreads();
     if (causal && i0 + BQ - 1 < kw0) continue;      // wave-uniform: every query of the tile precedes the wave's keys
@@ -480,8 +588,18 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_kv_kernel(const void* __re
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int qi = i0 + ip * 32 + j * 16 + 4 * kk + r;
-            const bool valid = klive[kt] && qi < L && (!causal || kpos[kt] <= qi);
-            const float p = valid ? __builtin_amdgcn_exp2f(st[r] * c2 - lse4[j][r]) : 0.f;
+            bool valid = klive[kt] && qi < L && (!causal || kpos[kt] <= qi);
+            float add = 0.f;
+            if constexpr (MASKED) {
+              valid = valid && kopen[kt];
+              if (amh) {      // four consecutive queries of one key column: a strided read, clamped into the mask
+                const float a = amh[(long)min(qi, L - 1) * L + min(kpos[kt], L - 1)];
+                valid = valid && a != -INFINITY;
+                add = a * FA_LOG2E;
+              }
+              add = valid ? add + kadd[kt] : 0.f;
+            }
+            const float p = valid ? __builtin_amdgcn_exp2f(MASKED ? st[r] * c2 + add - lse4[j][r] : st[r] * c2 - lse4[j][r]) : 0.f;
             float keep = 1.0f;
             if (p_drop > 0.f) keep = dropout_keep(seed, (mhead + (unsigned long long)qi) * L + (unsigned long long)kpos[kt], p_drop) ? ksc : 0.f;
             pd[j][r] = p * keep;
@@ -520,6 +638,65 @@ int flash_check(const char* who, int dtype, int C, int n_head, const TanteSeq* s
   return 0;
 }
 
+
+// the launches behind both pairs of entry points; `who` names the entry point in every message
+template <bool MASKED>
+int flash_fwd(const char* who, const void* qkv, void* o, float* stats, int dtype, int C, int n_head, const TanteSeq* seq, int causal, float p_drop,
+              uint64_t seed, FaMask<MASKED> mk, void* stream) {
+  if (!qkv || !o) TANTE_FAIL(-1, "%s: null pointer", who);
+  if (int rc = flash_check(who, dtype, C, n_head, seq, p_drop)) return rc;
+  if (((uintptr_t)qkv % 16) || ((uintptr_t)o % 16) || ((uintptr_t)stats % 8)) TANTE_FAIL(-1, "%s: qkv and o must be 16-byte aligned, stats 8-byte aligned", who);
+  const int nqb = (seq->L + FA_BQ - 1) / FA_BQ;
+  const dim3 grid((unsigned)(nqb * seq->nseq), (unsigned)n_head);
+  const float c2 = 1.4426950408889634f / sqrtf((float)FA_D);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == TANTE_BF16)
+    hipLaunchKernelGGL((attn_flash_fwd_kernel<false, MASKED>), grid, dim3(256), 0, s, qkv, o, stats, C, n_head, *seq, nqb, causal, c2, p_drop,
+                       (unsigned long long)seed, mk);
+  else
+    hipLaunchKernelGGL((attn_flash_fwd_kernel<true, MASKED>), grid, dim3(256), 0, s, qkv, o, stats, C, n_head, *seq, nqb, causal, c2, p_drop,
+                       (unsigned long long)seed, mk);
+  TANTE_CHECK_LAUNCH();
+  return 0;
+}
+
+template <bool MASKED>
+int flash_bwd(const char* who, const void* qkv, const void* o, const void* dO, float* stats, void* dqkv, int dtype, int C, int n_head,
+              const TanteSeq* seq, int causal, float p_drop, uint64_t seed, FaMask<MASKED> mk, void* stream) {
+  if (!qkv || !o || !dO || !stats || !dqkv) TANTE_FAIL(-1, "%s: null pointer", who);
+  if (int rc = flash_check(who, dtype, C, n_head, seq, p_drop)) return rc;
+  if (((uintptr_t)qkv % 16) || ((uintptr_t)o % 16) || ((uintptr_t)dO % 16) || ((uintptr_t)dqkv % 16) || ((uintptr_t)stats % 8))
+    TANTE_FAIL(-1, "%s: qkv, o, dO and dqkv must be 16-byte aligned, stats 8-byte aligned", who);
+  const int nqb = (seq->L + FA_BQ - 1) / FA_BQ;
+  const float scale = 1.0f / sqrtf((float)FA_D), c2 = 1.4426950408889634f * scale;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 gq((unsigned)(nqb * seq->nseq), (unsigned)n_head);
+  if (dtype == TANTE_BF16) {
+    const int nkb = (seq->L + 127) / 128;
+    hipLaunchKernelGGL((attn_flash_bwd_q_kernel<false, MASKED>), gq, dim3(256), 0, s, qkv, o, dO, stats, dqkv, C, n_head, *seq, nqb, causal, scale, c2,
+                       p_drop, (unsigned long long)seed, mk);
+    hipLaunchKernelGGL((attn_flash_bwd_kv_kernel<false, 2, 4, MASKED>), dim3((unsigned)(nkb * seq->nseq), (unsigned)n_head), dim3(256), 0, s, qkv, dO,
+                       (const float*)stats, dqkv, C, n_head, *seq, nkb, causal, scale, c2, p_drop, (unsigned long long)seed, mk);
+  } else {
+    const int nkb = (seq->L + 63) / 64;
+    hipLaunchKernelGGL((attn_flash_bwd_q_kernel<true, MASKED>), gq, dim3(256), 0, s, qkv, o, dO, stats, dqkv, C, n_head, *seq, nqb, causal, scale, c2,
+                       p_drop, (unsigned long long)seed, mk);
+    hipLaunchKernelGGL((attn_flash_bwd_kv_kernel<true, 1, 2, MASKED>), dim3((unsigned)(nkb * seq->nseq), (unsigned)n_head), dim3(256), 0, s, qkv, dO,
+                       (const float*)stats, dqkv, C, n_head, *seq, nkb, causal, scale, c2, p_drop, (unsigned long long)seed, mk);
+  }
+  TANTE_CHECK_LAUNCH();
+  return 0;
+}
+
+// the dense descriptor (token = b L + l) and the mask arguments of the masked entry points
+int flash_masked_args(const char* who, int Bp, int L, const float* attn_mask, int64_t mask_bstride, const float* key_padding_mask, TanteSeq* seq) {
+  if (Bp <= 0 || L <= 0) TANTE_FAIL(-1, "%s: bad shape", who);
+  if (attn_mask && mask_bstride != 0 && mask_bstride != (int64_t)L * L) TANTE_FAIL(-1, "%s: mask stride must be 0 (shared) or L * L", who);
+  if (((uintptr_t)attn_mask % 16) || ((uintptr_t)key_padding_mask % 4)) TANTE_FAIL(-1, "%s: attn_mask must be 16-byte aligned, key_padding_mask 4-byte aligned", who);
+  *seq = TanteSeq{Bp, L, 1, (int64_t)L, 0, L, 0, 1};
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int64_t tante_attention_flash_stats_floats(int n_head, const TanteSeq* seq) {
@@ -531,46 +708,34 @@ extern "C" int tante_attention_flash_supported(int dtype, int C, int n_head, int
 
 extern "C" int tante_attention_flash(const void* qkv, void* o, float* stats, int dtype, int C, int n_head, const TanteSeq* seq, int causal,
                                      float p_drop, uint64_t seed, void* stream) {
-  if (!qkv || !o) TANTE_FAIL(-1, "tante_attention_flash: null pointer");
-  if (int rc = flash_check("tante_attention_flash", dtype, C, n_head, seq, p_drop)) return rc;
-  if (((uintptr_t)qkv % 16) || ((uintptr_t)o % 16) || ((uintptr_t)stats % 8)) TANTE_FAIL(-1, "tante_attention_flash: qkv and o must be 16-byte aligned, stats 8-byte aligned");
-  const int nqb = (seq->L + FA_BQ - 1) / FA_BQ;
-  const dim3 grid((unsigned)(nqb * seq->nseq), (unsigned)n_head);
-  const float c2 = 1.4426950408889634f / sqrtf((float)FA_D);
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == TANTE_BF16)
-    hipLaunchKernelGGL(attn_flash_fwd_kernel<false>, grid, dim3(256), 0, s, qkv, o, stats, C, n_head, *seq, nqb, causal, c2, p_drop,
-                       (unsigned long long)seed);
-  else
-    hipLaunchKernelGGL(attn_flash_fwd_kernel<true>, grid, dim3(256), 0, s, qkv, o, stats, C, n_head, *seq, nqb, causal, c2, p_drop,
-                       (unsigned long long)seed);
-  TANTE_CHECK_LAUNCH();
-  return 0;
+  return flash_fwd<false>("tante_attention_flash", qkv, o, stats, dtype, C, n_head, seq, causal, p_drop, seed, FaMask<false>{}, stream);
 }
 
 extern "C" int tante_attention_flash_bwd(const void* qkv, const void* o, const void* dO, float* stats, void* dqkv, int dtype, int C, int n_head,
                                          const TanteSeq* seq, int causal, float p_drop, uint64_t seed, void* stream) {
-  if (!qkv || !o || !dO || !stats || !dqkv) TANTE_FAIL(-1, "tante_attention_flash_bwd: null pointer");
-  if (int rc = flash_check("tante_attention_flash_bwd", dtype, C, n_head, seq, p_drop)) return rc;
-  if (((uintptr_t)qkv % 16) || ((uintptr_t)o % 16) || ((uintptr_t)dO % 16) || ((uintptr_t)dqkv % 16) || ((uintptr_t)stats % 8))
-    TANTE_FAIL(-1, "tante_attention_flash_bwd: qkv, o, dO and dqkv must be 16-byte aligned, stats 8-byte aligned");
-  const int nqb = (seq->L + FA_BQ - 1) / FA_BQ;
-  const float scale = 1.0f / sqrtf((float)FA_D), c2 = 1.4426950408889634f * scale;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 gq((unsigned)(nqb * seq->nseq), (unsigned)n_head);
-  if (dtype == TANTE_BF16) {
-    const int nkb = (seq->L + 127) / 128;
-    hipLaunchKernelGGL(attn_flash_bwd_q_kernel<false>, gq, dim3(256), 0, s, qkv, o, dO, stats, dqkv, C, n_head, *seq, nqb, causal, scale, c2, p_drop,
-                       (unsigned long long)seed);
-    hipLaunchKernelGGL((attn_flash_bwd_kv_kernel<false, 2, 4>), dim3((unsigned)(nkb * seq->nseq), (unsigned)n_head), dim3(256), 0, s, qkv, dO,
-                       (const float*)stats, dqkv, C, n_head, *seq, nkb, causal, scale, c2, p_drop, (unsigned long long)seed);
-  } else {
-    const int nkb = (seq->L + 63) / 64;
-    hipLaunchKernelGGL(attn_flash_bwd_q_kernel<true>, gq, dim3(256), 0, s, qkv, o, dO, stats, dqkv, C, n_head, *seq, nqb, causal, scale, c2, p_drop,
-                       (unsigned long long)seed);
-    hipLaunchKernelGGL((attn_flash_bwd_kv_kernel<true, 1, 2>), dim3((unsigned)(nkb * seq->nseq), (unsigned)n_head), dim3(256), 0, s, qkv, dO,
-                       (const float*)stats, dqkv, C, n_head, *seq, nkb, causal, scale, c2, p_drop, (unsigned long long)seed);
-  }
-  TANTE_CHECK_LAUNCH();
-  return 0;
+  return flash_bwd<false>("tante_attention_flash_bwd", qkv, o, dO, stats, dqkv, dtype, C, n_head, seq, causal, p_drop, seed, FaMask<false>{}, stream);
+}
+
+// With both masks NULL these ARE the unmasked kernels on the dense descriptor (the same bits); a mask selects the masked instantiations.
+extern "C" int tante_attention_flash_masked(const void* qkv, void* o, float* stats, int dtype, int C, int n_head, int Bp, int L, int causal,
+                                            const float* attn_mask, int64_t mask_bstride, const float* key_padding_mask, float p_drop, uint64_t seed,
+                                            void* stream) {
+  const char* who = "tante_attention_flash_masked";
+  TanteSeq seq;
+  if (int rc = flash_masked_args(who, Bp, L, attn_mask, mask_bstride, key_padding_mask, &seq)) return rc;
+  if (!attn_mask && !key_padding_mask) return flash_fwd<false>(who, qkv, o, stats, dtype, C, n_head, &seq, causal, p_drop, seed, FaMask<false>{}, stream);
+  return flash_fwd<true>(who, qkv, o, stats, dtype, C, n_head, &seq, causal, p_drop, seed, FaMask<true>{attn_mask, (long)mask_bstride, key_padding_mask},
+                         stream);
+}
+
+extern "C" int tante_attention_flash_masked_bwd(const void* qkv, const void* o, const void* dO, float* stats, void* dqkv, int dtype, int C, int n_head,
+                                                int Bp, int L, int causal, const float* attn_mask, int64_t mask_bstride,
+                                                const float* key_padding_mask, float p_drop, uint64_t seed, void* stream) {
+  const char* who = "tante_attention_flash_masked_bwd";
+  TanteSeq seq;
+  if (int rc = flash_masked_args(who, Bp, L, attn_mask, mask_bstride, key_padding_mask, &seq)) return rc;
+  if (!attn_mask && !key_padding_mask)
+    return flash_bwd<false>(who, qkv, o, dO, stats, dqkv, dtype, C, n_head, &seq, causal, p_drop, seed, FaMask<false>{}, stream);
+  return flash_bwd<true>(who, qkv, o, dO, stats, dqkv, dtype, C, n_head, &seq, causal, p_drop, seed,
+                         FaMask<true>{attn_mask, (long)mask_bstride, key_padding_mask}, stream);
 }

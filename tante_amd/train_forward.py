@@ -16,8 +16,9 @@ import torch
 from . import _lib as L
 from . import options as _O
 from . import kernels as K
+from . import attn_flash as FA
 from . import stages as S
-from .autograd import (EncTailFn, TailCfg, TailFn, FilmTableFn, ActFn, AttentionFn, BlockFn, BlockTailFn, block_tail_ready, AxisHWFn, AxisMlpFn, BranchOutFn, DeconvFn, DropoutAddFn, FilmPosFn, FilmPosFramesFn, FoldFn, LayerNormFn, LayerNormSkipFn, LinearFn, MaskedAttentionFn,
+from .autograd import (EncTailFn, TailCfg, TailFn, FilmTableFn, ActFn, AttentionFn, BlockFn, BlockTailFn, block_tail_ready, AxisHWFn, AxisMlpFn, BranchOutFn, DeconvFn, DropoutAddFn, FilmPosFn, FilmPosFramesFn, FoldFn, LayerNormFn, LayerNormSkipFn, LinearFn, MaskedAttentionFn, MaskedFlashAttentionFn,
                        PatchEmbedFn, RtReduceFn, TaylorFn, _grad_slot, next_seed)
 
 
@@ -242,7 +243,11 @@ def _block_chain(blk, plan: BlockPlan, x, seq, causal: bool, p: float, compute: 
     xh, xs = LayerNormSkipFn.apply(x, blk.ln1.eps, adt, (t["xh1"], t["st1"]) if f else None)      # xs: x as the skip operand, whose gradient LN's backward adds
     qkv = LinearFn.apply(xh, w_in, b_in, None, compute, adt, t["qkv"] if f else None)
     if masks is not None:
-        o = MaskedAttentionFn.apply(qkv, blk.embed_dim, blk.n_head, seq.nseq, seq.L, causal, masks[0], masks[1])
+        ok = FA.supported(L.BF16 if adt == torch.bfloat16 else L.F32, blk.embed_dim, blk.n_head, seq.L)
+        if FA.masked_route(seq.L, p, ok, FA.ATTN_FLASH) == FA.MASKED_FLASH:      # off by default: p = 0 here (block_train refuses p > 0)
+            o = MaskedFlashAttentionFn.apply(qkv, blk.embed_dim, blk.n_head, seq.nseq, seq.L, causal, masks[0], masks[1], p)
+        else:
+            o = MaskedAttentionFn.apply(qkv, blk.embed_dim, blk.n_head, seq.nseq, seq.L, causal, masks[0], masks[1])
     else:
         o = AttentionFn.apply(qkv, seq, blk.embed_dim, blk.n_head, causal, p, (t["o"], seeds[0]) if f else None)
     if f and plan.fused_tail:      # the rest as ONE autograd node whose backward is ONE launch (tante_block_tail_bwd)

@@ -1,17 +1,22 @@
 """A/B timing of the flash attention kernels (csrc/attn_flash.hip) against the kernels that take the same calls by default.
 
-Four pairs, at cfg2's geometry (B = 8, T = 4, 32 x 32 patches, C = 256, 8 heads of dim 32, bf16, random operands):
+Six pairs; the first four at cfg2's geometry (B = 8, T = 4, 32 x 32 patches, C = 256, 8 heads of dim 32, bf16, random operands):
   fwd_L   tante_attention (attn_long_kernel)        vs tante_attention_flash       letter 'L': 32 sequences of 1024
   fwd_A   the same                                  vs the same                    letter 'A': 8 sequences of 4096
   bwd_L   tante_attention_masked_bwd (lane per row) vs tante_attention_flash_bwd   dense 'L' shape, p = 0; o and the row statistics given
   bwd_L_routed   the same old kernel                vs flash forward into scratch + flash backward: what AttentionFn.backward runs on the
                  route TANTE_ATTN_FLASH=1 enables (the p = 0 forward saved no statistics, so the backward recomputes them)
+and the masked pair, on the dense 'L' shape (32 sequences of 1024) under a shared boolean (L, L) attn_mask (30 % blocked, the diagonal
+open) and a (Bp, L) key_padding_mask (the last 37 keys of every odd sample), p = 0:
+  fwd_L_masked   tante_attention_masked (lane per row)     vs tante_attention_flash_masked
+  bwd_L_masked   tante_attention_masked_bwd (lane per row) vs tante_attention_flash_masked_bwd   o and the row statistics given
+(FLOP/s of the masked pair count the full L^2 products, blocked keys included: both sides compute them.)
 One process, old and new alternating behind a warm-up; every region is timed with device events and holds enough calls for >= 0.2 s;
 the figure of a kernel is the median of its regions (>= 7), its spread is (max - min) / median over those regions.  The new kernel counts
 as faster when the gap between the medians exceeds the larger of the two spreads.  FLOP/s = 4 L^2 d per (sequence, head) for a forward
 (x 2.5 for a backward: five products against two) over the time of one call.
 
-  python tools/attn_flash_ab.py [--regions 7] [--seconds 0.2] [--out FILE.json] [--once]
+  python tools/attn_flash_ab.py [--regions 7] [--seconds 0.2] [--out FILE.json] [--once] [--pairs fwd_L_masked,bwd_L_masked]
 --once: one call of each kernel and nothing else (the program to put behind `rocprofv3 --kernel-trace --stats --`).
 """
 import argparse
@@ -61,6 +66,29 @@ def cases(dev):
                 FA.forward(qkv, o2, st, CH, NH, seq, False)
                 FA.backward(qkv, o2, do, st, dqkv, CH, NH, seq, False)
             out.append(("bwd_L_routed", seq, flops, old, routed))
+    # the masked pair: what MaskedAttentionFn runs by default against what MaskedFlashAttentionFn runs
+    seq = K.dense_seq(32, 1024)
+    n = seq.nseq * seq.L
+    am = torch.zeros(1, seq.L, seq.L).masked_fill_(((torch.rand(seq.L, seq.L, generator=g) < 0.3) & ~torch.eye(seq.L, dtype=torch.bool))[None],
+                                                   float("-inf")).to(dev)
+    kp = torch.zeros(seq.nseq, seq.L)
+    kp[1::2, seq.L - 37:] = float("-inf")
+    kp = kp.to(dev)
+    qkv = torch.randn(n, 3 * CH, generator=g).to(torch.bfloat16).to(dev)
+    do = torch.randn(n, CH, generator=g).to(torch.bfloat16).to(dev)
+    o, dqkv = torch.empty(n, CH, dtype=torch.bfloat16, device=dev), torch.empty_like(qkv)
+    st_old = torch.empty(n * NH * 3, dtype=torch.float32, device=dev)
+    st_new = FA.new_stats(qkv, NH, seq)
+    FA.forward(qkv, o, st_new, CH, NH, seq, False, 0.0, 0, am, kp)
+    s = torch.cuda.current_stream().cuda_stream
+    flops = 4.0 * seq.L * seq.L * D * seq.nseq * NH
+
+    def old_bwd():
+        L.check(L.lib().tante_attention_masked_bwd(qkv.data_ptr(), do.data_ptr(), dqkv.data_ptr(), L.BF16, CH, NH, seq.nseq, seq.L, 0, am.data_ptr(), 0,
+                                                   kp.data_ptr(), st_old.data_ptr(), s), "masked_bwd")
+    out.append(("fwd_L_masked", seq, flops, lambda: K.attention_masked(qkv, o, CH, NH, seq.nseq, seq.L, False, am, kp),
+                lambda: FA.forward(qkv, o, None, CH, NH, seq, False, 0.0, 0, am, kp)))
+    out.append(("bwd_L_masked", seq, flops * 2.5, old_bwd, lambda: FA.backward(qkv, o, do, st_new, dqkv, CH, NH, seq, False, 0.0, 0, am, kp)))
     return out
 
 
@@ -80,10 +108,13 @@ def main():
     ap.add_argument("--seconds", type=float, default=0.2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--pairs", default=None, help="comma-separated pair names (default: all)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     rows = []
     for name, seq, flops, old, new in cases(dev):
+        if a.pairs and name not in a.pairs.split(","):
+            continue
         if a.once:
             old()
             new()
