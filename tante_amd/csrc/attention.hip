@@ -228,11 +228,6 @@ int launch_attn(const void* qkv, void* o, int dtype, int C, int n_head, const Ta
 // tiles or the 16 / L sequences of one tile behind a block-diagonal mask.  S^T = K Q^T puts a query in each lane's column, so the row
 // statistics are two cross-group shuffles; the (dropped) probabilities of two key tiles pack straight into the B operand of
 // O^T = V^T P^T, whose A operand is two transposing LDS reads of the row-major V image.
-__device__ __forceinline__ u32x2 afm_tr(unsigned addr) {
-  u32x2 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-  return r;
-}
 template <int NT>
 __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(const unsigned short* __restrict__ qkv, unsigned short* __restrict__ o, int C, int n_head,
                                                             TanteSeq sq, int SPT, int causal, float scale, float p_drop, unsigned long long seed) {
@@ -272,7 +267,7 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(const unsigned short
     }
     *(u32x4*)(Vs + (t * 16 + l15) * RS + kk * 8) = vf;   // row-major image (64-byte rows) for the transposing reads
   }
-  const unsigned troff = lds_addr((const char*)Vs) + (4 * kk + qq) * (RS * 2) + pp * 8;
+  const char* vt = (const char*)Vs + (4 * kk + qq) * (RS * 2) + pp * 8;   // transposing reads: lane 4 qq + pp of a group supplies row 4 kk + qq, columns 4 pp ..
   const float c2 = scale * 1.4426950408889634f;
   const float ksc = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
   const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -337,9 +332,7 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(const unsigned short
       const u32x4 pf = pack8(st[j0], (2 * jp + 1 < NT) ? st[j1] : zero4);   // un-normalised: 1 / l scales the 8 outputs instead
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
-        u32x2 lo = afm_tr(troff + dt * 32 + j0 * (16 * RS * 2)), hi = afm_tr(troff + dt * 32 + j1 * (16 * RS * 2));
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo), "+v"(hi) : : "memory");
-        oa[dt] = mfma_bf16(u32x4{lo[0], lo[1], hi[0], hi[1]}, pf, oa[dt]);
+        oa[dt] = mfma_bf16(lds_tr16_frag(vt + dt * 32 + j0 * (16 * RS * 2), vt + dt * 32 + j1 * (16 * RS * 2)), pf, oa[dt]);
       }
     }
     if (ilive) {

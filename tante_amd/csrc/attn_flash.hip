@@ -64,16 +64,6 @@ __device__ __forceinline__ long fa_tok(const TanteSeq& q, int s, int l) {
   else return fa_token(q, s, l);
 }
 
-// two transposing reads + their wait in one statement (the result cannot be consumed before the wait)
-__device__ __forceinline__ u32x4 fa_tr2(unsigned a0, unsigned a1) {
-  u32x2 lo, hi;
-  asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %3\n\ts_waitcnt lgkmcnt(0)"
-               : "=&v"(lo), "=&v"(hi)
-               : "v"(a0), "v"(a1)
-               : "memory");
-  return u32x4{lo[0], lo[1], hi[0], hi[1]};
-}
-
 // ---- operand fragments, per dtype ------------------------------------------------------------------------------------------------
 // Frag:  one 16-row tile x 32 dims as an MFMA A or B operand (row = lane & 15).  TFrag: 32 rows x 32 dims, transposed (output row = dim).
 template <bool F32>
@@ -99,10 +89,10 @@ struct Fa<false> {      // bf16
   static __device__ __forceinline__ f32x4 mm(const Frag& a, const Frag& b, const f32x4& c) { return mfma_bf16(a.a, b.a, c); }
   // rows row0 .. row0 + 15 and row1 .. row1 + 15 of the image: k-step element j < 4 is row0 + 4 kk + j, j >= 4 is row1 + 4 kk + j - 4
   static __device__ __forceinline__ TFrag t_from_lds(const elem* img, int row0, int row1, int l15, int kk) {
-    const unsigned base = lds_addr((const char*)img) + (4 * kk + (l15 >> 2)) * (RS * 2) + (l15 & 3) * 8;
+    const char* base = (const char*)img + (4 * kk + (l15 >> 2)) * (RS * 2) + (l15 & 3) * 8;
     TFrag t;
-    t.a[0] = fa_tr2(base + row0 * (RS * 2), base + row1 * (RS * 2));
-    t.a[1] = fa_tr2(base + row0 * (RS * 2) + 32, base + row1 * (RS * 2) + 32);
+    t.a[0] = lds_tr16_frag(base + row0 * (RS * 2), base + row1 * (RS * 2));
+    t.a[1] = lds_tr16_frag(base + row0 * (RS * 2) + 32, base + row1 * (RS * 2) + 32);
     return t;
   }
   static __device__ __forceinline__ void mm_t(const TFrag& t, const f32x4& p0, const f32x4& p1, f32x4 (&acc)[2]) {

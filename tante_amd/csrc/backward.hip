@@ -619,11 +619,6 @@ __global__ __launch_bounds__(128) void attn_bwd_small_kernel(const void* __restr
 // straight into the B operand of the second product with k order (tile a: 4 kk + r, tile b: 4 kk + r); the matching A operand - K^T, Q^T
 // or dO^T in that k order - is two ds_read_b64_tr_b16 of the row-major LDS image (MI355X_MICROARCH.md "LDS": 4 rows x 16 columns per
 // 16-lane group, column-major out).  The VALU kernel above spends ~260 FMAs per (query, key) pair; this one ~30 instructions.
-__device__ __forceinline__ u32x2 abm_tr(unsigned addr) {
-  u32x2 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-  return r;
-}
 template <int NT>
 __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(const unsigned short* __restrict__ qkv, const unsigned short* __restrict__ dO,
                                                             unsigned short* __restrict__ dqkv, int C, int n_head, TanteSeq sq, int SPT, int causal,
@@ -701,12 +696,10 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(const unsigned short
     gf[t] = *(const u32x4*)(Gs + (t * 16 + l15) * RS + kk * 8);
   }
   // transposed fragment of X (row tile rt, 16-dim tile dt): lane 4 qq + pp of a 16-lane group supplies row 4 kk + qq, columns 4 pp .. 4 pp + 3
-  const unsigned troff = (4 * kk + qq) * (RS * 2) + pp * 8;
+  const int troff = (4 * kk + qq) * (RS * 2) + pp * 8;
   auto tfrag = [&](const unsigned short* X, int rt0, int rt1, int dt) {
-    const unsigned a = lds_addr((const char*)X) + troff + dt * 32;
-    u32x2 lo = abm_tr(a + rt0 * (16 * RS * 2)), hi = abm_tr(a + rt1 * (16 * RS * 2));
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo), "+v"(hi) : : "memory");
-    return u32x4{lo[0], lo[1], hi[0], hi[1]};
+    const char* a = (const char*)X + troff + dt * 32;
+    return lds_tr16_frag(a + rt0 * (16 * RS * 2), a + rt1 * (16 * RS * 2));
   };
   const float c2 = scale * 1.4426950408889634f;
   const float ksc = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
@@ -910,12 +903,10 @@ __global__ __launch_bounds__(64 * NT * HG) void attn_bwd_split_kernel(const unsi
   }
   __syncthreads();
   auto rfrag = [&](const unsigned short* X, int t) { return *(const u32x4*)(X + (t * 16 + l15) * RS + kk * 8); };   // row l15 of tile t, dims 8 kk ..
-  const unsigned troff = (4 * kk + qq) * (RS * 2) + pp * 8;
+  const int troff = (4 * kk + qq) * (RS * 2) + pp * 8;
   auto tfrag = [&](const unsigned short* X, int rt0, int rt1, int dt) {
-    const unsigned a = lds_addr((const char*)X) + troff + dt * 32;
-    u32x2 lo = abm_tr(a + rt0 * (16 * RS * 2)), hi = abm_tr(a + rt1 * (16 * RS * 2));
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo), "+v"(hi) : : "memory");
-    return u32x4{lo[0], lo[1], hi[0], hi[1]};
+    const char* a = (const char*)X + troff + dt * 32;
+    return lds_tr16_frag(a + rt0 * (16 * RS * 2), a + rt1 * (16 * RS * 2));
   };
   const float c2 = scale * 1.4426950408889634f;
   const float ksc = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;

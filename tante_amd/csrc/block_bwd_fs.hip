@@ -89,16 +89,6 @@ __device__ __forceinline__ u32x2 bf_pack4(const f32x4& v) {
   return u;
 }
 __device__ __forceinline__ f32x4 bf_unpack4(const u32x2& u) { return f32x4{bf16_lo(u[0]), bf16_hi(u[0]), bf16_lo(u[1]), bf16_hi(u[1])}; }
-__device__ __forceinline__ u32x2 bf_tr(unsigned addr) {      // 4 rows x 16 columns of a row-major bf16 tile, column-major out (one 16-lane group)
-  u32x2 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-  return r;
-}
-__device__ __forceinline__ u32x4 bf_lds128(unsigned addr) {
-  u32x4 r;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-  return r;
-}
 
 // In-kernel stamps (cdna_hip_programming.md 7): a -DTANTE_ABLATE build records the shader clock at the phase boundaries of every wave into a
 // buffer of its own (tools/bf_stamps.py reads the phase shares from it); in the product build the macro is empty.
@@ -602,35 +592,28 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
       nomask = (L == 16) && !A.causal;
     }
     const unsigned long long sd_attn = A.seed_attn ^ smix;
-    const unsigned aA = lds_addr(imgA), aB = lds_addr(imgB), aC = lds_addr(imgC);
     const int qq = l15 >> 2, pp = l15 & 3;
     // per-query statistics of pass 1 (max + log2 l, delta), read back in pass 2 as four consecutive queries per lane: the bias block of LDS
     // (dead since the v GEMM) holds [2][16 NTT] floats per wave
     float* const wst = lbias + wave * (2 * 16 * NTT);
     static_assert(2 * 16 * NTT * 4 * NW <= 3 * FS_C * 4, "row statistics fit the bias block");
-    // LDS reads are issued in groups and waited for ONCE per group (every read of this phase used to be followed by its own
-    // s_waitcnt lgkmcnt(0): ~70 exposed LDS round trips per head at L = 48, and ~100 ds_bpermute round trips for the statistics)
-    auto rd64 = [&](unsigned addr) {
-      u32x2 r;
-      asm volatile("ds_read_b64 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-      return r;
-    };
-    auto wait0 = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
-    auto tie2 = [&](u32x2& v) { asm volatile("" : "+v"(v)); };      // keeps every use of v behind the wait above it (asm volatile statements keep their order)
+    // LDS reads are issued in groups ahead of their uses (plain loads: the compiler counts them and places the waits): a read that is
+    // followed by its own s_waitcnt lgkmcnt(0) is an exposed LDS round trip, ~70 per head at L = 48
+    auto rd64 = [](const char* p) { return *(const __attribute__((address_space(3))) u32x2*)p; };
     static_for<HPW>([&](auto hh_c) {
       constexpr int hh = decltype(hh_c)::value;
       const int head = HPW * wave + hh;
       // "row = token l15, k = dims" fragment of (image, tile): the packed-accumulator k order -- lane (l15, kk) holds dims 4 kk .. 4 kk + 3 of
       // the head's first 16 and of its second 16 -- so that it contracts against vf: two 8-byte reads
-      const unsigned fo0 = (unsigned)(l15 * FS_ROW + (((2 * RT * wave + 4 * hh + (kk >> 1)) ^ l15) << 4) + (kk & 1) * 8);
-      const unsigned fo1 = (unsigned)(l15 * FS_ROW + (((2 * RT * wave + 4 * hh + 2 + (kk >> 1)) ^ l15) << 4) + (kk & 1) * 8);
+      const int fo0 = l15 * FS_ROW + (((2 * RT * wave + 4 * hh + (kk >> 1)) ^ l15) << 4) + (kk & 1) * 8;
+      const int fo1 = l15 * FS_ROW + (((2 * RT * wave + 4 * hh + 2 + (kk >> 1)) ^ l15) << 4) + (kk & 1) * 8;
       // transposed fragment (rows = dims 16 dt .. + 15 of the head, k = tokens of tiles t0 | t1 in packed-pair order): lane 4 qq + pp of
       // 16-lane group kk supplies row 4 kk + qq, columns 4 pp .. 4 pp + 3 of the 16 x 16 block
-      unsigned to[2];
+      int to[2];
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
         const int row = 4 * kk + qq, chunk = 2 * RT * wave + 4 * hh + 2 * dt + (pp >> 1);
-        to[dt] = (unsigned)(row * FS_ROW + ((chunk ^ row) << 4) + (pp & 1) * 8);
+        to[dt] = row * FS_ROW + ((chunk ^ row) << 4) + (pp & 1) * 8;
       }
       // dropout mask rows: index = ((((seq0 + si) 8 + head) L + pi) L + key position  (block_sliced.hip); hb = the part that fits 32 bits
       const unsigned hb = (unsigned)(seq0 * 8 + head);
@@ -639,17 +622,13 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
       // ---- pass 1: queries in the columns ---------------------------------------------------------------------------------------------
       static_for<NTT>([&](auto qt_c) {
         constexpr int qt = decltype(qt_c)::value, k0 = (qt / TPS) * TPS, NP = (NK + 1) / 2;
-        u32x2 q0 = rd64(aA + fo0 + qt * 8192u), q1 = rd64(aA + fo1 + qt * 8192u), g0 = rd64(aB + fo0 + qt * 8192u), g1 = rd64(aB + fo1 + qt * 8192u);
+        u32x2 q0 = rd64(imgA + fo0 + qt * 8192), q1 = rd64(imgA + fo1 + qt * 8192), g0 = rd64(imgB + fo0 + qt * 8192), g1 = rd64(imgB + fo1 + qt * 8192);
         u32x2 k0r[NK], k1r[NK];
 #pragma unroll
         for (int j = 0; j < NK; ++j) {
-          k0r[j] = rd64(aC + fo0 + (k0 + j) * 8192u);
-          k1r[j] = rd64(aC + fo1 + (k0 + j) * 8192u);
+          k0r[j] = rd64(imgC + fo0 + (k0 + j) * 8192);
+          k1r[j] = rd64(imgC + fo1 + (k0 + j) * 8192);
         }
-        wait0();
-        tie2(q0); tie2(q1); tie2(g0); tie2(g1);
-#pragma unroll
-        for (int j = 0; j < NK; ++j) { tie2(k0r[j]); tie2(k1r[j]); }
         const u32x4 qfq = u32x4{q0[0], q0[1], q1[0], q1[1]}, gfq = u32x4{g0[0], g0[1], g1[0], g1[1]};
         f32x4 st[NK], dpt[NK];
 #pragma unroll
@@ -717,17 +696,12 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
         f32x4 dq[2] = {zero4, zero4};
         static_for<NP>([&](auto g_c) {      // K^T fragments pair by pair (every pair's fragments alive at once does not fit the register file)
           constexpr int g = decltype(g_c)::value, ja = 2 * g, jb = ja + 1;
-          u32x2 ktl[2], kth[2];
+          u32x4 kt[2];
 #pragma unroll
-          for (int dt = 0; dt < 2; ++dt) {
-            ktl[dt] = bf_tr(aC + to[dt] + (unsigned)(k0 + ja) * 8192u);
-            kth[dt] = bf_tr(aC + to[dt] + (unsigned)(k0 + (jb < NK ? jb : ja)) * 8192u);
-          }
+          for (int dt = 0; dt < 2; ++dt) kt[dt] = lds_tr16_frag(imgC + to[dt] + (k0 + ja) * 8192, imgC + to[dt] + (k0 + (jb < NK ? jb : ja)) * 8192);
           const u32x4 pf = pack8(dpt[ja], jb < NK ? dpt[jb < NK ? jb : ja] : zero4);
-          wait0();
-          tie2(ktl[0]); tie2(ktl[1]); tie2(kth[0]); tie2(kth[1]);
 #pragma unroll
-          for (int dt = 0; dt < 2; ++dt) dq[dt] = mfma_bf16(u32x4{ktl[dt][0], ktl[dt][1], kth[dt][0], kth[dt][1]}, pf, dq[dt]);
+          for (int dt = 0; dt < 2; ++dt) dq[dt] = mfma_bf16(kt[dt], pf, dq[dt]);
         });
         dqp[qt][0] = bf_pack4(dq[0]);
         dqp[qt][1] = bf_pack4(dq[1]);
@@ -737,17 +711,13 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
       u32x2 dkp[NTT][2], dvp[NTT][2];
       static_for<NTT>([&](auto jt_c) {
         constexpr int jt = decltype(jt_c)::value, k0 = (jt / TPS) * TPS, NP = (NK + 1) / 2;
-        u32x2 kj0 = rd64(aC + fo0 + jt * 8192u), kj1 = rd64(aC + fo1 + jt * 8192u);
+        u32x2 kj0 = rd64(imgC + fo0 + jt * 8192), kj1 = rd64(imgC + fo1 + jt * 8192);
         u32x2 q0r[NK], q1r[NK], g0r[NK], g1r[NK];
 #pragma unroll
         for (int i = 0; i < NK; ++i) {
-          q0r[i] = rd64(aA + fo0 + (k0 + i) * 8192u); q1r[i] = rd64(aA + fo1 + (k0 + i) * 8192u);
-          g0r[i] = rd64(aB + fo0 + (k0 + i) * 8192u); g1r[i] = rd64(aB + fo1 + (k0 + i) * 8192u);
+          q0r[i] = rd64(imgA + fo0 + (k0 + i) * 8192); q1r[i] = rd64(imgA + fo1 + (k0 + i) * 8192);
+          g0r[i] = rd64(imgB + fo0 + (k0 + i) * 8192); g1r[i] = rd64(imgB + fo1 + (k0 + i) * 8192);
         }
-        wait0();
-        tie2(kj0); tie2(kj1);
-#pragma unroll
-        for (int i = 0; i < NK; ++i) { tie2(q0r[i]); tie2(q1r[i]); tie2(g0r[i]); tie2(g1r[i]); }
         const u32x4 kfj = u32x4{kj0[0], kj0[1], kj1[0], kj1[1]};
         f32x4 sv[NK], dp[NK];
 #pragma unroll
@@ -780,22 +750,19 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
         f32x4 dk[2] = {zero4, zero4}, dv[2] = {zero4, zero4};
         static_for<NP>([&](auto g_c) {      // Q^T and dO^T fragments for dK, dV, pair by pair
           constexpr int g = decltype(g_c)::value, ia = 2 * g, ib = ia + 1;
-          u32x2 qtl[2], qth[2], gtl[2], gth[2];
+          u32x4 qtf[2], gtf[2];
 #pragma unroll
           for (int dt = 0; dt < 2; ++dt) {
-            const unsigned ta = to[dt] + (unsigned)(k0 + ia) * 8192u, tb = to[dt] + (unsigned)(k0 + (ib < NK ? ib : ia)) * 8192u;
-            qtl[dt] = bf_tr(aA + ta); qth[dt] = bf_tr(aA + tb);
-            gtl[dt] = bf_tr(aB + ta); gth[dt] = bf_tr(aB + tb);
+            const int ta = to[dt] + (k0 + ia) * 8192, tb = to[dt] + (k0 + (ib < NK ? ib : ia)) * 8192;
+            qtf[dt] = lds_tr16_frag(imgA + ta, imgA + tb);
+            gtf[dt] = lds_tr16_frag(imgB + ta, imgB + tb);
           }
           const u32x4 pfs = pack8(dp[ia], ib < NK ? dp[ib < NK ? ib : ia] : zero4);
           const u32x4 pfp = pack8(sv[ia], ib < NK ? sv[ib < NK ? ib : ia] : zero4);
-          wait0();
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) { tie2(qtl[dt]); tie2(qth[dt]); tie2(gtl[dt]); tie2(gth[dt]); }
 #pragma unroll
           for (int dt = 0; dt < 2; ++dt) {
-            dk[dt] = mfma_bf16(u32x4{qtl[dt][0], qtl[dt][1], qth[dt][0], qth[dt][1]}, pfs, dk[dt]);
-            dv[dt] = mfma_bf16(u32x4{gtl[dt][0], gtl[dt][1], gth[dt][0], gth[dt][1]}, pfp, dv[dt]);
+            dk[dt] = mfma_bf16(qtf[dt], pfs, dk[dt]);
+            dv[dt] = mfma_bf16(gtf[dt], pfp, dv[dt]);
           }
         });
         dkp[jt][0] = bf_pack4(dk[0]); dkp[jt][1] = bf_pack4(dk[1]);

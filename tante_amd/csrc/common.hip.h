@@ -197,6 +197,24 @@ __host__ __device__ __forceinline__ int swz_chunk(int r, int c, int cpr) {
   return (cpr >= 16) ? (c ^ (r & 15)) : (c ^ ((r >> 1) & 7));  // cpr == 8 -> two rows per bank row
 }
 
+// ---- LDS addresses and transposing reads ------------------------------------------------------------
+__device__ __forceinline__ unsigned lds_addr(const char* p) { return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p; }
+// ds_read_b64_tr_b16 (gfx950): per 16-lane group, 4 rows x 16 columns of a row-major 16-bit tile, delivered column-major; lane 4 q + p
+// supplies the address of row q, columns 4 p .. 4 p + 3 (8-byte aligned), and EXEC must be all ones.  It is the compiler's builtin and not
+// inline asm on purpose: an asm read's destination counts as written when the statement ends, so with the s_waitcnt in a later statement
+// the compiler was free to spill or copy the register before the data had landed (tail_chain.hip once returned gradients of 1e22 that
+// way).  The builtin is a load the compiler counts: it places the lgkmcnt wait itself, counted where several reads are in flight, and
+// folds constant byte offsets from p into the instruction's offset: immediate.
+typedef __attribute__((ext_vector_type(4))) short lds_i16x4;
+__device__ __forceinline__ u32x2 lds_tr16_b64(const char* p) {
+  return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) lds_i16x4*)p));
+}
+// the 16-row x 8-k MFMA operand every call site builds: two reads, k 0..3 from p0 and k 4..7 from p1
+__device__ __forceinline__ u32x4 lds_tr16_frag(const char* p0, const char* p1) {
+  const u32x2 lo = lds_tr16_b64(p0), hi = lds_tr16_b64(p1);
+  return u32x4{lo[0], lo[1], hi[0], hi[1]};
+}
+
 // d/dx GELU_erf(x) = Phi(x) + x phi(x) for the bf16 compute path: Phi from the forward's polynomial (|error| <= 8.3e-5), phi from one exp2
 __device__ __forceinline__ float gelu_erf_grad_fast(float x) {
   const float s = fminf(x * x, 18.0625f);

@@ -35,7 +35,6 @@ struct LdsAddr {   // LDS byte address = base (a VGPR) + OFF (an instruction imm
   unsigned base;
   static constexpr int off = OFF;
 };
-__device__ __forceinline__ unsigned lds_addr(const char* p) { return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p; }
 template <int OFF>
 __device__ __forceinline__ u32x4 lds_read128(LdsAddr<OFF> a) {
   static_assert(OFF >= 0 && OFF < 65536, "ds_read offset is a 16-bit immediate");

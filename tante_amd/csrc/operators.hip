@@ -422,17 +422,6 @@ constexpr int XWAVES = 4;         // waves per workgroup (measured: XQG 1 with 6
 constexpr int XGPW_MAX = 8;       // iterations per wave (32 queries each): 8 where the queries fill the chip anyway (K / V staged once per 1024 queries);
                                   // fewer -- more, shorter workgroups -- for the encoder's few hundred queries per (sample, head)
 
-template <int OFF>
-__device__ __forceinline__ u32x2 x_tr_read_off(unsigned base) {   // base VGPR + 16-bit immediate offset
-  u32x2 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(base), "n"(OFF) : "memory");
-  return r;
-}
-__device__ __forceinline__ u32x2 x_tr_read(unsigned addr) {   // ds_read_b64_tr_b16: 4 rows x 16 columns per 16-lane group, column-major out
-  u32x2 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-  return r;
-}
 // V rows are 128 bytes (64 bf16): 16-byte chunk c of row r sits at chunk c ^ (((r >> 1) & 3) << 1), which makes the two 16-lane groups of
 // a half-wave (8 consecutive rows, one aligned chunk pair each) hit 16 distinct 16-byte slots of the 256-byte bank row
 __device__ __forceinline__ int xv_swz(int row) { return ((row >> 1) & 3) << 1; }
@@ -465,10 +454,10 @@ __global__ __launch_bounds__(XWAVES * 64, 2) void xattn_mfma_kernel(const unsign
   // transposed V reads: lane 4 qq + pp of a 16-lane group supplies row (4 kk + qq), columns 4 pp .. 4 pp + 3 of the 16-dim tile dt; the
   // swizzle only looks at row bits 1-2, which the 32-key block offset and the +16 of the second read leave alone
   const int qq = l15 >> 2, pp = l15 & 3;
-  unsigned vb[4];
+  const char* vb[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
-    vb[dt] = lds_addr(vs) + (4 * kk + qq) * 128 + (((dt * 2 + (pp >> 1)) ^ xv_swz(4 * kk + qq)) << 4) + 8 * (pp & 1);
+    vb[dt] = vs + (4 * kk + qq) * 128 + (((dt * 2 + (pp >> 1)) ^ xv_swz(4 * kk + qq)) << 4) + 8 * (pp & 1);
   const u32x4 ones = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -551,13 +540,14 @@ __global__ __launch_bounds__(XWAVES * 64, 2) void xattn_mfma_kernel(const unsign
         for (int dt = 0; dt < 4; ++dt) oacc[g][dt] *= corr;
       }
       // O^T += V^T P^T per 32-key block.  P's k order inside the block is the accumulator order (keys 16 h + 4 kk + r), so an A fragment
-      // is two transposed reads of 4 keys each; the reads of block blk + 1 are in flight under the MFMAs of block blk.
-      unsigned vc[4];
+      // is two transposed reads of 4 keys each; the reads of block blk + 1 are issued before the MFMAs of block blk, which is what lets
+      // the compiler keep them in flight behind counted waits (block offsets are constants: they land in the offset: immediate).
+      const char* vc[4];
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) vc[dt] = vb[dt] + c0 * 128;
       u32x2 vlo[2][4], vhi[2][4];
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) { vlo[0][dt] = x_tr_read_off<0>(vc[dt]); vhi[0][dt] = x_tr_read_off<2048>(vc[dt]); }
+      for (int dt = 0; dt < 4; ++dt) { vlo[0][dt] = lds_tr16_b64(vc[dt]); vhi[0][dt] = lds_tr16_b64(vc[dt] + 2048); }
       static_for<4>([&](auto bc) {
         constexpr int blk = decltype(bc)::value, cur = blk & 1;
         u32x4 pf[XQG];
@@ -566,14 +556,9 @@ __global__ __launch_bounds__(XWAVES * 64, 2) void xattn_mfma_kernel(const unsign
         if constexpr (blk < 3) {
 #pragma unroll
           for (int dt = 0; dt < 4; ++dt) {
-            vlo[cur ^ 1][dt] = x_tr_read_off<(blk + 1) * 4096>(vc[dt]);
-            vhi[cur ^ 1][dt] = x_tr_read_off<(blk + 1) * 4096 + 2048>(vc[dt]);
+            vlo[cur ^ 1][dt] = lds_tr16_b64(vc[dt] + (blk + 1) * 4096);
+            vhi[cur ^ 1][dt] = lds_tr16_b64(vc[dt] + (blk + 1) * 4096 + 2048);
           }
-          asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(vlo[cur][0]), "+v"(vlo[cur][1]), "+v"(vlo[cur][2]), "+v"(vlo[cur][3]), "+v"(vhi[cur][0]),
-                       "+v"(vhi[cur][1]), "+v"(vhi[cur][2]), "+v"(vhi[cur][3]));
-        } else {
-          asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vlo[cur][0]), "+v"(vlo[cur][1]), "+v"(vlo[cur][2]), "+v"(vlo[cur][3]), "+v"(vhi[cur][0]),
-                       "+v"(vhi[cur][1]), "+v"(vhi[cur][2]), "+v"(vhi[cur][3]));
         }
 #pragma unroll
         for (int g = 0; g < XQG; ++g) lacc[g] = xmfma(ones, pf[g], lacc[g]);
