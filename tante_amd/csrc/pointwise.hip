@@ -498,11 +498,13 @@ __device__ __forceinline__ void axe_load_weights(const char* wst, int lane, int 
 // IL line groups are worked on at once, stage by stage (gather | pack | first contraction | GELU | pack | second contraction | update):
 // one group is a chain of dependent LDS reads, packs and 4 - 16 MFMAs that a wave sits out latency by latency (stamps: 3 k cycles per
 // group for ~100 instructions); two independent chains interleave.  IL = 2 is used by the 8-wave form (256 registers per lane).
-template <int MT, int CT, int NWV, int NG, int LS, int GS, bool GOUT, int IL = 1>
+// IT0, ITN: the iterations [IT0, IT0 + ITN) of the phase only (ITN < 0: all of them) -- the column-block schedule runs the H phase block by block.
+template <int MT, int CT, int NWV, int NG, int LS, int GS, bool GOUT, int IL = 1, int IT0 = 0, int ITN = -1>
 __device__ __forceinline__ void axe_phase(float* plane, const AxeW<MT>& W, int wave, int l15, int kk, float* __restrict__ gout, long gls,
                                           long ggs) {
-  constexpr int KB = AxeW<MT>::KB, NIT = CT == 32 ? NG : NG / 2, NE = 8 * KB;
+  constexpr int KB = AxeW<MT>::KB, NIT = ITN < 0 ? (CT == 32 ? NG : NG / 2) : IT0 + ITN, NE = 8 * KB;
   static_assert(CT == 32 || NG % 2 == 0, "16-channel tiles process line groups in pairs");
+  static_assert(IT0 >= 0 && NIT <= (CT == 32 ? NG : NG / 2), "iteration range outside the phase");
   // this lane's (line group within the iteration, channel pair)
   const int gsel = CT == 32 ? 0 : (l15 >> 3), cp = CT == 32 ? 2 * l15 : 2 * (l15 & 7);
   constexpr int GPI = CT == 32 ? 1 : 2;     // line groups per iteration
@@ -518,8 +520,8 @@ __device__ __forceinline__ void axe_phase(float* plane, const AxeW<MT>& W, int w
   f32x2 xa[IL][NE], xn[IL][NE];
 #pragma unroll
   for (int g = 0; g < IL; ++g)
-    if (wave + g * NWV < NIT) gather(wave + g * NWV, xa[g]);
-  for (int it0 = wave; it0 < NIT; it0 += IL * NWV) {
+    if (IT0 + wave + g * NWV < NIT) gather(IT0 + wave + g * NWV, xa[g]);
+  for (int it0 = IT0 + wave; it0 < NIT; it0 += IL * NWV) {
 #pragma unroll
     for (int g = 0; g < IL; ++g)
       if (it0 + (IL + g) * NWV < NIT) gather(it0 + (IL + g) * NWV, xn[g]);
@@ -611,7 +613,39 @@ unsigned long long* g_axe_stamps = nullptr;
 #define AXE_STAMP(k)
 #endif
 
-template <int MTH, int MTW, int CT, int NT>
+// ---- the column-block schedule (NB > 0): the H phase starts while the rest of the plane is still loading --------------------------
+// An H line (fixed w, all h) needs column w of the plane only, so the plane is requested in NB column blocks (all NH rows of NW / NB
+// tokens each): block 0, and once it has landed block 1, whose LDS-DMA is in flight while the H lines of block 0 run -- which the
+// one-block schedule (a wait for everything, then 16 waves computing with an idle memory pipe) never has.
+// What that takes:
+//   * waits by COUNT.  A wave's LDS-DMA instructions complete in issue order, so `vmcnt(n)` with n = the number this wave issued after
+//     the piece it needs retires its share of that piece; the workgroup barrier behind it makes every wave's share visible.  The compiler does
+//     not count LDS-DMA, so the wait is written out (axe_vmcnt) and the barrier is the LDS-only one (axe_lds_barrier): the fence of
+//     __syncthreads() waits vmcnt(0) and would drain the blocks still in flight.
+//   * no ordinary global load between the first DMA and the last wait: the compiler waits vmcnt(0) for the result of one (it would sit
+//     behind the whole plane in the queue anyway).  The weights and biases therefore come by LDS-DMA too, raw fp32 into a scratch area
+//     behind the fragment images and AHEAD of the plane in the queue, and axe_stage_weights turns them into fragment order LDS -> LDS.
+//     That scratch (axe_raw_floats) must fit beside the plane; where it does not, the launcher keeps the one-block schedule.
+//   * whole iterations for every wave in every block (axe_blocks): a wave without a line group in block b would only stand at the next
+//     barrier.  With 16 waves and 32 H groups that is NB = 2; NB = 4 halves the waves at work in each block and was not built.
+// The W phase, the arithmetic of every line and its order are those of the one-block schedule: the planes agree bit for bit
+// (tests/test_axis_hw_blocks.py).  The FiLM-on-load and training forms stay on the one-block schedule (NB = 0).
+__host__ __device__ constexpr int axe_vmcnt(int n) {      // s_waitcnt immediate: vmcnt(n) alone (bits 3:0 and 15:14), expcnt and lgkmcnt left open
+  return (n & 15) | ((n >> 4) << 14) | 0x0070 | 0x0F00;
+}
+__device__ __forceinline__ void axe_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+__host__ __device__ constexpr int axe_raw_floats(int nH, int nW) { return 2 * nH * nH + 2 * nW * nW + 4 * 64; }   // w1 | w2 per axis, then 4 bias rows of 64
+// the number of column blocks for a variant: 2 where both halves give every wave the same whole number of DMA instructions and H iterations
+__host__ __device__ constexpr int axe_blocks(int mth, int mtw, int ct, int nt) {
+  const int nwv = nt / 64, ipr = 16 * mtw / (256 / ct), nith = ct == 32 ? 16 * mtw : 8 * mtw;
+  const int il = (nt == 512 && ct == 32 && mth <= 2 && mtw <= 2) ? 2 : 1;
+  const int nwi = (2 * 256 * mth * mth + 2 * 256 * mtw * mtw) / 256 + 4;        // weight + bias DMA instructions of the workgroup
+  if (ipr % 2 || (16 * mth * (ipr / 2)) % nwv || (nith / 2) % (il * nwv)) return 0;
+  if ((nwi + nwv - 1) / nwv + 16 * mth * ipr / nwv > 63) return 0;              // the 6-bit vmcnt counter
+  return 2;
+}
+
+template <int MTH, int MTW, int CT, int NT, int NB = 0>
 __global__ __launch_bounds__(NT) void axis_hw_exact_kernel(float* __restrict__ x, AxisSrc S, int C, const float* __restrict__ wh1,
                                                            const float* __restrict__ bh1, const float* __restrict__ wh2,
                                                            const float* __restrict__ bh2, const float* __restrict__ ww1,
@@ -639,6 +673,80 @@ __global__ __launch_bounds__(NT) void axis_hw_exact_kernel(float* __restrict__ x
 #endif
   // ---- the plane: one instruction = TPI tokens of a row (lanes LPT t .. LPT t + LPT - 1 = the CT channels of token t) ------------
   constexpr int IPR = NW / TPI;                  // instructions per row
+  if constexpr (NB > 0) {     // ---- column blocks (see above); S.src, xmid: never in this form (the launcher) -------------------------
+    static_assert(NB == 2 && axe_blocks(MTH, MTW, CT, NT) == NB, "no column-block form for this variant");
+    constexpr int JPB = IPR / NB, DPW = NH * JPB / NWV;          // DMA instructions per row and block; per wave and block
+    constexpr int NITH = CT == 32 ? NW : NW / 2, GPB = NITH / NB;   // H iterations, and per block
+    constexpr int IH = NH * NH / 256, IW = NW * NW / 256, NWI = 2 * IH + 2 * IW + 4;
+    static_assert((NWI + NWV - 1) / NWV + NB * DPW <= 63, "the wave's outstanding DMA instructions must fit the 6-bit vmcnt counter");
+    char* wstH = (char*)(plane + NH * RS);
+    char* wstW = wstH + axe_wbytes<MTH>();
+    float* raw = (float*)(wstW + axe_wbytes<MTW>());
+    float* rawb = raw + 2 * NH * NH + 2 * NW * NW;
+    // the weights first: 1 KiB pieces of w1 | w2 (H), w1 | w2 (W), then the four bias vectors (one 4-byte-per-lane instruction each; lanes
+    // past the vector re-read its element 0 into the slack of its 64-float row)
+    for (int i = wave; i < NWI; i += NWV) {
+      if (i < 2 * IH + 2 * IW) {
+        const float* w = i < IH ? wh1 : i < 2 * IH ? wh2 : i < 2 * IH + IW ? ww1 : ww2;
+        const int k = i < IH ? i : i < 2 * IH ? i - IH : i < 2 * IH + IW ? i - 2 * IH : i - 2 * IH - IW;
+        float* d = i < IH ? raw : i < 2 * IH ? raw + NH * NH : i < 2 * IH + IW ? raw + 2 * NH * NH : raw + 2 * NH * NH + NW * NW;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w + k * 256 + lane * 4),
+                                         (__attribute__((address_space(3))) void*)(d + k * 256), 16, 0, 0);
+      } else {
+        const int v = i - (2 * IH + 2 * IW), n = v < 2 ? NH : NW;
+        const float* bp = v == 0 ? bh1 : v == 1 ? bh2 : v == 2 ? bw1 : bw2;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bp + (lane < n ? lane : 0)),
+                                         (__attribute__((address_space(3))) void*)(rawb + v * 64), 4, 0, 0);
+      }
+    }
+    const float* gin = xin ? xin + (gx - x) : gx;
+    auto issue_block = [&](int b) {
+      for (int r = wave; r < NH * JPB; r += NWV) {
+        const int h = r / JPB, j = b * JPB + (r - h * JPB);
+        const float* g = gin + ((long)h * NW + j * TPI + lane / LPT) * C + (lane % LPT) * 4;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                         (__attribute__((address_space(3))) void*)(plane + h * RS + j * 256), 16, 0, 0);
+      }
+    };
+    issue_block(0);
+    AXE_STAMP(1);
+    __builtin_amdgcn_s_waitcnt(axe_vmcnt(DPW));             // everything this wave issued ahead of block 0: the weights
+    axe_lds_barrier();
+    axe_stage_weights<MTH, NT>(raw, rawb, raw + NH * NH, rawb + 64, wstH, tid);
+    axe_stage_weights<MTW, NT>(raw + 2 * NH * NH, rawb + 128, raw + 2 * NH * NH + NW * NW, rawb + 192, wstW, tid);
+    AXE_STAMP(2);
+    __builtin_amdgcn_s_waitcnt(axe_vmcnt(0));               // this wave's share of block 0
+    axe_lds_barrier();                                      // ... and everyone's, and the fragment images
+    // Block 1 goes out HERE, behind block 0's barrier.  The memory pipe takes requests at the rate it serves them, so a wave leaves an
+    // issue loop only when most of what the workgroup asked for has arrived: with both blocks issued up front the first barrier opened
+    // when the whole plane was nearly there (stamps: block 0 ready no earlier than the one-block schedule's plane; 16.0 us a launch
+    // against 16.7), with block 1 issued behind the weights' barrier 15.2 us, here 14.5 us.
+    issue_block(1);
+    AXE_STAMP(3);
+    AxeW<MTH> WH;
+    axe_load_weights<MTH>(wstH, lane, kk, WH);
+    axe_phase<MTH, CT, NWV, NW, RS, CT, false, AXE_IL, 0, GPB>(plane, WH, wave, l15, kk, nullptr, 0, 0);
+    AXE_STAMP(10);
+    __builtin_amdgcn_s_waitcnt(axe_vmcnt(0));               // block 1
+    axe_lds_barrier();
+    AXE_STAMP(11);
+    axe_phase<MTH, CT, NWV, NW, RS, CT, false, AXE_IL, GPB, GPB>(plane, WH, wave, l15, kk, nullptr, 0, 0);
+    AXE_STAMP(4);
+    AxeW<MTW> WW;
+    axe_load_weights<MTW>(wstW, lane, kk, WW);
+    __syncthreads();
+    AXE_STAMP(5);
+    axe_phase<MTW, CT, NWV, NH, CT, RS, true, AXE_IL>(plane, WW, wave, l15, kk, gx, (long)C, (long)NW * C);
+    AXE_STAMP(6);
+#ifdef TANTE_ABLATE
+    if (stamps) {
+      __builtin_amdgcn_s_waitcnt(0x0070);
+      AXE_STAMP(7);
+      if (lane == 0) stamps[((long)blockIdx.x * 16 + wave) * 12 + 9] = __builtin_amdgcn_s_memrealtime();
+    }
+#endif
+    return;
+  }
   if (!S.src) {
     const float* gin = xin ? xin + (gx - x) : gx;
     for (int q = wave; q < NH * IPR; q += NWV) {
@@ -1070,11 +1178,28 @@ static int axis_hw_impl(float* x, const AxisSrc& S, int64_t BT, int nH, int nW, 
 #else
     unsigned long long* axe_st = nullptr;
 #endif
+    // TANTE_AXIS_BLOCKS: 0 = the one-block schedule (load everything, then compute); unset or anything else = the column-block schedule
+    // where the variant has one (axe_blocks), its scratch fits and the weights can go by 16-byte DMA.  Inference forms only.
+    const size_t raw_bytes = (size_t)axe_raw_floats(nH, nW) * sizeof(float);
+    const bool blocks = tante_opt("TANTE_AXIS_BLOCKS", -1) != 0 && !S.src && !xmid && elds + raw_bytes <= 160 * 1024 &&
+                        (((uintptr_t)wh1 | (uintptr_t)wh2 | (uintptr_t)ww1 | (uintptr_t)ww2 | (uintptr_t)xin) % 16) == 0 && C % 4 == 0;
 #define TANTE_AXE2(MH, MW, CTV, NTV)                                                                                                    \
   {                                                                                                                                     \
-    static TantePerDevice attr;                                                                                                         \
-    attr.once([&] { (void)hipFuncSetAttribute((const void*)axis_hw_exact_kernel<MH, MW, CTV, NTV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }); \
-    hipLaunchKernelGGL((axis_hw_exact_kernel<MH, MW, CTV, NTV>), dim3(grid), dim3(NTV), elds, s, x, S, C, wh1, bh1, wh2, bh2, ww1, bw1, ww2, bw2, axe_st, xin, xmid); \
+    constexpr int NBV = axe_blocks(MH, MW, CTV, NTV);                                                                                   \
+    bool done = false;                                                                                                                  \
+    if constexpr (NBV > 0) {                                                                                                            \
+      if (blocks) {                                                                                                                     \
+        static TantePerDevice attrb;                                                                                                    \
+        attrb.once([&] { (void)hipFuncSetAttribute((const void*)axis_hw_exact_kernel<MH, MW, CTV, NTV, NBV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }); \
+        hipLaunchKernelGGL((axis_hw_exact_kernel<MH, MW, CTV, NTV, NBV>), dim3(grid), dim3(NTV), elds + raw_bytes, s, x, S, C, wh1, bh1, wh2, bh2, ww1, bw1, ww2, bw2, axe_st, xin, xmid); \
+        done = true;                                                                                                                    \
+      }                                                                                                                                 \
+    }                                                                                                                                   \
+    if (!done) {                                                                                                                        \
+      static TantePerDevice attr;                                                                                                       \
+      attr.once([&] { (void)hipFuncSetAttribute((const void*)axis_hw_exact_kernel<MH, MW, CTV, NTV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }); \
+      hipLaunchKernelGGL((axis_hw_exact_kernel<MH, MW, CTV, NTV>), dim3(grid), dim3(NTV), elds, s, x, S, C, wh1, bh1, wh2, bh2, ww1, bw1, ww2, bw2, axe_st, xin, xmid); \
+    }                                                                                                                                   \
   }
 #define TANTE_AXE(MH, MW)                  \
   {                                        \

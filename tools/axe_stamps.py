@@ -17,6 +17,10 @@ import tante_amd  # noqa: E402,F401
 from tante_amd import kernels as K  # noqa: E402
 
 NAMES = ["issue plane DMA + weight loads", "wait vmcnt(0)", "barrier", "phase H", "W weights + barrier", "phase W (stores issued)", "stores drained"]
+# the column-block schedule (TANTE_AXIS_BLOCKS != 0) stamps its extra boundaries into slots 10 and 11
+ORDER_B = [0, 1, 2, 3, 10, 11, 4, 5, 6, 7]
+NAMES_B = ["issue weight + block 0 DMA", "wait weights + barrier + fragment images", "wait block 0 + barrier + issue block 1", "phase H, block 0",
+           "wait block 1 + barrier", "phase H, block 1", "W weights + barrier", "phase W (stores issued)", "stores drained"]
 
 
 def main():
@@ -45,11 +49,14 @@ def main():
     lib.tante_axe_set_stamps(None)
     raw = stamps.cpu().numpy().reshape(nwg * 16, 12).astype(np.int64)
     raw = raw[raw[:, 0] != 0]
-    d = np.diff(raw[:, :8], axis=1)
+    blocks = bool((raw[:, 10] != 0).any())
+    names = NAMES_B if blocks else NAMES
+    d = np.diff(raw[:, ORDER_B] if blocks else raw[:, :8], axis=1)
     tot = raw[:, 7] - raw[:, 0]
+    print("schedule:", "column blocks" if blocks else "one block")
     print(f"per wave: {tot.mean():.0f} shader-clock ticks start -> stores drained (min {tot.min()}, max {tot.max()})")
-    for i, n in enumerate(NAMES):
-        print(f"  {n:34s} {d[:, i].mean():9.0f}  ({100 * d[:, i].mean() / tot.mean():5.1f} %)   min {d[:, i].min():7d}  max {d[:, i].max():7d}")
+    for i, n in enumerate(names):
+        print(f"  {n:42s} {d[:, i].mean():9.0f}  ({100 * d[:, i].mean() / tot.mean():5.1f} %)   min {d[:, i].min():7d}  max {d[:, i].max():7d}")
     t0, t1 = raw[:, 8], raw[:, 9]       # 100 MHz wall clock
     base = t0.min()
     print(f"wall clock (10 ns ticks): first start 0, last start {t0.max() - base}, first end {t1.min() - base}, last end {t1.max() - base}")
