@@ -1080,7 +1080,8 @@ class AxisMlpFn(Function):
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, outer, n, inner, compute):
-        if n <= 8 and inner % 4 == 0 and x.dtype == torch.float32 and x.is_contiguous():
+        x = x.contiguous()      # the kernels, forward and backward, read dense (outer, n, inner) rows: a view is made dense ONCE, and that copy is saved
+        if n <= 8 and inner % 4 == 0 and x.dtype == torch.float32:
             # short axes (the temporal propagator): out of place in one launch instead of a 25 MB clone + the in-place kernel
             y = torch.empty_like(x)
             L.check(L.lib().tante_axis_mlp_oop(x.data_ptr(), y.data_ptr(), outer, n, inner, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
@@ -1164,7 +1165,8 @@ class AxisHWFn(Function):
 
     @staticmethod
     def forward(ctx, x, vw1, vb1, vw2, vb2, hw1, hb1, hw2, hb2, BT, H, W, C_, compute):
-        y, xm = K.axis_hw_train(x.detach().contiguous(), BT, H, W, C_, (vw1, vb1, vw2, vb2), (hw1, hb1, hw2, hb2), compute)
+        x = x.detach().contiguous()      # made dense once; the SAME copy is saved: the backward kernels read x.data_ptr() as dense planes
+        y, xm = K.axis_hw_train(x, BT, H, W, C_, (vw1, vb1, vw2, vb2), (hw1, hb1, hw2, hb2), compute)
         ctx.save_for_backward(x, xm, vw1, vb1, vw2, hw1, hb1, hw2)
         ctx.params = (vw1, vb1, vw2, vb2, hw1, hb1, hw2, hb2)
         ctx.dims = (BT, H, W, C_)

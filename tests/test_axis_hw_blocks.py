@@ -9,6 +9,9 @@ tiles and 8 waves; the `ct32` cases force the 32-channel, 16-wave form that the 
   (32, 32) C 128      24 workgroups: gridDim % 8 == 0, the XCD-major remap
   (16, 32), (32, 16)  non-square, both ways round (the second has one DMA instruction per row: one block)
   (64, 32) C 16       the largest MTH that fits 160 KiB (no room for the raw weights beside it: one block)
+
+The FiLM-on-load form (axis_hw_film) is compared here with its own one-block schedule only; its float64 check -- B != T, a window inside
+a wider cache, a FiLM table per slot, s_emb per token -- is tests/test_hip_axis_nodes.py::test_film_on_load_against_float64.
 """
 import math
 
@@ -49,7 +52,7 @@ class _Options:
     def __init__(self, **kw):
         self.kw = kw
 
-    UNSET = {"TANTE_AXIS_BLOCKS": -1, "TANTE_AXIS_CT": 0}       # the values that mean "the launcher's own choice"
+    UNSET = {"TANTE_AXIS_BLOCKS": -1, "TANTE_AXIS_CT": 0, "TANTE_AXIS_GENERIC": 0}       # the values that mean "the launcher's own choice"
 
     def __enter__(self):
         from tante_amd import _lib as L

@@ -965,6 +965,162 @@ def test_harness_step_bars_reject_single_mutations():
         assert r > 2 * R.UPDATE_BAR, f"{mutation}: {r:.3e} inside twice the bar"
 
 
+def test_axis_node_references_match_the_oracles():
+    """The float64 references of tests/test_hip_axis_nodes.py, evaluated in float32, against the CPU oracle (oracle/tante_oracle.py, which
+    tests/golden pins to the reference model): the axis MLP composed as test_hip_parity.py::test_axis_hw_fused composes it, and the FiLM
+    expression against film() + s_emb + t_emb as tante_embed (tante.py:136-141) applies them.  Every comparison <= 1e-5 relative L2."""
+    import test_hip_axis_nodes as R
+    from oracle import tante_oracle as TO
+
+    def rel(a, b):
+        return float((a.double() - b.double()).norm() / b.double().norm())
+
+    def as_w(p):
+        return {"p.0.weight": p[0], "p.0.bias": p[1], "p.2.weight": p[2], "p.2.bias": p[3]}
+
+    g = torch.Generator().manual_seed(10)
+    BT, nH, nW, C = 3, 16, 48, 32
+    x = R.randn((BT, nH, nW, C), g)
+    vp, hp = R.mlp_params(nH, g), R.mlp_params(nW, g)
+    xm = x + TO._axis_mlp(as_w(vp), "p", x.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)            # along h
+    y = xm + TO._axis_mlp(as_w(hp), "p", xm.permute(0, 1, 3, 2)).permute(0, 1, 3, 2)           # along w
+    got_y, got_xm = R.ref_hw(x, vp, hp)
+    assert rel(got_xm, xm) < 1e-5 and rel(got_y, y) < 1e-5
+    # AxisMlpFn's view of the same two calls: (BT, H, W C) along H, then (BT H, W, C) along W
+    a = R.ref_axis_mlp(x.reshape(BT, nH, nW * C), vp)
+    assert rel(a.reshape(BT, nH, nW, C), xm) < 1e-5
+    assert rel(R.ref_axis_mlp(a.reshape(BT * nH, nW, C), hp).reshape(BT, nH, nW, C), y) < 1e-5
+    # the temporal propagator's grouping (B, T, H W C) with T = 3: x + MLP over dimension 1 (attn_backbone.py:144-145)
+    B, T = 2, 3
+    xt = R.randn((B, T, 5, 4, 8), g)
+    tp = R.mlp_params(T, g)
+    want = xt + TO._axis_mlp(as_w(tp), "p", xt.permute(0, 2, 3, 4, 1)).permute(0, 4, 1, 2, 3)
+    assert rel(R.ref_axis_mlp(xt.reshape(B, T, -1), tp).reshape(xt.shape), want) < 1e-5
+    # FiLM on a frame-major cache: fa = 1 + scale(t), fb = shift(t) + t_emb
+    Hp, Wp, Cc = 4, 6, 16
+    w = {}
+    for name in ("condition_to_scale", "condition_to_shift"):
+        w[name + ".0.weight"], w[name + ".0.bias"] = R.randn((Cc // 2, 1), g), R.randn((Cc // 2,), g)
+        w[name + ".2.weight"], w[name + ".2.bias"] = R.randn((Cc, Cc // 2), g, scale=0.5), R.randn((Cc,), g)
+    s_emb, t_emb = R.randn((1, Hp, Wp, Cc), g), R.randn((1, T, Cc), g)
+    ts = TO.t_series(T, 0.5)
+    enc = R.randn((B, T, Hp, Wp, Cc), g)                                            # the encoder's output, (B, T, Hp, Wp, C)
+    want = TO.film(w, enc, ts) + s_emb[:, None] + t_emb[:, :, None, None, :]        # tante_embed's last two lines
+    fa = 1.0 + TO._film_mlp(w, "condition_to_scale", ts)
+    fb = TO._film_mlp(w, "condition_to_shift", ts) + t_emb[0]
+    src = enc.reshape(B, T, Hp * Wp, Cc).transpose(0, 1).contiguous()               # frame-major: (T, B, HW, C)
+    got = R.ref_film(src, fa, fb, s_emb.reshape(Hp * Wp, Cc))
+    assert got.shape == (B, T, Hp * Wp, Cc) and rel(got.reshape(want.shape), want) < 1e-5
+
+
+def test_axis_node_bars_reject_near_misses():
+    """For the kernels of tests/test_hip_axis_nodes.py a WRONG float64 result of the kind they are able to produce, measured the way the
+    GPU test measures (relative L2, max-norm) on that test's own inputs: it lies beyond TWICE the bar the GPU test applies, in at least one
+    of the two norms.  And the other side of the bar: an exact evaluation with both operands of every product rounded to bf16 stays under
+    a third of the forward bar and under half of every gradient bar, so a kernel that does what it says has room.
+    tanh-GELU for erf-GELU differs by about 1e-4 relative: only the fp32 bars see it (asserted); the bf16 routes cannot tell the two
+    apart (also asserted, so that nobody reads those tests as a check of the GELU's form)."""
+    import torch.nn.functional as F
+    import test_hip_axis_nodes as R
+    from conftest import rel_err, max_rel
+
+    def seen(wrong, right, bar, what):
+        r, m = rel_err(wrong.detach(), right.detach()), max_rel(wrong.detach(), right.detach())
+        assert r > 2 * bar[0] or m > 2 * bar[1], f"{what}: rel {r:.3e} max {m:.3e} inside twice the bar {bar}"
+
+    def inside(got, right, bar, frac, what):
+        r, m = rel_err(got.detach(), right.detach()), max_rel(got.detach(), right.detach())
+        assert r < frac * bar[0] and m < frac * bar[1], f"{what}: rel {r:.3e} max {m:.3e} not under {frac:.2f} of the bar {bar}"
+
+    # ---- the FiLM-on-load forward and the saved plane, on every case of the GPU test -----------------------------------------------------
+    for B, T in R.FILM_BT:
+        for nH, nW, C in sorted({p[:3] for p in R.FILM_PLANES}):
+            c = R.film_case(B, T, nH, nW, C)
+            vp, hp, z, fa, fb, se = R.f64(c.vp), R.f64(c.hp), c.z.double(), c.fa.double(), c.fb.double(), c.se.double()
+            what = f"B={B} T={T} {nH}x{nW} C={C}: "
+
+            def run(src, fa=fa, fb=fb, se=se):
+                return R.ref_hw(R.ref_film(src, fa, fb, se).reshape(B * T, nH, nW, C), vp, hp)[0]
+            win = c.win.double()
+            assert rel_err(run(win), c.y) == 0.0
+            seen(run(win, fa=fa.roll(-1, 0), fb=fb.roll(-1, 0)), c.y, R.BF16_FWD, what + "FiLM table of slot t + 1")
+            seen(run(win, se=torch.zeros_like(se)), c.y, R.BF16_FWD, what + "no s_emb")
+            seen(run(win[:, :1].expand(T, B, -1, -1)), c.y, R.BF16_FWD, what + "batch entry 0 for every b")
+            flat = z[1:].reshape(-1)      # the batch stride taken for the plane size: plane (t, b) read at t t_stride + b HW C
+            ts, hw = (B + 1) * (c.HW + R.FILM_PAD) * C, c.HW * C
+            dense_b = torch.stack([torch.stack([flat[t * ts + b * hw: t * ts + (b + 1) * hw] for b in range(B)]) for t in range(T)])
+            seen(run(dense_b.reshape(T, B, c.HW, C)), c.y, R.BF16_FWD, what + "the plane size for the batch stride")
+            tb = R.ref_film(win, fa, fb, se).transpose(0, 1).reshape(T * B, nH, nW, C)
+            seen(R.ref_hw(tb, vp, hp)[0], c.y, R.BF16_FWD, what + "(t, b)-major planes")
+            seen(run(z[0:T, :B, :c.HW]), c.y, R.BF16_FWD, what + "window one frame early")
+            seen(R.ref_prop(R.ref_prop(c.x0, hp, 2), vp, 1), c.y, R.BF16_FWD, what + "W before H")
+            seen(R.ref_prop(c.xm, hp[:3] + (torch.zeros_like(hp[3]),), 2), c.y, R.BF16_FWD, what + "W propagator without b2")
+            seen(c.x0, c.xm, R.BF16_FWD, what + "xm = the input")
+            seen(c.y, c.xm, R.BF16_FWD, what + "xm = the output")
+            x0e = R.ref_film(c.win, c.fa, c.fb, c.se).reshape(B * T, nH, nW, C)      # fp32, as the kernel forms it
+            ye, xme = R.emul_hw(x0e, c.vp, c.hp)
+            inside(ye, c.y, R.BF16_FWD, 1 / 3, what + "bf16-operand y")
+            inside(xme, c.xm, R.BF16_FWD, 1 / 3, what + "bf16-operand xm")
+    # ---- the training forward's cases -------------------------------------------------------------------------------------------------------
+    for nH, nW, C, _ in R.TRAIN_ALL:
+        c = R.hw_case(R.TRAIN_BT, nH, nW, C)
+        ye, xme = R.emul_hw(c.x, c.vp, c.hp)
+        inside(ye, c.y, R.BF16_FWD, 1 / 3, f"train {nH}x{nW} C={C}: bf16-operand y")
+        inside(xme, c.xm, R.BF16_FWD, 1 / 3, f"train {nH}x{nW} C={C}: bf16-operand xm")
+        seen(c.x.double(), c.xm, R.BF16_FWD, f"train {nH}x{nW}: xm = the input")
+        seen(c.y, c.xm, R.BF16_FWD, f"train {nH}x{nW}: xm = the output")
+    # ---- AxisHWFn: the gradients an exact bf16-operand backward gives, and wrong ones -------------------------------------------------------
+    for shape in R.HW_NODE_CASES:
+        c = R.hw_case(*shape)
+        dxe, dpe = R.emul_hw_bwd(c.x, c.G, c.vp, c.hp)
+        inside(R.emul_hw(c.x, c.vp, c.hp)[0], c.y, R.BF16_FWD, 0.5, f"AxisHWFn {shape}: bf16-operand y")
+        inside(dxe, c.dx, R.BF16_DX, 0.5, f"AxisHWFn {shape}: bf16-operand dx")
+        for name, e, r in zip(R.HW_NAMES, dpe, c.dp):
+            inside(e, r, R.BF16_DP, 0.5, f"AxisHWFn {shape}: bf16-operand d{name}")
+        seen(c.dx - c.G.double(), c.dx, R.BF16_DX, f"AxisHWFn {shape}: dx without the residual term")
+        seen(c.dp[2], c.dp[0], R.BF16_DP, f"AxisHWFn {shape}: dW1 and dW2 exchanged (H axis)")
+        seen(c.dp[6], c.dp[4], R.BF16_DP, f"AxisHWFn {shape}: dW1 and dW2 exchanged (W axis)")
+        if c.nH == c.nW:
+            seen(c.dp[0], c.dp[4], R.BF16_DP, f"AxisHWFn {shape}: the H axis' dW1 in the W axis' place")
+    # ---- AxisMlpFn: every case at its own (largest) bar --------------------------------------------------------------------------------------
+    g = torch.Generator().manual_seed(11)
+    for outer, n, inner, mode, _, route in R.MLP_CASES:
+        c = R.mlp_case(outer, n, inner)
+        _, bx, bp = R.mlp_bars(c, mode, route)
+        what = f"AxisMlpFn ({outer},{n},{inner}) {mode} {route}: "
+        xd = c.x.double().requires_grad_()
+        pd = [t.double().requires_grad_() for t in c.p]
+        # one weight used twice, y = f(f(x)): the gradient of the OUTER use alone (the inner output held constant)
+        y1 = R.ref_axis_mlp(xd, pd)
+        both = torch.autograd.grad((R.ref_axis_mlp(y1, pd) * c.G.double()).sum(), pd, retain_graph=True)
+        outer_only = torch.autograd.grad((R.ref_axis_mlp(y1.detach(), pd) * c.G.double()).sum(), pd)
+        for name, a, b in zip(R.NAMES, outer_only, both):
+            seen(a, b, bp, what + f"d{name} from one of two uses")
+        for name, t, r in zip(R.NAMES, c.p, c.dp):
+            fill = R.randn(t.shape, g, scale=R.SLOT_FILL).double()
+            seen(r - fill, r, bp, what + f"the slot of {name} overwritten")
+            seen(2 * r, r, bp, what + f"the slot of {name} added to twice")
+        seen(c.dx - c.G.double(), c.dx, bx, what + "dx without the residual term")
+        seen(c.dp[2], c.dp[0], bp, what + "dW1 and dW2 exchanged")
+        seen(c.dp[0], c.dp[2], bp, what + "dW2 and dW1 exchanged")
+        # db2 = sum of the cotangent over (outer, inner); summed over (outer, n) instead it has `inner` entries, of which n are read
+        assert inner >= n
+        seen(c.G.double().sum((0, 1))[:n], c.dp[3], bp, what + "db2 summed over the wrong axis")
+        if route == R.FUSED and n != 4:
+            dxe, dw1e, db1e, dw2e, db2e = R.emul_prop_bwd(c.x, c.G, c.p, 1)
+            inside(dxe, c.dx, bx, 0.5, what + "bf16-operand dx")
+            for name, e, r in zip(R.NAMES, (dw1e, db1e, dw2e, db2e), c.dp):
+                inside(e, r, bp, 0.5, what + f"bf16-operand d{name}")
+    # ---- tanh-GELU for erf-GELU ---------------------------------------------------------------------------------------------------------------
+    c = R.mlp_case(3, 16, 448)
+    w1, b1, w2, b2 = R.f64(c.p)
+    v = c.x.double().movedim(1, -1)
+    y_tanh = c.x.double() + (F.gelu(v @ w1.t() + b1, approximate="tanh") @ w2.t() + b2).movedim(-1, 1)
+    seen(y_tanh, c.y, R.F32_BAR, "tanh-GELU for erf-GELU, fp32 forward")
+    r, m = rel_err(y_tanh, c.y), max_rel(y_tanh, c.y)
+    assert r < R.BF16_FWD[0] / 10 and m < R.BF16_FWD[1] / 10, "the bf16 bars were not expected to tell the two GELUs apart"
+
+
 def test_lr_schedule_function_and_scheduler_match_the_reference_row():
     """tante_amd.warmup_cosine_lr and the scheduler object stepped per epoch against all 41 values of g10's lr_schedule row (the
     reference's scheduler run past max_epochs), 1e-12 relative -- on an optimizer that exposes .lr, on one that exposes param_groups, and
