@@ -359,6 +359,39 @@ int tante_head_fused_multi_streams(int n_ord, const float* const* rows, const vo
                            int64_t a_s1, int64_t a_s0, int64_t a_off, int n_img, int Hp, int Wp, int C, int D, float* out,
                            int64_t out_bstride, const float* last, int64_t last_bstride, void* stream);
 
+/* ---- adaptive-step tail (adaptive_tail.hip; bf16, deg=False inference: tante.py:145-176) ----------------------------------------------
+ * What a deg=False call does after its last backbone, with the frame count decided on the device.  C in {128, 256}, D <= 16,
+ * patch_scale 8, Hp Wp % 16 == 0 (a wave's 16-token tile lies in one image), n_ord <= 4 orders, n_cap = floor(out_T - 1 + ep) <= 8.
+ * rows[k]: the token rows of the residual stream as backbone k left them, every order addressed like the derivative head's rows
+ * (row r at (r / a_n0) * a_s1 + (r % a_n0) * a_s0 + a_off, a_n0 % 16 == 0).
+ *
+ * The step-size heads of every order (interprator, tante.py:178-201):  t = w3 . relu(W2 relu(W1 x + b1) + b2) + b3 per token on the bf16
+ * matrix pipe (fp32 accumulation; the two hidden activations rounded to bf16, as the GEMM chain stores them), c = t + relu(-t) -
+ * relu(t - (out_T - 1)) (the straight-through clamp's forward value, tante.py:196-198),  r[k][b] = mean_l c + ep.  The mean is a
+ * fixed-order sum: one partial per 16-token tile in `ws`, added in index order -- no floating-point atomics, two runs give the same bits.
+ * R[b] = mean_k r[k][b] (tante.py:157);  count[b] = floor(R[b]) (tante.py:163);  film_a / film_s (n_ord, n_img, C): the modifier's
+ * rows 1 + scale_k(r[k][b]) and shift_k(r[k][b]) (film, tante.py:203-230).  rt_streams[k]: the packed interprator of order k;
+ * film: per order [scale.0.w | scale.0.b | scale.2.w | scale.2.b | shift.0.w | shift.0.b | shift.2.w | shift.2.b] fp32, orders
+ * back to back.  Two launches (tiles; combine + FiLM rows), no host read. */
+int tante_adaptive_tail_supported(int C, int D, int Hp, int Wp, int n_ord, int n_cap);
+int64_t tante_adaptive_rt_stream_bytes(int C);
+int64_t tante_adaptive_ws_bytes(int n_ord, int n_img, int Hp, int Wp);
+int tante_pack_adaptive_rt(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, int C,
+                           void* rt_stream, void* stream);
+int tante_adaptive_rt(int n_ord, const float* const* rows, const void* const* rt_streams, const float* film, int32_t a_n0, int64_t a_s1,
+                      int64_t a_s0, int64_t a_off, int n_img, int Hp, int Wp, int C, float out_T, float ep, void* ws, int64_t ws_bytes,
+                      float* r, float* R, int32_t* count, float* film_a, float* film_s, void* stream);
+/* Every order's derivative head and every frame's Taylor sum in ONE launch (tante.py:147-153, 165-171; enc_dec_cnn.py:263-277):
+ *   d_k = rows_k * film_a[k][b] + film_s[k][b] (applied as the rows are loaded),  D_k = dec_CNN_k(d_k),
+ *   out_j[b] = last[b] + sum_k coefs[k][j - 1] * D_k[b],  j = 1 .. n_b,   n_b = min(count[rule ? b : 0], n_cap)
+ * (rule 0: sample 0 decides for the batch, tante.py:163; rule 1: per sample).  `count` and `coefs` ((n_ord, 8) fp32: (j dt)^(k+1) /
+ * (k+1)!) are DEVICE pointers; frames past n_b are not written.  out / last: base pointer + batch stride (elements), frames of `out`
+ * contiguous (n_cap of them per image); head_streams[k]: the packed head of decoder k. */
+int tante_head_adaptive(int n_ord, const float* const* rows, const void* const* head_streams, int32_t a_n0, int64_t a_s1, int64_t a_s0,
+                        int64_t a_off, int n_img, int Hp, int Wp, int C, int D, const float* film_a, const float* film_s,
+                        const int32_t* count, int rule, const float* coefs, int n_cap, float* out, int64_t out_bstride,
+                        const float* last, int64_t last_bstride, void* stream);
+
 /* Attention over DENSE sequences (token b * L + l) with nn.MultiheadAttention's masks as additive fp32 tensors: attn_mask (L, L) shared
  * (mask_bstride 0) or (Bp * n_head, L, L) (mask_bstride L * L), key_padding_mask (Bp, L); either may be NULL; -inf blocks a key.
  * qkv / o layouts as tante_attention.  The reference's TransformerBlock.forward(x, key_padding_mask, attn_mask, causal) signature

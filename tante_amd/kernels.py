@@ -605,6 +605,98 @@ def head_enc_fused(rows: Sequence[torch.Tensor], a_n0: int, a_s1: int, a_s0: int
     return out
 
 
+# ---- adaptive-step tail (csrc/adaptive_tail.hip): deg=False inference after the last backbone ------------------------------------------
+def adaptive_n_cap(out_T: float, ep: float = 1.001) -> int:
+    """The most frames a deg=False call can return: floor(out_T - 1 + ep), with the kernel's own fp32 arithmetic (the clamp bounds every
+    token to [0, out_T - 1], tante.py:191-201, so R_t <= (out_T - 1) + ep as fp32 sums)."""
+    import math
+    f = lambda v: C.c_float(v).value      # noqa: E731
+    hi = f(f(float(out_T)) - 1.0)
+    return math.floor(f(max(hi, 0.0) + f(float(ep))))
+
+
+def adaptive_tail_supported_py(C_: int, D: int, Hp: int, Wp: int, n_ord: int, n_cap: int) -> bool:
+    """Pure-Python mirror of tante_adaptive_tail_supported (tests/test_adaptive_tail_cpu.py holds the two together)."""
+    return (C_ in (128, 256) and 1 <= D <= 16 and Hp > 0 and Wp > 0 and (Hp * Wp) % 16 == 0 and Hp * Wp < (1 << 22) and 1 <= n_ord <= 4
+            and 1 <= n_cap <= 8)
+
+
+def adaptive_tail_supported(C_: int, D: int, Hp: int, Wp: int, n_ord: int, n_cap: int) -> bool:
+    return bool(L.lib().tante_adaptive_tail_supported(C_, D, Hp, Wp, n_ord, n_cap))
+
+
+def pack_adaptive_rt(params: Sequence[torch.Tensor], C_: int) -> torch.Tensor:
+    """params = (lin1.w, lin1.b, lin2.w, lin2.b, lin3.w, lin3.b) of an interprator -> its stream for adaptive_rt."""
+    ps = [p.detach() for p in params]
+    _dev(*ps)
+    if C_ not in (128, 256):
+        raise RuntimeError(f"pack_adaptive_rt: unsupported C={C_}")
+    st = torch.empty(L.lib().tante_adaptive_rt_stream_bytes(C_), dtype=torch.uint8, device=ps[0].device)
+    L.check(L.lib().tante_pack_adaptive_rt(*[_p(p) for p in ps], C_, _p(st), _stream()), "tante_pack_adaptive_rt")
+    return st
+
+
+def pack_adaptive_film(films: Sequence[Sequence[torch.Tensor]]) -> torch.Tensor:
+    """films[k] = (scale.0.w, scale.0.b, scale.2.w, scale.2.b, shift.0.w, shift.0.b, shift.2.w, shift.2.b) of modifier k -> one flat fp32
+    buffer, orders back to back (a parameter-sized copy, made when the weights change)."""
+    ps = [p.detach() for f in films for p in f]
+    _dev(*ps)
+    return torch.cat([p.reshape(-1).to(torch.float32) for p in ps]).contiguous()
+
+
+def adaptive_rt(rows: Sequence[torch.Tensor], a_n0: int, a_s1: int, a_s0: int, a_off: int, n_img: int, Hp: int, Wp: int, C_: int,
+                rt_streams: Sequence[torch.Tensor], film: torch.Tensor, out_T: float, ep: float):
+    """Every order's step-size head, the fixed-order means and the modifier FiLM rows, without a host read:
+    -> (r (n_ord, n_img), R (n_img,), count (n_img,) int32 = floor(R), film_a, film_s (n_ord, n_img, C_)).  All five are views of one
+    buffer (with the tile partials in front)."""
+    n = len(rows)
+    _dev(*rows, *rt_streams, film)
+    if n != len(rt_streams) or not 1 <= n <= 4:
+        raise RuntimeError("adaptive_rt: 1 .. 4 orders, one stream each")
+    if not adaptive_tail_supported_py(C_, 1, Hp, Wp, n, 1) or n_img < 1:
+        raise RuntimeError(f"adaptive_rt: unsupported shape C={C_} Hp={Hp} Wp={Wp} n_img={n_img}")
+    if any(r.dtype != torch.float32 for r in rows) or film.dtype != torch.float32 or film.numel() != n * 2 * (C_ + C_ // 2 * (C_ + 2)):
+        raise RuntimeError("adaptive_rt: fp32 rows and the packed modifiers of every order expected")
+    al = lambda v: (v + 3) // 4 * 4      # noqa: E731
+    wsf = al(L.lib().tante_adaptive_ws_bytes(n, n_img, Hp, Wp) // 4)
+    o_r, o_R, o_c = wsf, wsf + al(n * n_img), wsf + al(n * n_img) + al(n_img)
+    o_a = o_c + al(n_img)
+    o_s = o_a + n * n_img * C_
+    buf = torch.empty(o_s + n * n_img * C_, dtype=torch.float32, device=rows[0].device)
+    r, R, cnt = buf[o_r: o_r + n * n_img].view(n, n_img), buf[o_R: o_R + n_img], buf[o_c: o_c + n_img].view(torch.int32)
+    fa, fs = buf[o_a: o_s].view(n, n_img, C_), buf[o_s:].view(n, n_img, C_)
+    rp = (C.c_void_p * n)(*[t.data_ptr() for t in rows])
+    sp = (C.c_void_p * n)(*[t.data_ptr() for t in rt_streams])
+    L.check(L.lib().tante_adaptive_rt(n, rp, sp, _p(film), a_n0, a_s1, a_s0, a_off, n_img, Hp, Wp, C_, float(out_T), float(ep), buf.data_ptr(),
+                                      wsf * 4, r.data_ptr(), R.data_ptr(), cnt.data_ptr(), fa.data_ptr(), fs.data_ptr(), _stream()),
+            "tante_adaptive_rt")
+    return r, R, cnt, fa, fs
+
+
+def head_adaptive(rows: Sequence[torch.Tensor], a_n0: int, a_s1: int, a_s0: int, a_off: int, n_img: int, Hp: int, Wp: int, C_: int, D: int,
+                  head_streams: Sequence[torch.Tensor], film_a: torch.Tensor, film_s: torch.Tensor, count: torch.Tensor, per_sample: bool,
+                  coefs: torch.Tensor, n_cap: int, out: torch.Tensor, out_bstride: int, last: torch.Tensor, last_elem_off: int,
+                  last_bstride: int):
+    """out_j[b] = last[b] + sum_k coefs[k, j - 1] * head_k(rows[k] * film_a[k, b] + film_s[k, b]) for j <= count[b if per_sample else 0]
+    (held to n_cap), in ONE launch; `count` (int32) and `coefs` ((n_ord, 8) fp32) stay on the device.  `out` / `last` are base tensors
+    addressed by data_ptr (+ offset) and a batch stride; frames past the count are not written."""
+    n = len(rows)
+    _dev(*rows, *head_streams, film_a, film_s, count, coefs)
+    if not (out.is_cuda and last.is_cuda):
+        raise RuntimeError("tante_amd kernels need CUDA/HIP tensors (no CPU fallback)")
+    if n != len(head_streams) or not adaptive_tail_supported_py(C_, D, Hp, Wp, n, n_cap) or n_img < 1:
+        raise RuntimeError(f"head_adaptive: unsupported shape C={C_} D={D} Hp={Hp} Wp={Wp} n_ord={n} n_cap={n_cap}")
+    if (count.dtype != torch.int32 or count.numel() != n_img or coefs.dtype != torch.float32 or coefs.numel() != n * 8
+            or film_a.dtype != torch.float32 or film_a.numel() != n * n_img * C_ or film_s.dtype != torch.float32 or film_s.numel() != n * n_img * C_):
+        raise RuntimeError("head_adaptive: count (n_img,) int32, coefs (n_ord, 8) fp32, film rows (n_ord, n_img, C) fp32 expected")
+    rp = (C.c_void_p * n)(*[t.data_ptr() for t in rows])
+    sp = (C.c_void_p * n)(*[t.data_ptr() for t in head_streams])
+    L.check(L.lib().tante_head_adaptive(n, rp, sp, a_n0, a_s1, a_s0, a_off, n_img, Hp, Wp, C_, D, _p(film_a), _p(film_s), _p(count),
+                                        int(bool(per_sample)), _p(coefs), n_cap, out.data_ptr(), out_bstride,
+                                        last.data_ptr() + 4 * last_elem_off, last_bstride, _stream()), "tante_head_adaptive")
+    return out
+
+
 def enc23_supported(C_: int) -> bool:
     return bool(L.lib().tante_enc23_supported(C_))
 

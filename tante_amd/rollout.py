@@ -291,6 +291,11 @@ def rollout_adaptive(model, batch: Dict, formatter, n_steps: int, out_T: float, 
         per_sample = False
     if per_sample and batch_when_equivalent and xs.shape[0] > 1:
         return _rollout_adaptive_batched(model, xs, y_ref.to(device), formatter, n_steps, out_T)
+    from .tante import TANTE
+    if (not per_sample and isinstance(model, TANTE) and not model.deg and not torch.is_grad_enabled() and xs.is_cuda and xs.dtype == torch.float32
+            and xs.shape[1] == model.T and n_steps >= 1 and model.adaptive_tail_route(out_T)):
+        y, rts = _rollout_adaptive_in_place(model, xs, n_steps, out_T)
+        return formatter.process_output(y), y_ref.to(device), rts
     chunks = [xs[i:i + 1] for i in range(xs.shape[0])] if per_sample else [xs]
     from .train_forward import fold_scope
     rts, outs = [], []
@@ -306,6 +311,37 @@ def rollout_adaptive(model, batch: Dict, formatter, n_steps: int, out_T: float, 
                 rts.append(rt)
             outs.append(torch.cat(preds, dim=1)[:, :n_steps])
     return torch.cat(outs, dim=0), y_ref.to(device), torch.cat(rts, dim=0)
+
+
+def _rollout_adaptive_in_place(model, x: torch.Tensor, n_steps: int, out_T: float):
+    """R_Evaler's loop (r_evaler.py:87-105, sample 0 decides every call's frame count) without its copies, as _rollout_in_place does for
+    the fixed step: one (B, T + n_steps + n_cap - 1, D, H, W) buffer holds the window and every predicted frame.  A call reads
+    buf[:, pos: pos + T] in place and writes through out= into the n_cap slots behind it; after its one host read pos advances by the n
+    frames it returned, and the slots past them are overwritten by the next call.  Every frame is encoded once (encode_frames on the n new
+    frames after each call) where the model has the frame-encoding cache.  -> (frames (B, n_steps, D, H, W), concatenated R_t)."""
+    from . import kernels as K
+    B, T = x.shape[:2]
+    n_cap = K.adaptive_n_cap(out_T, model.interprators[0].ep)
+    total = T + n_steps + n_cap - 1
+    buf = torch.empty(B, total, *x.shape[2:], dtype=torch.float32, device=x.device)
+    buf[:, :T].copy_(x)           # the formatter's 'b t h w c -> b t c h w' is materialised here, once
+    cache = model.enc_cache_supported(out_T) and not NO_ENC_CACHE
+    HW, C_ = model.H_p * model.W_p, model.C
+    z = torch.empty(total, B, HW, C_, dtype=torch.float32, device=x.device) if cache else None
+    pos, encoded, rts = 0, 0, []
+    while pos < n_steps:
+        kw = {}
+        if cache:
+            if pos + T > encoded:                    # the first call encodes the whole window, later calls the frames the last one added
+                model.encode_frames(buf[:, encoded: pos + T], z[encoded: pos + T])
+                encoded = pos + T
+            kw["enc_cache"] = (z[pos:], B * HW * C_, HW * C_)
+        y, rt = model(buf[:, pos: pos + T], out_T, out=buf[:, pos + T: pos + T + n_cap], **kw)
+        rts.append(rt)
+        if y.shape[1] < 1:
+            raise RuntimeError("rollout_adaptive: a call returned no frame (R_t[0] < 1): the rollout cannot advance")
+        pos += y.shape[1]
+    return buf[:, T: T + n_steps], torch.cat(rts, dim=0)
 
 
 def _rollout_adaptive_batched(model, xs: torch.Tensor, y_ref: torch.Tensor, formatter, n_steps: int, out_T: float):

@@ -61,6 +61,10 @@ HEAD_ENC = _O.register("TANTE_HEAD_ENC", True, __name__, "HEAD_ENC")          # 
 # the last Taylor order's backbone finishes only the rows of time slot T - 1, the one slot the head reads (Attn_Backbone.forward_tokens
 # (last_slot_only=True)): its last T letter writes those rows alone, the H / W letters after it run on the slot-(T - 1) planes
 LAST_SLOT = _O.register("TANTE_LAST_SLOT", True, __name__, "LAST_SLOT")
+# deg=False inference: the tail of a call (step-size heads, modifier FiLM, derivative heads, Taylor sums) as tante_adaptive_rt +
+# tante_head_adaptive with the frame count decided on the device (csrc/adaptive_tail.hip).  0: a GEMM chain, a reduction, a FiLM table, a
+# FiLM pass per order, a host read, then one head launch per order (A/B).
+ADAPTIVE_TAIL = _O.register("TANTE_ADAPTIVE_TAIL", True, __name__, "ADAPTIVE_TAIL")
 
 
 def _check_patch_cfg(patch_scale, overlap_ratio):
@@ -361,6 +365,12 @@ class interprator(nn.Module):
         return self._cache.get(compute, [p for l in lin for p in (l.weight, l.bias)],
                                lambda: [K.pack_weight(l.weight, l.bias, compute) for l in lin])
 
+    def packed_rt(self):
+        """Stream of the one-launch step-size heads (kernels.adaptive_rt), rebuilt when a parameter changes; _packed stays as it is."""
+        lin = [self.interprete[0], self.interprete[2], self.interprete[4]]
+        params = [p for l in lin for p in (l.weight, l.bias)]
+        return self._cache.get(-5, params, lambda: K.pack_adaptive_rt(params, self.h_dim))
+
     def forward_tokens(self, src: torch.Tensor, B: int, out_T: float, compute: int, a_n0: int, a_s1: int, a_s0: int, a_off: int):
         pk = self._packed(compute)
         n = B * self.sp_dim
@@ -487,27 +497,30 @@ class TANTE(nn.Module):
     # depend on the window it is read in: a sliding-window rollout needs each frame encoded ONCE, not once per window containing it
     # (T times).  encode_frame() writes that pre-FiLM encoding; forward(enc_cache=...) skips the encoder and lets the first propagator
     # kernel apply FiLM while it loads the planes.  Same arithmetic per token, term for term.
-    def enc_cache_supported(self) -> bool:
+    def enc_cache_supported(self, out_T=None) -> bool:
+        """deg=False: only for calls that take the adaptive tail (adaptive_tail_route(out_T)); give the out_T the calls will use."""
+        if not self.deg:
+            return bool(out_T is not None and self.adaptive_tail_route(out_T) and (self._enc_cache_fused(True) or self._enc_cache_frames(True)))
         return self._enc_cache_fused() or self._enc_cache_frames()
 
-    def _enc_cache_fused(self) -> bool:
+    def _enc_cache_fused(self, any_deg: bool = False) -> bool:
         """enc_CNN with the fused stages: the first propagator launch applies FiLM while it loads the cached planes."""
         compute = resolve_compute(self.compute)
-        return bool(self.deg and type(self.encoder).__name__ == "enc_CNN" and self.encoder.fuses_23(compute)
+        return bool((self.deg or any_deg) and type(self.encoder).__name__ == "enc_CNN" and self.encoder.fuses_23(compute)
                     and K.axis_hw_supported(self.H_p, self.W_p, self.C))
 
-    def _enc_cache_frames(self) -> bool:
+    def _enc_cache_frames(self, any_deg: bool = False) -> bool:
         """The spectral encoder (round 5): enc_FNO is per frame too (enc_dec_fno.py:224-273: every layer acts on (B T) images), so the
         rollout encodes each frame once and a window is T cached encodings + one FiLM / positional pass over them
         (tante_film_pos_fwd_frames: the same expression per token as the dense pass).  At cfg5 the encoder was 42 % of a model call and
         three of its four frames had been encoded by the previous calls."""
-        return bool(self.deg and type(self.encoder).__name__ == "enc_FNO" and self.C == 256 and 1 <= self.T <= 8)
+        return bool((self.deg or any_deg) and type(self.encoder).__name__ == "enc_FNO" and self.C == 256 and 1 <= self.T <= 8)
 
     def encode_frames(self, frames: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
         """frames: (B, F, D, H, W) fp32 view (contiguous frames, any batch stride) -> z (F, B, Hp*Wp, C) fp32, the encoder output before
         FiLM in the frame-major layout forward(enc_cache=...) reads (one launch pair for the F frames)."""
         compute = resolve_compute(self.compute)
-        if self._enc_cache_frames() and not self._enc_cache_fused():
+        if self._enc_cache_frames(True) and not self._enc_cache_fused(True):
             B, F = frames.shape[:2]
             # one frame: the rows (b, hw) ARE the cache entry -- the encoder's last GEMM writes them there
             want = z.view(B * self.H_p * self.W_p, self.C) if (F == 1 and z.is_contiguous()) else None
@@ -531,10 +544,70 @@ class TANTE(nn.Module):
                     and self.decoders[0].overlap == 0.0 and K.head_enc_supported(self.C, self.D, self.H_p, self.W_p)
                     and all(b.takes_x_in(compute) for b in self.blocks[1:self.taylor_order]))
 
+    def adaptive_tail_route(self, out_T) -> bool:
+        """A deg=False inference call with this out_T runs its tail as tante_adaptive_rt + tante_head_adaptive (csrc/adaptive_tail.hip):
+        the switch TANTE_ADAPTIVE_TAIL is on, compute is bf16, the heads are the three 2 x 2 stages of patch_scale 8 at C = 128 / 256,
+        whole 16-token tiles per image, at most 4 orders and n_cap = floor(out_T - 1 + ep) <= 8 frames.  Everything else keeps the
+        launches and the bits it had."""
+        if self.deg or not ADAPTIVE_TAIL or resolve_compute(self.compute) != L.BF16 or not self.fused_head:
+            return False
+        if getattr(self.decoders[0], 'P', None) != (2, 2, 2) or self.decoders[0].overlap != 0.0:
+            return False
+        ep = self.interprators[0].ep
+        if any(ip.ep != ep for ip in self.interprators):
+            return False
+        return K.adaptive_tail_supported(self.C, self.D, self.H_p, self.W_p, self.taylor_order, K.adaptive_n_cap(out_T, ep))
+
+    def _adaptive_packs(self, device):
+        """(modifier FiLM weights of every order as one buffer, Taylor coefficients (n_ord, 8) on the device)."""
+        mods = []
+        for m in self.modifiers:
+            sc, sh = m.condition_to_scale, m.condition_to_shift
+            mods.append((sc[0].weight, sc[0].bias, sc[2].weight, sc[2].bias, sh[0].weight, sh[0].bias, sh[2].weight, sh[2].bias))
+        film = self._film_cache.get(1, [p for f in mods for p in f], lambda: K.pack_adaptive_film(mods))
+        key = (self.taylor_order, float(self.frame_interval), device)
+        hit = getattr(self, "_adaptive_coefs", None)
+        if hit is None or hit[0] != key:
+            rows = [[(j * self.frame_interval) ** (k + 1) / math.factorial(k + 1) for j in range(1, 9)] for k in range(self.taylor_order)]
+            hit = (key, torch.tensor(rows, dtype=torch.float32, device=device).contiguous())
+            self._adaptive_coefs = hit
+        return film, hit[1]
+
+    def _adaptive_tail(self, x, inp, out_T, n_cap, out, enc_cache, film, film_frames, per_sample_counts, compute):
+        """deg=False inference on the fused head path (tante.py:145-176): the backbones as ever, then rt -> head with no host read between."""
+        B, T, D, H, W = inp.shape
+        Hp, Wp, C_, n_ord = self.H_p, self.W_p, self.C, self.taylor_order
+        HW, frame = Hp * Wp, D * H * W
+        # each order's last-slot rows must survive the later backbones, as on the deg=True multi-head route: out-of-place streams when
+        # every later backbone can write a buffer of its own, else dense copies of the last-slot rows
+        streams = all(b.takes_x_in(compute) for b in self.blocks[1:n_ord])
+        rows = []
+        for i in range(n_ord):
+            if streams and i > 0:
+                x_prev, x = x, torch.empty_like(x)
+                self.blocks[i].forward_tokens(x, B, compute, x_in=x_prev)
+            else:
+                self.blocks[i].forward_tokens(x, B, compute, film_src=(enc_cache + (film,)) if (enc_cache is not None and i == 0) else None,
+                                              film_frames=film_frames if i == 0 else None)                      # l.146 (chained)
+            rows.append(x if streams else x.view(B, T, HW * C_)[:, T - 1].clone(memory_format=torch.contiguous_format).view(B * HW, C_))
+        addr = (HW, T * HW * C_, C_, (T - 1) * HW * C_) if streams else (B * HW, 0, C_, 0)
+        film_pack, coefs = self._adaptive_packs(x.device)
+        _, R_t, count, fa, fs = K.adaptive_rt(rows, *addr, B, Hp, Wp, C_, [ip.packed_rt() for ip in self.interprators], film_pack, out_T,
+                                              self.interprators[0].ep)                                          # l.148-152, 157
+        if out is None:
+            out = torch.empty(B, n_cap, D, H, W, dtype=torch.float32, device=x.device)
+        K.head_adaptive(rows, *addr, B, Hp, Wp, C_, D, [d.packed_head() for d in self.decoders], fa, fs, count, per_sample_counts, coefs,
+                        n_cap, out, out.stride(0), inp, (T - 1) * frame, inp.stride(0))                          # l.147,153,163-171
+        # l.163: the one host read, after everything is enqueued -- it only sizes the returned view
+        counts = count.tolist()
+        n_out = min(max(counts) if per_sample_counts else counts[0], n_cap)
+        return out[:, :max(n_out, 0)], R_t
+
     def forward(self, input: torch.Tensor, out_T=1, out: Optional[torch.Tensor] = None, enc_cache: Optional[tuple] = None,
                 enc_next: Optional[torch.Tensor] = None, per_sample_counts: bool = False):
-        """`out` (optional, deg=True only): a (B, output_length, D, H, W) fp32 view with contiguous frames (e.g. the next
-        slots of a rollout buffer) that receives the prediction instead of a fresh tensor.
+        """`out` (optional): a (B, output_length, D, H, W) fp32 view with contiguous frames (e.g. the next slots of a rollout buffer)
+        that receives the prediction instead of a fresh tensor.  deg=False: only on the adaptive tail (adaptive_tail_route(out_T)), where
+        it is a (B, n_cap, D, H, W) view, n_cap = kernels.adaptive_n_cap(out_T); only the frames the call returns are defined afterwards.
         `enc_cache` = (z, t_stride, b_stride): the window's frames already encoded by encode_frame (frame t of item b at
         z + t * t_stride + b * b_stride); see enc_cache_supported().
         `enc_next` (tail_fused_supported() only): a contiguous (B, Hp*Wp, C) fp32 tensor that receives the pre-FiLM encoding of the
@@ -543,6 +616,11 @@ class TANTE(nn.Module):
         (tante.py:163), which is why R_Trainer loops over the samples one at a time (r_trainer.py:118-119).  With this flag the call
         produces max_i floor(R_t[i]) frames; frame j of sample i is what a single-sample call would give for j < floor(R_t[i]) (every op
         of the path is per sample), and the caller keeps floor(R_t[i]) frames of sample i (rollout.rollout_adaptive).
+        deg=False, inference, bf16 (adaptive_tail_route): after the last backbone the call is tante_adaptive_rt (two small launches) and ONE
+        tante_head_adaptive launch whatever the order count; the frame count is read from device memory by the head launch, and the one
+        host read (of floor(R_t), to size the returned view) comes after everything is enqueued.  Against TANTE_ADAPTIVE_TAIL=0 the
+        results differ in bf16 rounding ORDER only: the same operand roundings, another summation order in the step-size mean and in the
+        Taylor sum.
         With autograd enabled the differentiable path (train_forward.py: HIP forward + HIP backward kernels) runs."""
         if not input.is_cuda:
             raise RuntimeError("tante_amd.TANTE runs on the GPU only (no CPU fallback); move the input to cuda")
@@ -566,11 +644,12 @@ class TANTE(nn.Module):
         fa, fb = self._time_tables()
         film = (fa, fb, self.s_emb.view(HW, C_), T, HW)
         film_frames = None
+        adaptive = self.adaptive_tail_route(out_T)
         if enc_cache is not None:
-            if not self.enc_cache_supported():
+            if not (self.enc_cache_supported() if self.deg else (adaptive and self.enc_cache_supported(out_T))):
                 raise RuntimeError("enc_cache: this model / compute mode has no frame-encoding cache path")
             x = torch.empty(B * T * HW, C_, dtype=torch.float32, device=inp.device)
-            if not self._enc_cache_fused():      # cached frames + FiLM / positional terms in one pass (tante.py:136-141 over the window)
+            if not self._enc_cache_fused(True):      # cached frames + FiLM / positional terms in one pass (tante.py:136-141 over the window)
                 zc = enc_cache[0]
                 fr = L.Frames()
                 for t in range(T):
@@ -594,12 +673,17 @@ class TANTE(nn.Module):
         last_slot = dict(a_n0=HW, a_s1=T * HW * C_, a_s0=C_, a_off=(T - 1) * HW * C_)               # x[:, -1:] by stride
         fused_head = (compute == L.BF16 and self.fused_head and getattr(self.decoders[0], 'P', None) == (2, 2, 2) and self.decoders[0].overlap == 0.0
                       and K.head_fused_supported(C_, D))
+        n_cap = K.adaptive_n_cap(out_T, self.interprators[0].ep) if adaptive else 0
         if out is not None:
-            if not self.deg:
-                raise ValueError("out= is only meaningful with a fixed output length (deg=True)")
-            if tuple(out.shape) != (B, self.output_length, D, H, W) or out.dtype != torch.float32 or not out.is_cuda \
+            if not self.deg and not adaptive:
+                raise ValueError("out= is only meaningful with a fixed output length (deg=True) or on the adaptive tail (adaptive_tail_route)")
+            if tuple(out.shape) != (B, self.output_length if self.deg else n_cap, D, H, W) or out.dtype != torch.float32 or not out.is_cuda \
                     or out.stride()[1:] != (frame, H * W, W, 1) or out.stride(0) % 4 or out.data_ptr() % 16:
-                raise ValueError("out must be a (B, output_length, D, H, W) fp32 CUDA view with contiguous frames")
+                raise ValueError("out must be a (B, output_length, D, H, W) fp32 CUDA view with contiguous frames (deg=False: n_cap frames)")
+        if adaptive:
+            if enc_next is not None:
+                raise RuntimeError("enc_next: this model / compute mode has no fused head + re-encoding path (tail_fused_supported())")
+            return self._adaptive_tail(x, inp, out_T, n_cap, out, enc_cache, film, film_frames, per_sample_counts, compute)
         derivs, r_t, srcs = [], [], []
         # one prediction frame, several Taylor orders: ONE head launch after the last backbone (tante_head_fused_multi) instead of one per
         # order -- the frame is read and written once instead of taylor_order times.  The earlier orders' last-slot rows are copied aside
