@@ -537,7 +537,12 @@ int tante_resize_bilinear_bwd(const void* dout, int d_dtype, int64_t n_img, int 
                               float* din, void* stream);
 /* softmax(q k^T / sqrt(D)) v per (batch, head) with separate query and key/value sequences -- the core of
  * nn.MultiheadAttention(q, kv, kv) in CViT's CrossAttnBlock / TimeAggregation / SelfAttnBlock (cvit.py:125, 162, 199-204).
- * Rows: q (b, i) at (b*Lq + i)*ldq + h*D, k / v (b, j) at (b*Lk + j)*ldkv + h*D, o at (b*Lq + i)*ldo + h*D (elements). */
+ * Rows: q (b, i) at (b*Lq + i)*ldq + h*D, k / v (b, j) at (b*Lk + j)*ldkv + h*D, o at (b*Lq + i)*ldo + h*D (elements).
+ * bf16 with D = 32 or 64 runs on the matrix pipe for ANY Lk (fp32 scores, online softmax over 128-key chunks, probabilities rounded to
+ * bf16, fp32 accumulation): K and V resident in LDS while Lk rounded up to 128 times D * 4 bytes fits 128 KiB (512 keys at D = 64, 1024
+ * at D = 32), streamed through a two-stage LDS ring (64 KiB at D = 64, 32 KiB at D = 32) beyond that, with the same bits where both apply.  It needs ldq, ldkv multiples of 8,
+ * ldo of 4, q / k / v 16-byte and o 8-byte aligned; everything else (fp32, other head dims in {4, 8, 12, 16, 32, 64}, unaligned rows)
+ * takes the exact lane-per-query kernel.  tante_cross_attention_route tells which. */
 int tante_cross_attention(const void* q, const void* k, const void* v, void* o, int dtype, int64_t n_batch, int n_head, int D, int Lq,
                           int Lk, int64_t ldq, int64_t ldkv, int64_t ldo, void* stream);
 /* CViT blocks at width 512 (8 heads x 64, mlp_ratio 1), bf16: everything behind the attention of a SelfAttnBlock / CrossAttnBlock
@@ -564,6 +569,11 @@ int tante_cvit_chain512_qkv(const void* a, const float* resid, int64_t resid_per
  * attends with the SAME Lq queries -- the decoder's coordinate queries, cvit.py:452, whose projection is then computed once). */
 int tante_cross_attention_q(const void* q, const void* k, const void* v, void* o, int dtype, int64_t n_batch, int n_head, int D, int Lq,
                             int Lk, int64_t ldq, int64_t ldkv, int64_t ldo, int64_t q_batch_rows, void* stream);
+/* The kernel tante_cross_attention[_q] picks for (dtype, D, Lk) when the leading dimensions and pointers are aligned as described there
+ * (nn.MultiheadAttention's head dims in CViT: cvit.py:125, 162, 199-204): 0 = exact lane-per-query kernel, 1 = matrix pipe with K and V
+ * resident in LDS, 2 = matrix pipe with K and V streamed through the LDS ring.  Options: TANTE_XATTN_VALU = 1 forces 0;
+ * TANTE_XATTN_STREAM = 1 forces 2 wherever the matrix pipe applies.  Added without an ABI bump (nothing that existed changed). */
+int tante_cross_attention_route(int dtype, int D, int Lk);
 /* Backward of tante_cross_attention.  o is the forward output; dq gets the query gradient in the layout of q; the key / value gradients
  * are ADDED (fp32 atomics) to dk / dv, rows (b, j) at (b*Lk + j)*ldg + h*D -- zero them first.  stats: n_batch*n_head*Lq*3 floats of
  * scratch (softmax max, 1 / sum, dO . O per query). */

@@ -399,15 +399,23 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(const void* __restrict_
   }
 }
 
-// ---- CViT attention on the matrix cores (bf16, head dim 64, up to 512 keys) ----------------------------------------------------
-// One workgroup = one (batch, head) and XQ_PER_WG queries.  K (rows = keys) and V^T (rows = head dims, keys k-permuted inside every
-// 32-block) are staged ONCE per workgroup in LDS as bf16 in the swizzled 16-byte-chunk image the MFMA A operand reads with
-// ds_read_b128; every wave then walks its queries 32 at a time (two B operands per fragment read, halving the LDS traffic):
+// ---- CViT attention on the matrix cores (bf16, head dim 32 or 64, any number of keys) -------------------------------------------
+// One workgroup = one (batch, head) and XQ_PER_WG queries.  K and V (rows = keys) sit in LDS as bf16, row-major, in the swizzled
+// 16-byte-chunk image that the MFMA A operand reads with ds_read_b128 (K) and with transposing reads (V); every wave walks its queries
+// 32 at a time (two B operands per fragment read, halving the LDS traffic):
 //   S^T tile (16 keys x 16 queries) = K_tile . Q^T            -- "rows = keys", so a lane holds 4 keys of ONE query column
 //   online softmax over 128-key chunks: per-lane max / partial sums, two __shfl_xor for the cross-lane max, exp2 with the
 //   1/sqrt(D) log2(e) factor applied to the fp32 scores
 //   O^T (16 dims x 16 queries) += V^T_tile . P^T              -- the probability tiles, packed to bf16, ARE the B operand
-// (key order inside a 32-block = accumulator order, matched by the V^T staging permutation).  Nothing but q, k, v, o touches HBM.
+// (key order inside a 32-block = accumulator order, matched by the two transposing reads of an A fragment).  Nothing but q, k, v, o
+// touches HBM.  Two forms share the chunk body, and so every bit of the result:
+//   resident (STREAM = false): all of K and V staged ONCE per workgroup, Sp * D * 2 * 2 bytes <= 128 KiB -- 512 keys at D = 64,
+//     1024 at D = 32; a wave runs XGPW iterations of 32 queries against them.
+//   streamed (STREAM = true): any number of keys.  128-key chunks of K and V travel through a ring of XNS = 2 stages by LDS-DMA while
+//     the waves compute on the previous chunk, in increasing key order.  The running max, row sums and O^T stay in registers across the
+//     whole key loop, so a wave owns ONE 32-query iteration (XGPW = 1).  A stage is 128 * D * 2 * 2 bytes: the ring is 64 KiB at D = 64
+//     and 32 KiB at D = 32, so the two workgroups per CU of the launch bounds (three at D = 32, where the registers allow it) stay
+//     resident in the CU's 160 KiB.
 __device__ __forceinline__ u32x4 xpack8(const f32x4& a, const f32x4& b) {
   u32x4 f;
   f[0] = pack_bf16x2(a[0], a[1]); f[1] = pack_bf16x2(a[2], a[3]); f[2] = pack_bf16x2(b[0], b[1]); f[3] = pack_bf16x2(b[2], b[3]);
@@ -416,167 +424,235 @@ __device__ __forceinline__ u32x4 xpack8(const f32x4& a, const f32x4& b) {
 __device__ __forceinline__ f32x4 xmfma(const u32x4& a, const u32x4& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
-constexpr int XD = 64;            // head dim
 constexpr int XQG = 2;            // 16-query groups a wave processes together (2: half the LDS reads per MFMA, but 50 more VGPRs)
 constexpr int XWAVES = 4;         // waves per workgroup (measured: XQG 1 with 6 waves = 3 waves/SIMD is 25 % slower than XQG 2 with 4)
 constexpr int XGPW_MAX = 8;       // iterations per wave (32 queries each): 8 where the queries fill the chip anyway (K / V staged once per 1024 queries);
                                   // fewer -- more, shorter workgroups -- for the encoder's few hundred queries per (sample, head)
+constexpr int XRES_BYTES = 128 * 1024;   // the resident form's LDS cap
+constexpr int XNS = 2;                   // ring stages of the streamed form (128 keys of K and of V each)
 
-// V rows are 128 bytes (64 bf16): 16-byte chunk c of row r sits at chunk c ^ (((r >> 1) & 3) << 1), which makes the two 16-lane groups of
-// a half-wave (8 consecutive rows, one aligned chunk pair each) hit 16 distinct 16-byte slots of the 256-byte bank row
-__device__ __forceinline__ int xv_swz(int row) { return ((row >> 1) & 3) << 1; }
-
+// K rows, read by ds_read_b128 with lane (l15, kk) -> row l15, chunk kk (+ 4 per 32-dim block).
+// D = 64: rows are 128 bytes; 16-byte chunk c of row r sits at chunk c ^ ((r >> 1) & 7) (swz_chunk with 8 chunks per row).
+// D = 32: rows are 64 bytes, FOUR rows per 256-byte bank row, so row r owns the four 16-byte slots 4 (r & 3) .. + 3 and rows r, r + 4,
+// r + 8, r + 12 compete for the same four.  A ds_read_b128 is served in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the
+// same + 32, i.e. chunk kk of rows {0-3, 12-15} together with chunk kk ^ 1 of rows {4-11}.  Chunk c of row r sits at c ^ g(r >> 2) with
+// g = (0, 3, 2, 1): in the first group row quarter 0 reads slot 0, quarter 3 slot 1, quarters 1 and 2 slots 1 ^ 3 = 2 and 1 ^ 2 = 3; in
+// the second group quarters 1, 2 read slots 3, 2 and quarters 0, 3 slots 1, 0; the groups of kk = 2, 3 are the same XOR 2.  Every group
+// therefore hits 16 distinct 16-byte slots of the bank row: conflict-free.
+template <int D>
+__device__ __forceinline__ int xk_swz(int row) {
+  if constexpr (D == 64) return (row >> 1) & 7;
+  const int t = (row >> 2) & 3;
+  return t ^ ((t & 1) << 1);
+}
+// V rows, read by ds_read_b64_tr_b16: a half-wave reads 8 consecutive rows, one aligned chunk PAIR (32 bytes, a 16-dim tile) of each.
+// D = 64: 16-byte chunk c of row r sits at chunk c ^ (((r >> 1) & 3) << 1), which makes the two 16-lane groups of a half-wave hit 16
+// distinct 16-byte slots of the 256-byte bank row.
+// D = 32: a row has two chunk pairs and four rows share a bank row, so rows r and r + 4 of the half-wave's eight meet in the same 64
+// bytes; chunk c sits at c ^ (((r >> 2) & 1) << 1), which sends them to opposite pairs: 8 rows x 32 bytes = the 256-byte bank row once.
+// Either swizzle looks only at row bits that the 32-key block offset and the + 16 of an A fragment's second read leave alone.
+template <int D>
+__device__ __forceinline__ int xv_swz(int row) {
+  if constexpr (D == 64) return ((row >> 1) & 3) << 1;
+  return ((row >> 2) & 1) << 1;
+}
+template <int D, bool STREAM>
 __global__ __launch_bounds__(XWAVES * 64, 2) void xattn_mfma_kernel(const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
                                                             const unsigned short* __restrict__ v, unsigned short* __restrict__ o, int n_head,
                                                             int Lq, int Lk, int Sp, long ldq, long ldkv, long ldo, float scale_log2e, long qbr, int XGPW) {
+  constexpr int ROWB = D * 2, CPR = ROWB / 16, RPI = 1024 / ROWB;   // bytes per K / V row, 16-byte chunks per row, rows per wave DMA instruction
+  constexpr int NB = D / 32, ND = D / 16, NS = XNS;              // 32-dim blocks of a K row, 16-dim tiles of O^T, ring stages
   const int XQ_PER_WG = XWAVES * XGPW * 16 * XQG;
-  extern __shared__ __attribute__((aligned(16))) char xsm[];   // K image [Sp][8 chunks] (row reads), then V image [Sp][8 chunks] (transposed reads)
-  char* ks = xsm;
-  char* vs = xsm + (size_t)Sp * XD * 2;
+  extern __shared__ __attribute__((aligned(16))) char xsm[];   // K image [rows][CPR chunks] (row reads), then V image [rows][CPR chunks] (transposed reads);
+  char* ks = xsm;                                              // rows = Sp (resident) or NS stages of 128 (streamed)
+  char* vs = xsm + (size_t)(STREAM ? NS * 128 : Sp) * ROWB;
   const int bh = blockIdx.x, b = bh / n_head, h = bh - b * n_head;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kk = lane >> 4, l15 = lane & 15;
-  // ---- stage K and V row-major by LDS-DMA (no register round trip, no transposing stores): a wave instruction moves 8 rows of 128 bytes;
-  // the swizzles are applied to the SOURCE chunk each lane fetches.  Rows >= Lk re-read row Lk - 1 (their scores are masked below). ----
-  {
-    const int rl = lane >> 3, cs = lane & 7;
-    for (int r0 = wave * 8; r0 < Sp; r0 += XWAVES * 8) {
-      const int row = r0 + rl, src = row < Lk ? row : Lk - 1;
-      const unsigned short* gk = k + ((long)b * Lk + src) * ldkv + (long)h * XD + ((cs ^ ((row >> 1) & 7)) * 8);
-      const unsigned short* gv = v + ((long)b * Lk + src) * ldkv + (long)h * XD + ((cs ^ xv_swz(row)) * 8);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gk, (__attribute__((address_space(3))) void*)(ks + r0 * 128), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gv, (__attribute__((address_space(3))) void*)(vs + r0 * 128), 16, 0, 0);
+  // ---- stage keys key0 .. key0 + nrows - 1 into LDS rows lrow0 .. by LDS-DMA (no register round trip, no transposing stores): a wave
+  // instruction moves RPI rows of ROWB bytes; the swizzles are applied to the SOURCE chunk each lane fetches (key0 and lrow0 are multiples
+  // of 128, so key and LDS row agree in the bits the swizzles read).  Rows >= Lk re-read row Lk - 1 (their scores are masked below). ----
+  auto stage = [&](int key0, int lrow0, int nrows) {
+    const int rl = lane / CPR, cs = lane % CPR;
+    for (int r0 = wave * RPI; r0 < nrows; r0 += XWAVES * RPI) {
+      const int row = key0 + r0 + rl, src = row < Lk ? row : Lk - 1;
+      const unsigned short* gk = k + ((long)b * Lk + src) * ldkv + (long)h * D + ((cs ^ xk_swz<D>(row)) * 8);
+      const unsigned short* gv = v + ((long)b * Lk + src) * ldkv + (long)h * D + ((cs ^ xv_swz<D>(row)) * 8);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gk, (__attribute__((address_space(3))) void*)(ks + (lrow0 + r0) * ROWB), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gv, (__attribute__((address_space(3))) void*)(vs + (lrow0 + r0) * ROWB), 16, 0, 0);
     }
-  }
+  };
+  stage(0, 0, STREAM ? 128 : Sp);
   // per-lane LDS byte addresses; everything that varies with the (compile-time) tile indices is an instruction immediate
-  unsigned kb[2];   // K row l15 of a 16-key tile, 32-dim block bb (row reads, ds_read_b128)
+  unsigned kb[NB];   // K row l15 of a 16-key tile, 32-dim block bb (row reads, ds_read_b128)
 #pragma unroll
-  for (int bb = 0; bb < 2; ++bb) kb[bb] = lds_addr(ks) + l15 * 128 + (swz_chunk(l15, bb * 4 + kk, 8) << 4);
-  // transposed V reads: lane 4 qq + pp of a 16-lane group supplies row (4 kk + qq), columns 4 pp .. 4 pp + 3 of the 16-dim tile dt; the
-  // swizzle only looks at row bits 1-2, which the 32-key block offset and the +16 of the second read leave alone
+  for (int bb = 0; bb < NB; ++bb) kb[bb] = lds_addr(ks) + l15 * ROWB + (((bb * 4 + kk) ^ xk_swz<D>(l15)) << 4);
+  // transposed V reads: lane 4 qq + pp of a 16-lane group supplies row (4 kk + qq), columns 4 pp .. 4 pp + 3 of the 16-dim tile dt
   const int qq = l15 >> 2, pp = l15 & 3;
-  const char* vb[4];
+  const char* vb[ND];
 #pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-    vb[dt] = vs + (4 * kk + qq) * 128 + (((dt * 2 + (pp >> 1)) ^ xv_swz(4 * kk + qq)) << 4) + 8 * (pp & 1);
+  for (int dt = 0; dt < ND; ++dt)
+    vb[dt] = vs + (4 * kk + qq) * ROWB + (((dt * 2 + (pp >> 1)) ^ xv_swz<D>(4 * kk + qq)) << 4) + 8 * (pp & 1);
   const u32x4 ones = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
 
-  // the next iteration's query fragments are fetched while this one computes
-  auto load_q = [&](int it, u32x4 (&dst)[XQG][2]) {
+  auto load_q = [&](int it, u32x4 (&dst)[XQG][NB]) {
     const int q0n = blockIdx.y * XQ_PER_WG + (wave * XGPW + it) * 16 * XQG;
 #pragma unroll
     for (int g = 0; g < XQG; ++g) {
       const int qi = q0n + g * 16 + l15;
       const bool lv = it < XGPW && qi < Lq;
-      const long qoff = ((long)b * qbr + (lv ? qi : 0)) * ldq + (long)h * XD;
+      const long qoff = ((long)b * qbr + (lv ? qi : 0)) * ldq + (long)h * D;
 #pragma unroll
-      for (int bb = 0; bb < 2; ++bb) dst[g][bb] = lv ? *(const u32x4*)(q + qoff + bb * 32 + kk * 8) : u32x4{0u, 0u, 0u, 0u};
+      for (int bb = 0; bb < NB; ++bb) dst[g][bb] = lv ? *(const u32x4*)(q + qoff + bb * 32 + kk * 8) : u32x4{0u, 0u, 0u, 0u};
     }
   };
-  u32x4 qnext[XQG][2];
+  // resident: everything is staged before the first read.  streamed: chunk 0 is in flight; it is retired together with the query loads
+  if constexpr (!STREAM) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+
+  // resident: the next iteration's query fragments are fetched while this one computes
+  u32x4 qnext[XQG][NB];
   load_q(0, qnext);
+  if constexpr (STREAM) {
+    // ---- streamed form (one iteration: XGPW = 1).  Chunk c lives in ring stage c % NS.  Order of one pass of the key loop below:
+    //   (this wave's DMAs of chunk c were retired by the wait that ended pass c - 1, or by the one here)
+    //   barrier       -- every wave has retired its share of chunk c: the stage may be READ; and every wave has finished computing on
+    //                    chunk c - 1, whose LDS reads returned before its MFMAs ran: stage (c - 1) % NS may be OVERWRITTEN
+    //   issue chunk c + 1 into stage (c + 1) % NS = (c - 1) % NS
+    //   compute on chunk c
+    //   counted wait for chunk c + 1: with two stages nothing younger has been issued, so the count is vmcnt(0) -- placed AFTER the
+    //   compute, which is what the DMA overlaps
+    // The barrier is the raw s_barrier: __syncthreads() would drain the DMA queue (an LDS-DMA is a pending LDS write on vmcnt).  No
+    // ordinary global_load result is used while a DMA is outstanding, which would make the compiler wait vmcnt(0) at the use: the query
+    // fragments are loaded once, retired here together with chunk 0, and handed to the loop as results of an asm statement; there is
+    // no next-iteration prefetch.  The compiler still waits vmcnt(0) where it sees an LDS read that an in-flight DMA might alias (the
+    // transposing V reads; the K ring of mfma_stream is inline asm behind its own counted waits), which costs overlap in the second
+    // half of a chunk and nothing in correctness. ----
+    static_assert(NS == 2, "the wait that ends a pass is written for two stages");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int g = 0; g < XQG; ++g)
+#pragma unroll
+      for (int bb = 0; bb < NB; ++bb) asm volatile("" : "+v"(qnext[g][bb]));
+  }
   for (int it = 0; it < XGPW; ++it) {
     const int q0 = blockIdx.y * XQ_PER_WG + (wave * XGPW + it) * 16 * XQG;
-    if (q0 >= Lq) break;
-    u32x4 qf[XQG][2];
+    // wave-uniform.  A streamed wave without queries still stages its rows and meets every barrier; it skips the arithmetic
+    const bool active = q0 < Lq;
+    if constexpr (!STREAM)
+      if (!active) break;
+    u32x4 qf[XQG][NB];
     bool live[XQG];
 #pragma unroll
     for (int g = 0; g < XQG; ++g) {
       live[g] = q0 + g * 16 + l15 < Lq;
 #pragma unroll
-      for (int bb = 0; bb < 2; ++bb) qf[g][bb] = qnext[g][bb];
+      for (int bb = 0; bb < NB; ++bb) qf[g][bb] = qnext[g][bb];
     }
-    load_q(it + 1, qnext);
+    if constexpr (!STREAM) load_q(it + 1, qnext);
     float m[XQG];                           // running max of the RAW scores (the positive scale commutes with max)
-    f32x4 oacc[XQG][4], lacc[XQG];          // lacc: row sums of P by an all-ones MFMA (every row of the tile holds the same sum)
+    f32x4 oacc[XQG][ND], lacc[XQG];         // lacc: row sums of P by an all-ones MFMA (every row of the tile holds the same sum)
 #pragma unroll
     for (int g = 0; g < XQG; ++g) {
       m[g] = -INFINITY;
       lacc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) oacc[g][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int dt = 0; dt < ND; ++dt) oacc[g][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 
+    // one pass = one 128-key chunk, keys c0 .. c0 + 127, held in LDS rows lrow ..
     for (int c0 = 0; c0 < Sp; c0 += 128) {
-      const unsigned kc[2] = {kb[0] + c0 * 128, kb[1] + c0 * 128};
-      f32x4 s[XQG][8];
-      // S^T tiles: 16 K fragments (tile t, dim block bb), each feeding both query groups, through the counted LDS read ring
-      mfma_stream<16, 4>(
-          [&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(i >> 1) * 2048>{kc[i & 1]}; },
-          [&](auto ic, const u32x4& kf) {
-            constexpr int i = decltype(ic)::value, t = i >> 1, bb = i & 1;
+      if constexpr (STREAM) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (c0 + 128 < Sp) stage(c0 + 128, ((c0 >> 7) + 1) % NS * 128, 128);
+      }
+      const int lrow = STREAM ? (c0 >> 7) % NS * 128 : c0;
+      if (!STREAM || active) {
+        unsigned kc[NB];
 #pragma unroll
-            for (int g = 0; g < XQG; ++g) {
-              if constexpr (bb == 0) s[g][t] = xmfma(kf, qf[g][0], f32x4{0.f, 0.f, 0.f, 0.f});
-              else s[g][t] = xmfma(kf, qf[g][1], s[g][t]);
-            }
-          });
-      const bool tail = c0 + 128 > Lk;   // uniform: this chunk holds padded keys
+        for (int bb = 0; bb < NB; ++bb) kc[bb] = kb[bb] + lrow * ROWB;
+        f32x4 s[XQG][8];
+        // S^T tiles: 8 NB K fragments (tile t, dim block bb), each feeding both query groups, through the counted LDS read ring
+        mfma_stream<8 * NB, 4>(
+            [&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(i / NB) * 16 * ROWB>{kc[i % NB]}; },
+            [&](auto ic, const u32x4& kf) {
+              constexpr int i = decltype(ic)::value, t = i / NB, bb = i % NB;
 #pragma unroll
-      for (int g = 0; g < XQG; ++g) {
-        if (tail) {
+              for (int g = 0; g < XQG; ++g) {
+                if constexpr (bb == 0) s[g][t] = xmfma(kf, qf[g][bb], f32x4{0.f, 0.f, 0.f, 0.f});
+                else s[g][t] = xmfma(kf, qf[g][bb], s[g][t]);
+              }
+            });
+        const bool tail = c0 + 128 > Lk;   // uniform: this chunk holds padded keys
+#pragma unroll
+        for (int g = 0; g < XQG; ++g) {
+          if (tail) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t)
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                if (c0 + t * 16 + kk * 4 + r >= Lk) s[g][t][r] = -INFINITY;
+          }
+          float cm = -INFINITY;
+#pragma unroll
+          for (int t = 0; t < 8; ++t) cm = fmaxf(cm, fmaxf(fmaxf(s[g][t][0], s[g][t][1]), fmaxf(s[g][t][2], s[g][t][3])));
+          cm = fmaxf(cm, __shfl_xor(cm, 16));
+          cm = fmaxf(cm, __shfl_xor(cm, 32));
+          const float mn = fmaxf(m[g], cm);
+          const float corr = __builtin_amdgcn_exp2f((m[g] - mn) * scale_log2e);
+          m[g] = mn;
+          const float nm = -mn * scale_log2e;
 #pragma unroll
           for (int t = 0; t < 8; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (c0 + t * 16 + kk * 4 + r >= Lk) s[g][t][r] = -INFINITY;
+            for (int r = 0; r < 4; ++r) s[g][t][r] = __builtin_amdgcn_exp2f(fmaf(s[g][t][r], scale_log2e, nm));   // one fma + one exp per score
+          lacc[g] *= corr;
+#pragma unroll
+          for (int dt = 0; dt < ND; ++dt) oacc[g][dt] *= corr;
         }
-        float cm = -INFINITY;
+        // O^T += V^T P^T per 32-key block.  P's k order inside the block is the accumulator order (keys 16 h + 4 kk + r), so an A fragment
+        // is two transposed reads of 4 keys each; the reads of block blk + 1 are issued before the MFMAs of block blk, which is what lets
+        // the compiler keep them in flight behind counted waits (block offsets are constants: they land in the offset: immediate).
+        const char* vc[ND];
 #pragma unroll
-        for (int t = 0; t < 8; ++t) cm = fmaxf(cm, fmaxf(fmaxf(s[g][t][0], s[g][t][1]), fmaxf(s[g][t][2], s[g][t][3])));
-        cm = fmaxf(cm, __shfl_xor(cm, 16));
-        cm = fmaxf(cm, __shfl_xor(cm, 32));
-        const float mn = fmaxf(m[g], cm);
-        const float corr = __builtin_amdgcn_exp2f((m[g] - mn) * scale_log2e);
-        m[g] = mn;
-        const float nm = -mn * scale_log2e;
+        for (int dt = 0; dt < ND; ++dt) vc[dt] = vb[dt] + lrow * ROWB;
+        u32x2 vlo[2][ND], vhi[2][ND];
 #pragma unroll
-        for (int t = 0; t < 8; ++t)
+        for (int dt = 0; dt < ND; ++dt) { vlo[0][dt] = lds_tr16_b64(vc[dt]); vhi[0][dt] = lds_tr16_b64(vc[dt] + 16 * ROWB); }
+        static_for<4>([&](auto bc) {
+          constexpr int blk = decltype(bc)::value, cur = blk & 1;
+          u32x4 pf[XQG];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) s[g][t][r] = __builtin_amdgcn_exp2f(fmaf(s[g][t][r], scale_log2e, nm));   // one fma + one exp per score
-        lacc[g] *= corr;
+          for (int g = 0; g < XQG; ++g) pf[g] = xpack8(s[g][2 * blk], s[g][2 * blk + 1]);
+          if constexpr (blk < 3) {
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) oacc[g][dt] *= corr;
-      }
-      // O^T += V^T P^T per 32-key block.  P's k order inside the block is the accumulator order (keys 16 h + 4 kk + r), so an A fragment
-      // is two transposed reads of 4 keys each; the reads of block blk + 1 are issued before the MFMAs of block blk, which is what lets
-      // the compiler keep them in flight behind counted waits (block offsets are constants: they land in the offset: immediate).
-      const char* vc[4];
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) vc[dt] = vb[dt] + c0 * 128;
-      u32x2 vlo[2][4], vhi[2][4];
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) { vlo[0][dt] = lds_tr16_b64(vc[dt]); vhi[0][dt] = lds_tr16_b64(vc[dt] + 2048); }
-      static_for<4>([&](auto bc) {
-        constexpr int blk = decltype(bc)::value, cur = blk & 1;
-        u32x4 pf[XQG];
-#pragma unroll
-        for (int g = 0; g < XQG; ++g) pf[g] = xpack8(s[g][2 * blk], s[g][2 * blk + 1]);
-        if constexpr (blk < 3) {
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) {
-            vlo[cur ^ 1][dt] = lds_tr16_b64(vc[dt] + (blk + 1) * 4096);
-            vhi[cur ^ 1][dt] = lds_tr16_b64(vc[dt] + (blk + 1) * 4096 + 2048);
+            for (int dt = 0; dt < ND; ++dt) {
+              vlo[cur ^ 1][dt] = lds_tr16_b64(vc[dt] + (blk + 1) * 32 * ROWB);
+              vhi[cur ^ 1][dt] = lds_tr16_b64(vc[dt] + (blk + 1) * 32 * ROWB + 16 * ROWB);
+            }
           }
-        }
 #pragma unroll
-        for (int g = 0; g < XQG; ++g) lacc[g] = xmfma(ones, pf[g], lacc[g]);
+          for (int g = 0; g < XQG; ++g) lacc[g] = xmfma(ones, pf[g], lacc[g]);
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          const u32x4 vf = u32x4{vlo[cur][dt][0], vlo[cur][dt][1], vhi[cur][dt][0], vhi[cur][dt][1]};
+          for (int dt = 0; dt < ND; ++dt) {
+            const u32x4 vf = u32x4{vlo[cur][dt][0], vlo[cur][dt][1], vhi[cur][dt][0], vhi[cur][dt][1]};
 #pragma unroll
-          for (int g = 0; g < XQG; ++g) oacc[g][dt] = xmfma(vf, pf[g], oacc[g][dt]);
-        }
-      });
+            for (int g = 0; g < XQG; ++g) oacc[g][dt] = xmfma(vf, pf[g], oacc[g][dt]);
+          }
+        });
+      }
+      if constexpr (STREAM) wait_vmcnt<0>();
     }
 #pragma unroll
     for (int g = 0; g < XQG; ++g) {
       const float inv = 1.0f / lacc[g][0];
       if (live[g]) {
-        const long ooff = ((long)b * Lq + q0 + g * 16 + l15) * ldo + (long)h * XD;
+        const long ooff = ((long)b * Lq + q0 + g * 16 + l15) * ldo + (long)h * D;
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {   // lane holds dims 16 dt + 4 kk + r of its query
+        for (int dt = 0; dt < ND; ++dt) {   // lane holds dims 16 dt + 4 kk + r of its query
           u32x2 w;
           w[0] = pack_bf16x2(oacc[g][dt][0] * inv, oacc[g][dt][1] * inv);
           w[1] = pack_bf16x2(oacc[g][dt][2] * inv, oacc[g][dt][3] * inv);
@@ -1366,6 +1442,42 @@ extern "C" int tante_spectral_layer_bwd(const float* x, const float* dy, int64_t
   return 0;
 }
 
+// 0 = the exact VALU kernel, 1 = matrix pipe with K and V resident in LDS, 2 = matrix pipe with K and V streamed through the LDS ring
+extern "C" int tante_cross_attention_route(int dtype, int D, int Lk) {
+  if (dtype != TANTE_BF16 || (D != 32 && D != 64) || Lk <= 0) return 0;
+  if (tante_opt("TANTE_XATTN_VALU", 0) != 0) return 0;
+  if (tante_opt("TANTE_XATTN_STREAM", 0) != 0) return 2;
+  const long Sp = ((long)Lk + 127) / 128 * 128;
+  return Sp * D * 2 * 2 <= XRES_BYTES ? 1 : 2;
+}
+
+template <int D, bool STREAM>
+static int xattn_launch(const void* q, const void* k, const void* v, void* o, int64_t n_batch, int n_head, int Lq, int Lk, int64_t ldq,
+                        int64_t ldkv, int64_t ldo, float scale_log2e, long qbr, hipStream_t s) {
+  const int Sp = ((Lk + 127) / 128) * 128;
+  const size_t lds = STREAM ? (size_t)XNS * 128 * D * 2 * 2 : (size_t)Sp * D * 2 * 2;
+  static size_t attr = 0;
+  if (lds > attr) {
+    hipFuncSetAttribute((const void*)xattn_mfma_kernel<D, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr = lds;
+  }
+  int gpw = 1;   // streamed: the running softmax state of one 32-query iteration fills the registers
+  if (!STREAM) {
+    // iterations per wave: as many as keep >= 512 workgroups in the launch
+    gpw = XGPW_MAX;
+    while (gpw > 1 && n_batch * n_head * (long)((Lq + XWAVES * gpw * 16 * XQG - 1) / (XWAVES * gpw * 16 * XQG)) < 512) gpw >>= 1;
+    gpw = tante_opt("TANTE_XATTN_GPW", gpw);
+    if (gpw < 1 || gpw > 64) TANTE_FAIL(-1, "tante_cross_attention: TANTE_XATTN_GPW = %d out of range", gpw);
+  }
+  const int XQ_PER_WG = XWAVES * gpw * 16 * XQG;
+  if ((Lq + XQ_PER_WG - 1) / XQ_PER_WG > 65535) TANTE_FAIL(-2, "tante_cross_attention: grid too large");
+  const dim3 mgrid((unsigned)(n_batch * n_head), (unsigned)((Lq + XQ_PER_WG - 1) / XQ_PER_WG));
+  hipLaunchKernelGGL((xattn_mfma_kernel<D, STREAM>), mgrid, dim3(XWAVES * 64), lds, s, (const unsigned short*)q, (const unsigned short*)k,
+                     (const unsigned short*)v, (unsigned short*)o, n_head, Lq, Lk, Sp, (long)ldq, (long)ldkv, (long)ldo, scale_log2e, qbr, gpw);
+  TANTE_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int tante_cross_attention(const void* q, const void* k, const void* v, void* o, int dtype, int64_t n_batch, int n_head, int D, int Lq,
                                      int Lk, int64_t ldq, int64_t ldkv, int64_t ldo, void* stream) {
   return tante_cross_attention_q(q, k, v, o, dtype, n_batch, n_head, D, Lq, Lk, ldq, ldkv, ldo, Lq, stream);
@@ -1379,28 +1491,14 @@ extern "C" int tante_cross_attention_q(const void* q, const void* k, const void*
   if ((Lq + 255) / 256 > 65535 || n_batch * n_head > 2147483647L) TANTE_FAIL(-2, "tante_cross_attention: grid too large");
   const float scale = 1.0f / sqrtf((float)D);
   hipStream_t s = (hipStream_t)stream;
-  const bool force_valu = tante_opt("TANTE_XATTN_VALU", 0) != 0;
-  if (dtype == TANTE_BF16 && D == XD && Lk <= 512 && !force_valu && ldq % 8 == 0 && ldkv % 8 == 0 && ldo % 4 == 0 &&
-      ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)o % 8) == 0) {
-    const int Sp = ((Lk + 127) / 128) * 128;
-    const size_t lds = (size_t)Sp * XD * 2 * 2;
-    static size_t attr = 0;
-    if (lds > attr) {
-      hipFuncSetAttribute((const void*)xattn_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr = lds;
-    }
-    // iterations per wave: as many as keep >= 512 workgroups in the launch
-    int gpw = XGPW_MAX;
-    while (gpw > 1 && n_batch * n_head * (long)((Lq + XWAVES * gpw * 16 * XQG - 1) / (XWAVES * gpw * 16 * XQG)) < 512) gpw >>= 1;
-    gpw = tante_opt("TANTE_XATTN_GPW", gpw);
-    if (gpw < 1 || gpw > 64) TANTE_FAIL(-1, "tante_cross_attention: TANTE_XATTN_GPW = %d out of range", gpw);
-    const int XQ_PER_WG = XWAVES * gpw * 16 * XQG;
-    if ((Lq + XQ_PER_WG - 1) / XQ_PER_WG > 65535) TANTE_FAIL(-2, "tante_cross_attention: grid too large");
-    const dim3 mgrid((unsigned)(n_batch * n_head), (unsigned)((Lq + XQ_PER_WG - 1) / XQ_PER_WG));
-    hipLaunchKernelGGL(xattn_mfma_kernel, mgrid, dim3(XWAVES * 64), lds, s, (const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v,
-                       (unsigned short*)o, n_head, Lq, Lk, Sp, (long)ldq, (long)ldkv, (long)ldo, scale * 1.44269504088896340736f, qbr, gpw);
-    TANTE_CHECK_LAUNCH();
-    return 0;
+  const int route = tante_cross_attention_route(dtype, D, Lk);
+  if (route != 0 && ldq % 8 == 0 && ldkv % 8 == 0 && ldo % 4 == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 &&
+      ((uintptr_t)v % 16) == 0 && ((uintptr_t)o % 8) == 0) {
+    const float sl2 = scale * 1.44269504088896340736f;
+    if (D == 64) return route == 1 ? xattn_launch<64, false>(q, k, v, o, n_batch, n_head, Lq, Lk, ldq, ldkv, ldo, sl2, qbr, s)
+                                   : xattn_launch<64, true>(q, k, v, o, n_batch, n_head, Lq, Lk, ldq, ldkv, ldo, sl2, qbr, s);
+    return route == 1 ? xattn_launch<32, false>(q, k, v, o, n_batch, n_head, Lq, Lk, ldq, ldkv, ldo, sl2, qbr, s)
+                      : xattn_launch<32, true>(q, k, v, o, n_batch, n_head, Lq, Lk, ldq, ldkv, ldo, sl2, qbr, s);
   }
   const dim3 grid((unsigned)(n_batch * n_head), (unsigned)((Lq + 255) / 256));
 #define TANTE_XA(DD) hipLaunchKernelGGL(cross_attn_kernel<DD>, grid, dim3(256), 0, s, q, k, v, o, dtype, n_head, Lq, Lk, (long)ldq, (long)ldkv, (long)ldo, scale, qbr)

@@ -824,7 +824,8 @@ def spectral_layer(x: torch.Tensor, w_re: torch.Tensor, w_im: torch.Tensor, mode
 def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, n_batch: int, n_head: int, D: int, Lq: int, Lk: int,
                     ldq: int, ldkv: int, ldo: int, shared_q: bool = False):
     """k and v may be views into one packed (…, 2C) buffer: rows are addressed by data_ptr + strides.  shared_q: q holds Lq rows that every
-    sample attends with (the decoder's coordinate queries)."""
+    sample attends with (the decoder's coordinate queries).  bf16 with D = 32 or 64 runs on the matrix pipe for any Lk
+    (cross_attention_route), everything else on the exact lane-per-query kernel."""
     if not (q.is_cuda and k.is_cuda and v.is_cuda and o.is_cuda):
         raise RuntimeError("tante_amd kernels need CUDA/HIP tensors (no CPU fallback)")
     if not (q.dtype == k.dtype == v.dtype == o.dtype):
@@ -832,6 +833,16 @@ def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.
     L.check(L.lib().tante_cross_attention_q(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), _DT[q.dtype], n_batch, n_head, D, Lq, Lk, ldq,
                                             ldkv, ldo, 0 if shared_q else Lq, _stream()), "tante_cross_attention")
     return o
+
+
+_XATTN_ROUTES = ("valu", "resident", "stream")
+
+
+def cross_attention_route(dtype: torch.dtype, D: int, Lk: int) -> str:
+    """The kernel cross_attention takes for aligned operands (tante_cross_attention_route): "valu" = the exact lane-per-query kernel,
+    "resident" = matrix pipe with K and V staged once in LDS (bf16, up to 512 keys at D = 64 and 1024 at D = 32), "stream" = matrix pipe
+    with K and V streamed through an LDS ring (bf16, D = 32 or 64, beyond that).  Follows TANTE_XATTN_VALU and TANTE_XATTN_STREAM."""
+    return _XATTN_ROUTES[L.lib().tante_cross_attention_route(_DT[dtype], int(D), int(Lk))]
 
 
 # ---- CViT blocks at width 512 in one launch (cvit_fused.hip) ------------------------------------------------------------------------
