@@ -422,14 +422,20 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const TanteGemm g, int n_t
       float v[CB][E];
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb) load_chunk_any<AM, E>(g, ri, (cb * 4 + kk) * E, a_vec, v[cb]);
+      // sums of (x - pivot), the pivot the row's first element (lane l15 holds it): a mean that is itself rounded to fp32 is off by up
+      // to half a unit in its last place, which for rows far from 0 (mean 1e3, unit spread) was 3e-5 of the spread in every element
+      const float piv = __shfl(v[0][0], l15);
       float s = 0.0f;
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
-        for (int i = 0; i < E; ++i) s += v[cb][i];
+        for (int i = 0; i < E; ++i) {
+          v[cb][i] = ((cb * 4 + kk) * E + i < g.K) ? v[cb][i] - piv : 0.0f;
+          s += v[cb][i];
+        }
       s += __shfl_xor(s, 16);
       s += __shfl_xor(s, 32);
-      const float mean = s / (float)g.K;
+      const float mean = s / (float)g.K;      // of the shifted row
       float q = 0.0f;
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb)
@@ -568,11 +574,15 @@ __global__ __launch_bounds__(64) void gemm_small_kernel(const TanteGemm g) {
     float v[CB][E];
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) load_chunk_fast_lin<E>(g, ri, (cb * 4 + kk) * E, v[cb]);
+    const float piv = __shfl(v[0][0], l15);      // as in gemm_kernel: the row shifted by its first element before it is summed
     float s = 0.0f;
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
-      for (int i = 0; i < E; ++i) s += v[cb][i];
+      for (int i = 0; i < E; ++i) {
+        v[cb][i] -= piv;
+        s += v[cb][i];
+      }
     s += __shfl_xor(s, 16);
     s += __shfl_xor(s, 32);
     const float mean = s / (float)g.K;

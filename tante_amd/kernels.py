@@ -93,10 +93,11 @@ def _run(g: L.Gemm):
 def linear(a: torch.Tensor, pw: PackedWeight = None, out: torch.Tensor = None, *, M: Optional[int] = None, act: int = L.ACT_NONE,
            ln: bool = False, ln_eps: float = 1e-5, residual: Optional[torch.Tensor] = None,
            a_n0: Optional[int] = None, a_s1: int = 0, a_s0: Optional[int] = None, a_off: int = 0,
-           out_ld: Optional[int] = None, drop_p: float = 0.0, drop_seed: int = 0, dact: Optional[torch.Tensor] = None,
-           dact_kind: int = L.ACT_NONE):
+           out_ld: Optional[int] = None, res_ld: Optional[int] = None, drop_p: float = 0.0, drop_seed: int = 0,
+           dact: Optional[torch.Tensor] = None, dact_kind: int = L.ACT_NONE):
     """out[M, N] = act(norm?(rows(a)) @ W^T + b) (+ residual).  Row r of `a` starts at element
-    (r // a_n0) * a_s1 + (r % a_n0) * a_s0 + a_off  (default: dense rows of length K).
+    (r // a_n0) * a_s1 + (r % a_n0) * a_s0 + a_off  (default: dense rows of length K).  Row r of `out` starts at r * out_ld (default N),
+    row r of `residual` at r * res_ld: by default out_ld when the residual IS `out` (in place on the residual stream), else N.
     Training epilogues (see TanteGemm in include/tante_hip.h): drop_p > 0 drops the product before the residual is added;
     dact multiplies it by act'(dact) (an (M, N) pre-activation tensor)."""
     K = pw.K
@@ -112,7 +113,9 @@ def linear(a: torch.Tensor, pw: PackedWeight = None, out: torch.Tensor = None, *
         _dev(residual)
         if residual.dtype != torch.float32:
             raise RuntimeError("residual stream is fp32")
-        g.residual, g.res_ld = _p(residual), pw.N
+        if res_ld is None:
+            res_ld = g.out_ld if residual.data_ptr() == out.data_ptr() else pw.N
+        g.residual, g.res_ld = _p(residual), res_ld
     if drop_p > 0.0:
         g.drop_p, g.drop_seed = float(drop_p), int(drop_seed)
     if dact is not None:
