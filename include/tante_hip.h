@@ -574,6 +574,28 @@ int tante_cross_attention_q(const void* q, const void* k, const void* v, void* o
  * resident in LDS, 2 = matrix pipe with K and V streamed through the LDS ring.  Options: TANTE_XATTN_VALU = 1 forces 0;
  * TANTE_XATTN_STREAM = 1 forces 2 wherever the matrix pipe applies.  Added without an ABI bump (nothing that existed changed). */
 int tante_cross_attention_route(int dtype, int D, int Lk);
+
+/* ---- AFNO spectral filter (afno_filter.hip; added without an ABI bump: nothing that existed changed) ----
+ * AFNO_ND.forward (afno.py:103-117) with the complex block MLP (ComplexBlockLinear / RealImagGELU, afno.py:17-49), the axis swap and the
+ * first skip of Block.forward (afno.py:154-159), on channels-last fp32 rows x (B, H, W, C):
+ *   out[h, w] = residual[h, w] + irfftn(softshrink(W2 . gelu(W1 . rfftn(x, dim=(2, 1))), lambda), s=(H, W), dim=(2, 1))[w, h]
+ * kept as the reference computes it: the half spectrum is taken over axis 1 (H), and the inverse gets the SWAPPED sizes (an H-point
+ * inverse over the first min(W, H) entries of axis 2, a W-point complex-to-real inverse over the first min(H/2+1, W/2+1) entries of
+ * axis 1), which crops or zero-pads the spectrum when H != W.  Three launches of fp32 MFMA products against twiddle tables, fp32 in both
+ * compute modes (afno.py:105).  Served: 1 <= H, W <= 64, block size bs <= 64, C a multiple of bs, B <= 65535 -- _supported says so, the
+ * call returns -2 with the reason in the last-error string otherwise.
+ *   twiddles: the four tables T1 (Lc, W) = e^{-2 pi i l w / W} / sqrt(W), T2 (Kc, H) = e^{-2 pi i k h / H} / sqrt(H),
+ *     T3 (W, Kc) = c_k e^{+2 pi i k w / W} / sqrt(W), T4 (H, Lc) = e^{+2 pi i l h / H} / sqrt(H), Lc = min(H, W), Kc = min(H/2+1, W/2+1),
+ *     c_k = 1 for k = 0 and k = W/2 (W even), else 2; each as a real plane then an imaginary plane, row-major, rows zero padded to a
+ *     multiple of 16 and columns to a multiple of 4, back to back: _twiddle_floats(H, W) floats in all (-1: unsupported grid).
+ *   w1, w2: per channel block g the real-ified (2 bsP, 2 bsP) matrix [[Wr, Wi], [-Wi, Wr]] (row = input, column = output; real parts at
+ *     0.., imaginary parts at bsP..; bsP = bs rounded up to 16, zero padded), row-major, blocks back to back.
+ *   residual: (B, H, W, C) or NULL; out may alias residual, not x.  work: _workspace_bytes(B, H, W, C) bytes, 16-byte aligned. */
+int tante_afno_filter_supported(int64_t B, int H, int W, int C, int bs);
+int64_t tante_afno_twiddle_floats(int H, int W);
+int64_t tante_afno_filter_workspace_bytes(int64_t B, int H, int W, int C);
+int tante_afno_filter(const float* x, const float* residual, int64_t B, int H, int W, int C, int bs, const float* twiddles, const float* w1,
+                      const float* w2, float lambda, float* out, void* work, int64_t work_bytes, void* stream);
 /* Backward of tante_cross_attention.  o is the forward output; dq gets the query gradient in the layout of q; the key / value gradients
  * are ADDED (fp32 atomics) to dk / dv, rows (b, j) at (b*Lk + j)*ldg + h*D -- zero them first.  stats: n_batch*n_head*Lq*3 floats of
  * scratch (softmax max, 1 / sum, dO . O per query). */

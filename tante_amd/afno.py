@@ -1,0 +1,373 @@
+"""AFNO baseline on the HIP kernels  (reference models/afno.py, configs/afno.yaml: the adaptive Fourier neural operator of FourCastNet).
+
+Same constructor arguments, attributes, `state_dict` keys / shapes and forward contract (`b t c h w -> b 1 c h w`, so the sliding-window
+rollout re-feeds it one frame per call) as the reference's models.AFNO.  Every arithmetic step is a C-ABI call of libtante_hip:
+tante_im2col + chunked tante_gemm (the Conv2d patch embed, with the positional embedding riding the GEMM's residual operand),
+tante_layernorm_affine (norm1), tante_afno_filter (the spectral filter, its axis swap and the first skip), tante_gemm with LayerNorm 2
+folded in + erf GELU, chunked tante_gemm with the second skip as the residual, and the transposed-conv de-embedding as one scatter GEMM.
+torch allocates and reshapes.
+
+Reference quirks kept on purpose (pinned by the g18 fixtures):
+  * the filter transforms over dim=(2, 1): the HALF spectrum is taken over axis 1 (H), the full transform over axis 2 (W)  (afno.py:106);
+  * the inverse receives s=resolution against those reversed axes, i.e. the SWAPPED sizes -- for H != W a frequency crop / zero pad --
+    and returns (b, W, H, C), which Block.forward swaps back  (afno.py:113-115, 155);
+  * ComplexBlockLinear takes `bias=True` and creates no bias  (afno.py:22-44); the filter runs in fp32 also under autocast (l.105);
+  * a freshly initialised filter is identically zero on unit-variance input: weights of scale 0.02 against a soft threshold of 0.01.
+
+Inference only (eval mode under no_grad).  Training, dropout / drop-path in train() and n_spatial_dims = 3 raise NotImplementedError;
+there is no CPU fallback."""
+from __future__ import annotations
+
+from functools import partial
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib as L
+from . import kernels as K
+from . import stages as S
+from .attn_backbone import _PackCache, resolve_compute
+
+MAX_GRID = 64     # token-grid points per axis the filter kernels serve
+MAX_BLOCK = 64    # channels per diagonal block
+
+
+def _r(n: int, m: int) -> int:
+    return (n + m - 1) // m * m
+
+
+# ---- host side of tante_afno_filter: the predicate's mirror, the twiddle tables, the real-ified weights ---------------------------------
+def filter_supported_py(B: int, H: int, W: int, C_: int, bs: int) -> bool:
+    """Python mirror of tante_afno_filter_supported."""
+    return (1 <= H <= MAX_GRID and 1 <= W <= MAX_GRID and 1 <= bs <= MAX_BLOCK and C_ >= 1 and C_ % bs == 0 and 0 <= B <= 65535)
+
+
+def filter_supported(B: int, H: int, W: int, C_: int, bs: int) -> bool:
+    return bool(L.lib().tante_afno_filter_supported(B, H, W, C_, bs))
+
+
+def kept_modes(H: int, W: int) -> Tuple[int, int]:
+    """(Lc, Kc): the entries of axis 2 / axis 1 of the spectrum that the swapped-size inverse reads."""
+    return min(H, W), min(H // 2 + 1, W // 2 + 1)
+
+
+def _cis(num: np.ndarray, n: int, sign: int) -> np.ndarray:
+    """e^{sign 2 pi i num / n} in float64 with the angle reduced in integers (so the entries that are real / imaginary are exactly so)."""
+    m = np.mod(num, n).astype(np.float64)
+    z = np.cos(2.0 * np.pi * m / n) + sign * 1j * np.sin(2.0 * np.pi * m / n)
+    z.real[np.abs(z.real) < 1e-15] = 0.0
+    z.imag[np.abs(z.imag) < 1e-15] = 0.0
+    return z
+
+
+def twiddle_tables(H: int, W: int) -> List[np.ndarray]:
+    """The four complex128 tables of tante_afno_filter (include/tante_hip.h), unpadded: T1 (Lc, W), T2 (Kc, H), T3 (W, Kc), T4 (H, Lc)."""
+    Lc, Kc = kept_modes(H, W)
+    l, k, w, h = np.arange(Lc), np.arange(Kc), np.arange(W), np.arange(H)
+    ck = np.where((k == 0) | ((W % 2 == 0) & (k == W // 2)), 1.0, 2.0)
+    return [_cis(np.outer(l, w), W, -1) / np.sqrt(W), _cis(np.outer(k, h), H, -1) / np.sqrt(H),
+            _cis(np.outer(w, k), W, +1) * ck[None, :] / np.sqrt(W), _cis(np.outer(h, l), H, +1) / np.sqrt(H)]
+
+
+def pack_twiddles(H: int, W: int) -> np.ndarray:
+    """-> the float32 buffer tante_afno_filter reads: per table a real then an imaginary plane, rows padded to 16, columns to 4."""
+    planes = []
+    for t in twiddle_tables(H, W):
+        p = np.zeros((2, _r(t.shape[0], 16), _r(t.shape[1], 4)), dtype=np.float32)
+        p[0, :t.shape[0], :t.shape[1]] = t.real
+        p[1, :t.shape[0], :t.shape[1]] = t.imag
+        planes.append(p.reshape(-1))
+    return np.concatenate(planes)
+
+
+def pack_block_weight(weight: torch.Tensor) -> torch.Tensor:
+    """ComplexBlockLinear.weight (n_blocks, bs, bs, 2) -> the real-ified (n_blocks, 2 bsP, 2 bsP) fp32 matrices [[Wr, Wi], [-Wi, Wr]]
+    ([Re | Im] . M = [Re Wr - Im Wi | Re Wi + Im Wr]), bsP = bs rounded up to 16, zero padded."""
+    w = weight.detach().to(torch.float32)
+    nb, bs = w.shape[0], w.shape[1]
+    bp = _r(bs, 16)
+    m = torch.zeros(nb, 2 * bp, 2 * bp, dtype=torch.float32, device=w.device)
+    wr, wi = w[..., 0], w[..., 1]
+    m[:, :bs, :bs] = wr
+    m[:, :bs, bp:bp + bs] = wi
+    m[:, bp:bp + bs, :bs] = -wi
+    m[:, bp:bp + bs, bp:bp + bs] = wr
+    return m.contiguous()
+
+
+_TWIDDLES = {}     # (H, W, device) -> packed tables on the device: weight independent, built once per shape
+
+
+def _twiddles(H: int, W: int, device) -> torch.Tensor:
+    key = (H, W, str(device))
+    t = _TWIDDLES.get(key)
+    if t is None:
+        host = pack_twiddles(H, W)
+        n = int(L.lib().tante_afno_twiddle_floats(H, W))
+        if n != host.size:
+            raise RuntimeError(f"twiddle tables for a {H} x {W} grid: {host.size} floats packed, the library expects {n}")
+        t = torch.from_numpy(host).to(device)
+        _TWIDDLES[key] = t
+    return t
+
+
+def afno_filter(x: torch.Tensor, residual: Optional[torch.Tensor], w1: torch.Tensor, w2: torch.Tensor, bs: int, lam: float,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tante_afno_filter on x (B, H, W, C) fp32 channels-last: residual + swap_hw(filter(x)); w1 / w2 from pack_block_weight."""
+    K._dev(x, residual, w1, w2, out)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError("the AFNO filter takes fp32 channels-last rows (B, H, W, C)")
+    B, H, W, C_ = x.shape
+    lib = L.lib()
+    if not lib.tante_afno_filter_supported(B, H, W, C_, bs):
+        # the call itself refuses with the reason; made here without touching the device
+        L.check(lib.tante_afno_filter(None, None, B, H, W, C_, bs, None, None, None, float(lam), None, None, 0, None), "tante_afno_filter")
+    if out is None:
+        out = torch.empty_like(x)
+    nbytes = int(lib.tante_afno_filter_workspace_bytes(B, H, W, C_))
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    L.check(lib.tante_afno_filter(K._p(x), K._p(residual), B, H, W, C_, bs, K._p(_twiddles(H, W, x.device)), K._p(w1), K._p(w2), float(lam),
+                                  K._p(out), K._p(work), nbytes, K._stream()), "tante_afno_filter")
+    return out
+
+
+# ---- the reference's modules -------------------------------------------------------------------------------------------------------
+class RealImagGELU(nn.Module):
+    """gelu(Re) + i gelu(Im)  (afno.py:17-19): evaluated inside tante_afno_filter."""
+
+
+class ComplexBlockLinear(nn.Module):
+    """Block-diagonal complex linear layer, no bias  (afno.py:22-49): the weight of one layer of tante_afno_filter's MLP."""
+
+    def __init__(self, hidden_dim, bias=True, cmlp_diagonal_blocks=8):
+        super().__init__()
+        self.scale = 0.02
+        self.hidden_dim = hidden_dim
+        self.cmlp_diagonal_blocks = cmlp_diagonal_blocks
+        self.block_size = self.hidden_dim // self.cmlp_diagonal_blocks
+        self.weight = nn.Parameter(torch.view_as_real(self.scale * torch.randn(cmlp_diagonal_blocks, self.block_size, self.block_size,
+                                                                                dtype=torch.cfloat)))
+
+
+class Mlp(nn.Module):
+    """fc2(gelu_erf(fc1(x)))  (afno.py:52-75)."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.0):
+        super().__init__()
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        self.fc1 = nn.Linear(in_features, hidden_features)
+        self.act = act_layer()
+        self.fc2 = nn.Linear(hidden_features, out_features)
+        self.drop = nn.Dropout(drop)
+
+
+class AFNO_ND(nn.Module):
+    """The spectral filter  (afno.py:78-117)."""
+
+    def __init__(self, hidden_size: int, resolution, cmlp_diagonal_blocks=8, sparsity_threshold=0.01):
+        super().__init__()
+        assert hidden_size % cmlp_diagonal_blocks == 0, \
+            f"hidden_size {hidden_size} should be divisble by cmlp_diagonal_blocks {cmlp_diagonal_blocks}"
+        self.resolution = resolution
+        self.hidden_size = hidden_size
+        self.sparsity_threshold = sparsity_threshold
+        self.cmlp_diagonal_blocks = cmlp_diagonal_blocks
+        self.scale = 0.02
+        self.cmlp = nn.Sequential(ComplexBlockLinear(hidden_size, cmlp_diagonal_blocks=cmlp_diagonal_blocks), RealImagGELU(),
+                                  ComplexBlockLinear(hidden_size, cmlp_diagonal_blocks=cmlp_diagonal_blocks))
+        self._cache = _PackCache()
+
+    def _packed(self):
+        ws = [self.cmlp[0].weight, self.cmlp[2].weight]
+        return self._cache.get(0, ws, lambda: tuple(pack_block_weight(w) for w in ws))
+
+    def run(self, x: torch.Tensor, residual: Optional[torch.Tensor]) -> torch.Tensor:
+        """x (B, H, W, C) fp32 -> swap_hw(filter(x)) (+ residual): the (B, H, W, C) stream Block.forward holds after its first skip."""
+        w1, w2 = self._packed()
+        return afno_filter(x, residual, w1, w2, self.hidden_size // self.cmlp_diagonal_blocks, self.sparsity_threshold)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """(b, H, W, C) -> (b, W, H, C), as the reference returns it (afno.py:103-117).  Inference only."""
+        _inference_only(self)
+        if x.dim() != 4:
+            raise NotImplementedError("the AFNO filter is two-dimensional here: n_spatial_dims = 3 is out of scope")
+        _gpu(x)
+        return self.run(x.detach().to(torch.float32).contiguous(), None).transpose(1, 2).to(x.dtype)
+
+
+class Block(nn.Module):
+    """x = swap_hw(filter(norm1 x)) + x;  x = mlp(norm2 x) + x   (afno.py:120-166)."""
+
+    def __init__(self, hidden_dim, resolution, mlp_ratio=4.0, drop=0.0, drop_path=0.0, act_layer=nn.GELU, norm_layer=nn.LayerNorm,
+                 double_skip=True, cmlp_diagonal_blocks=8, sparsity_threshold=0.01):
+        super().__init__()
+        self.norm1 = norm_layer(hidden_dim)
+        self.filter = AFNO_ND(hidden_dim, resolution, cmlp_diagonal_blocks, sparsity_threshold)
+        self.drop_path = nn.Identity()
+        self.drop_path_rate = float(drop_path)
+        self.norm2 = norm_layer(hidden_dim)
+        mlp_hidden_dim = int(hidden_dim * mlp_ratio)
+        self.mlp = Mlp(in_features=hidden_dim, hidden_features=mlp_hidden_dim, act_layer=act_layer, drop=drop)
+        self.double_skip = double_skip
+        self.hidden_dim = hidden_dim
+        self._cache = _PackCache()
+
+    def _packed(self, compute: int):
+        n2, m = self.norm2, self.mlp
+        params = [n2.weight, n2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias]
+        return self._cache.get(compute, params, lambda: dict(
+            fc1_ln2=K.pack_weight(m.fc1.weight, m.fc1.bias, compute, gamma=n2.weight, beta=n2.bias),
+            fc2=S.pack_linear_chunks(m.fc2.weight.detach(), m.fc2.bias, compute)))
+
+    def run(self, x: torch.Tensor, compute: int) -> torch.Tensor:
+        """x (B, H, W, C) fp32 -> block(x), same shape."""
+        B, H, W, C_ = x.shape
+        M = B * H * W
+        pk = self._packed(compute)
+        n1 = K.layernorm_affine(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)
+        if self.double_skip:
+            x1 = self.filter.run(n1, x)              # the filter's store epilogue adds the first skip
+            skip = x1
+        else:
+            x1 = self.filter.run(n1, None)
+            skip = x
+        h = torch.empty(M, pk["fc1_ln2"].N, dtype=K.act_torch_dtype(compute), device=x.device)
+        K.linear(x1.view(M, C_), pk["fc1_ln2"], h, M=M, act=L.ACT_GELU_ERF, ln=True, ln_eps=self.norm2.eps)
+        y = torch.empty(M, C_, dtype=torch.float32, device=x.device)
+        k0, Kt = 0, h.shape[1]
+        for i, pw in enumerate(pk["fc2"]):           # K-chunks accumulate through the residual operand; the first one carries the skip
+            K.linear(h, pw, y, M=M, a_n0=M, a_s0=Kt, a_off=k0, residual=skip.view(M, C_) if i == 0 else y)
+            k0 += pw.K
+        return y.view(B, H, W, C_)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        _inference_only(self)
+        if x.dim() != 4:
+            raise NotImplementedError("the AFNO block is two-dimensional here: n_spatial_dims = 3 is out of scope")
+        _gpu(x)
+        return self.run(x.detach().to(torch.float32).contiguous(), resolve_compute(None))
+
+
+def _gpu(x: torch.Tensor):
+    if not x.is_cuda:
+        raise RuntimeError("tante_amd.AFNO runs on the GPU only (no CPU fallback); move the model and its input to cuda")
+
+
+def _inference_only(module: nn.Module):
+    if torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()):
+        raise NotImplementedError("tante_amd.AFNO is inference only: training is out of scope (the filter's backward is a kernel of its own "
+                                  "that is not built); call it in eval mode under torch.no_grad()")
+
+
+class AFNO(nn.Module):
+    """models/afno.py:169-278 -- same constructor, attributes, parameters and forward contract."""
+
+    def __init__(self, in_T, dset_metadata=None, hidden_dim=256, n_blocks=12, cmlp_diagonal_blocks=8, patch_size=8, mlp_ratio=4.0,
+                 drop_rate=0.0, drop_path_rate=0.0, sparsity_threshold=0.01):
+        super().__init__()
+        n_channel = dset_metadata.n_fields if dset_metadata else 5
+        dim_in = n_channel * in_T
+        dim_out = n_channel
+        self.dim_in = dim_in
+        self.dim_out = dim_out
+        self.resolution = dset_metadata.spatial_resolution if dset_metadata else (128, 384)
+        self.n_spatial_dims = dset_metadata.n_spatial_dims if dset_metadata else 2
+        self.n_blocks = n_blocks
+        self.cmlp_diagonal_blocks = cmlp_diagonal_blocks
+        self.in_T, self.hidden_dim, self.patch_size = in_T, hidden_dim, patch_size
+        self.drop_rate, self.drop_path_rate = float(drop_rate), float(drop_path_rate)
+        norm_layer = partial(nn.LayerNorm, eps=1e-6)
+        if self.n_spatial_dims == 3:
+            raise NotImplementedError("AFNO with n_spatial_dims = 3 is out of scope: the HIP filter is two-dimensional (no dataset of the "
+                                      "reference is 3-D)")
+        if self.n_spatial_dims != 2 or len(self.resolution) != 2:
+            raise ValueError(f"n_spatial_dims must be 2, got {self.n_spatial_dims} with resolution {tuple(self.resolution)}")
+        self.patch_embed = nn.Conv2d(dim_in, hidden_dim, kernel_size=patch_size, stride=patch_size)
+        self.embed_permutation = ["b h w c -> b c h w", "b c h w -> b h w c"]
+        self.patch_debed = nn.ConvTranspose2d(hidden_dim, dim_out, kernel_size=patch_size, stride=patch_size)
+        self.inner_size = [k // patch_size for k in self.resolution]
+        self.pos_embed = nn.Parameter(0.02 * torch.randn([1] + self.inner_size + [hidden_dim]))
+        self.pos_drop = nn.Dropout(p=drop_rate)
+        dpr = [x.item() for x in torch.linspace(0, drop_path_rate, n_blocks)]
+        self.blocks = nn.ModuleList([Block(hidden_dim=hidden_dim, resolution=self.inner_size, mlp_ratio=mlp_ratio, drop=drop_rate,
+                                           drop_path=dpr[i], norm_layer=norm_layer, cmlp_diagonal_blocks=self.cmlp_diagonal_blocks,
+                                           sparsity_threshold=sparsity_threshold) for i in range(n_blocks)])
+        self.apply(self._init_weights)
+        self.output_length = 1
+        self.compute: Optional[str] = None
+        self._cache = _PackCache()
+        self._pos = _PackCache()
+
+    def _init_weights(self, m):
+        if isinstance(m, nn.Linear):
+            torch.nn.init.trunc_normal_(m.weight, std=0.02)
+            if m.bias is not None:
+                nn.init.constant_(m.bias, 0)
+        elif isinstance(m, nn.LayerNorm):
+            nn.init.constant_(m.bias, 0)
+            nn.init.constant_(m.weight, 1.0)
+
+    @torch.jit.ignore
+    def no_weight_decay(self):
+        return {"pos_embed", "cls_token"}
+
+    def set_compute(self, mode: Optional[str]):
+        if mode is not None and mode not in K.COMPUTE:
+            raise ValueError("compute must be None, 'fp32' or 'bf16'")
+        self.compute = mode
+        return self
+
+    def _packed(self, compute: int):
+        pe, pd = self.patch_embed, self.patch_debed
+        p = self.patch_size
+        return self._cache.get(compute, [pe.weight, pe.bias, pd.weight, pd.bias], lambda: (
+            S.pack_linear_chunks(pe.weight.detach().reshape(pe.weight.shape[0], -1), pe.bias, compute),
+            K.pack_weight(pd.weight, pd.bias, compute, L.W_DECONV_NCHW, N=pd.weight.shape[1] * p * p, K=pd.weight.shape[0], P=p,
+                          C_other=pd.weight.shape[1])))
+
+    def forward_features(self, x: torch.Tensor, compute: int) -> torch.Tensor:
+        """x (b, t c, h, w) fp32 contiguous -> tokens (b, H', W', C) fp32  (afno.py:257-268)."""
+        b, cin, h, w = x.shape
+        p, C_ = self.patch_size, self.hidden_dim
+        Hp, Wp = h // p, w // p
+        M = b * Hp * Wp
+        chunks, _ = self._packed(compute)
+        cols = K.im2col(x, True, b, cin, h, w, p, p, p, p, 0, 0, 0, K.act_torch_dtype(compute))
+        # x + pos_embed: the embedding's rows, repeated per sample, are the residual the first K-chunk accumulates onto
+        pos = self._pos.get(b, [self.pos_embed], lambda: self.pos_embed.detach().expand(b, -1, -1, -1).reshape(M, C_).contiguous())
+        y = torch.empty(M, C_, dtype=torch.float32, device=x.device)
+        k0, Kt = 0, cols.shape[1]
+        for i, pw in enumerate(chunks):
+            K.linear(cols, pw, y, M=M, a_n0=M, a_s0=Kt, a_off=k0, residual=pos if i == 0 else y)
+            k0 += pw.K
+        y = y.view(b, Hp, Wp, C_)
+        for blk in self.blocks:
+            y = blk.run(y, compute)
+        return y
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x (b, t, c, h, w) -> (b, 1, c, h, w)   (afno.py:270-278)."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("tante_amd.AFNO is inference only: training is out of scope (the filter's backward is a kernel of its "
+                                      "own that is not built); call it in eval mode under torch.no_grad()")
+        if self.training and (self.drop_rate > 0.0 or self.drop_path_rate > 0.0):
+            raise NotImplementedError("drop_rate / drop_path_rate > 0 in train() is out of scope: dropout and stochastic depth belong to the "
+                                      "training path, which is not built; call .eval()")
+        if x.dim() != 5 or x.shape[1] * x.shape[2] != self.dim_in:
+            raise ValueError(f"expected (B, {self.in_T}, {self.dim_out}, H, W), got {tuple(x.shape)}")
+        _gpu(x)
+        b, t, c, h, w = x.shape
+        p = self.patch_size
+        if [h // p, w // p] != list(self.inner_size) or h % p or w % p:
+            raise ValueError(f"input {h} x {w} does not give the {tuple(self.inner_size)} token grid of pos_embed at patch size {p}")
+        compute = resolve_compute(self.compute)
+        x = x.detach().to(torch.float32).contiguous().view(b, t * c, h, w)       # 'b t c h w -> b (t c) h w' (the conv's channel order)
+        y = self.forward_features(x, compute)
+        _, pd = self._packed(compute)
+        Hp, Wp = self.inner_size
+        out = torch.empty(b, self.dim_out, h, w, dtype=torch.float32, device=x.device)
+        K.deconv(y.view(b * Hp * Wp, self.hidden_dim), pd, out, n_img=b, Hi=Hp, Wi=Wp, P=p, Cout=self.dim_out, nchw_out=True, act=L.ACT_NONE)
+        return out.unsqueeze(1)                                                  # 'b c h w -> b 1 c h w'

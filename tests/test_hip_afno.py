@@ -1,0 +1,171 @@
+"""GPU: the AFNO baseline -- tante_afno_filter alone against the reference's filter fixtures (relative to the FILTER's output: added to a
+unit-scale stream a 10 % filter error would vanish), the whole model and a re-fed rollout against the reference / its float64
+restatement, and the out-of-scope cases."""
+import contextlib
+
+import pytest
+import torch
+
+import afno_ref as R
+from conftest import load_golden, max_rel, record_parity, rel_err
+from test_afno_cpu import FILTERS, MODELS, model_golden
+
+pytestmark = pytest.mark.gpu
+
+TOL = {"fp32": 1e-5, "bf16": 1e-2}
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    return torch.device("cuda:0")
+
+
+def close(a, b, mode, note="", bar=None):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    assert a.shape == b.shape, (a.shape, b.shape)
+    assert torch.isfinite(a).all()
+    bar = TOL[mode] if bar is None else bar
+    r, m = rel_err(a, b), max_rel(a, b)
+    print(f"{note} [{mode}]: rel {r:.3e} max {m:.3e} (bar {bar:.1e})")
+    record_parity(r, m, bar, mode, note)
+    assert r < bar and m < 2 * bar, f"{note}: rel={r:.3e} max={m:.3e} (bar {bar:.1e})"
+    return r
+
+
+def mode_scope(mode):
+    return torch.autocast("cuda", dtype=torch.bfloat16) if mode == "bf16" else contextlib.nullcontext()
+
+
+def filter_module(g, dev):
+    import tante_amd.afno as A
+    _, H, W, C = g["x"].shape
+    f = A.AFNO_ND(C, [H, W], cmlp_diagonal_blocks=g["w1"].shape[0], sparsity_threshold=float(g["lam"]))
+    f.load_state_dict({"cmlp.0.weight": g["w1"], "cmlp.2.weight": g["w2"]}, strict=True)
+    return f.to(dev).eval()
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16"])
+@pytest.mark.parametrize("name", FILTERS)
+def test_filter_alone_against_the_reference(dev, name, mode):
+    """AFNO_ND.forward (zero residual) under the fp32 bar in BOTH compute modes: the reference keeps the filter in fp32 under autocast."""
+    g = load_golden(name)
+    f = filter_module(g, dev)
+    with torch.no_grad(), mode_scope(mode):
+        y = f(g["x"].to(dev))
+    assert y.dtype == torch.float32
+    close(y, g["y"], "fp32", f"{name} filter alone, {mode} scope")
+
+
+@pytest.mark.parametrize("name", FILTERS)
+def test_filter_with_residual(dev, name):
+    """The store epilogue's skip: out = residual + swap_hw(filter(x)) is ONE fp32 add of the finished filter value, so it equals the
+    zero-residual result plus the residual bit for bit -- with a separate output and in place on the residual stream -- and the zero-
+    residual result itself meets the fp32 bar against the fixture with explicit zeros passed."""
+    import tante_amd.afno as A
+    g = load_golden(name)
+    x = g["x"].to(dev)
+    bs = g["w1"].shape[1]
+    w1, w2 = A.pack_block_weight(g["w1"].to(dev)), A.pack_block_weight(g["w2"].to(dev))
+    lam = float(g["lam"])
+    y0 = A.afno_filter(x, torch.zeros_like(x), w1, w2, bs, lam)
+    close(y0, g["y"].transpose(1, 2), "fp32", f"{name} kernel, zero residual")
+    assert torch.equal(y0, A.afno_filter(x, None, w1, w2, bs, lam))
+    res = torch.randn(x.shape, generator=torch.Generator().manual_seed(7)).to(dev)
+    y1 = A.afno_filter(x, res, w1, w2, bs, lam)
+    assert torch.equal(y1, y0 + res)
+    stream = res.clone()
+    A.afno_filter(x, stream, w1, w2, bs, lam, out=stream)
+    assert torch.equal(stream, y1)
+
+
+@pytest.mark.parametrize("B,H,W,C,bs", [(2, 7, 9, 40, 8), (1, 64, 33, 48, 24), (1, 33, 64, 128, 64), (3, 1, 1, 16, 16)])
+def test_filter_shapes_without_a_fixture(dev, B, H, W, C, bs):
+    """Odd axes, the 64-point limit, block sizes that are no multiple of 16, the largest block, channel counts that are no multiple of the
+    64-channel workgroup slice, a one-point grid: against the float64 restatement, relative to the filter's own output."""
+    import tante_amd.afno as A
+    gen = torch.Generator().manual_seed(H * 100 + W)
+    s = 0.04 * (32.0 / bs) ** 0.5 * (3.0 if H * W == 1 else 1.0)
+    w1, w2 = s * torch.randn(C // bs, bs, bs, 2, generator=gen), s * torch.randn(C // bs, bs, bs, 2, generator=gen)
+    x = torch.randn(B, H, W, C, generator=gen)
+    want = R.afno_filter(x, w1, w2, 0.01).transpose(1, 2)
+    assert float(want.abs().max()) > 1e-2                      # neither dead ...
+    if H * W > 1:
+        assert 0.1 <= R.zeroed_share(x, w1, w2, 0.01) <= 0.9   # ... nor free of the threshold
+    y = A.afno_filter(x.to(dev), None, A.pack_block_weight(w1.to(dev)), A.pack_block_weight(w2.to(dev)), bs, 0.01)
+    close(y, want, "fp32", f"filter {H}x{W} C {C} block {bs} B {B} vs float64 restatement")
+
+
+def build(name, dev, mode):
+    import tante_amd
+    g, sd, _ = model_golden(name)
+    res, patch = MODELS[name]
+    m = tante_amd.AFNO(in_T=3, dset_metadata=tante_amd.TanteMetadata(n_fields=2, spatial_resolution=res), hidden_dim=64, n_blocks=2,
+                       cmlp_diagonal_blocks=2, patch_size=patch)
+    m.load_state_dict(sd, strict=True)
+    return m.to(dev).eval().set_compute(mode), g, sd
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16"])
+@pytest.mark.parametrize("name", sorted(MODELS))
+def test_model_against_the_reference(dev, name, mode):
+    """Whole model under the project's bars (1e-5 / 1e-2).  (The reference's own fp32 rounding against the float64 restatement is 2.4e-7 /
+    1.8e-7 relative on these two fixtures: tests/test_afno_cpu.py.)"""
+    m, g, _ = build(name, dev, mode)
+    with torch.no_grad():
+        y = m(g["x"].to(dev))
+    assert tuple(y.shape) == tuple(g["y"].shape)
+    close(y, g["y"], mode, f"{name} model")
+    if mode == "bf16":          # autocast resolves to the same mode as set_compute
+        m.set_compute(None)
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+            assert torch.equal(m(g["x"].to(dev)), y)
+
+
+def test_rollout_against_the_refed_restatement(dev):
+    """rollout_model re-feeds the one-frame model: 4 steps on the square fixture against the float64 restatement re-fed on the CPU."""
+    import tante_amd
+    m, g, sd = build("g18_afno_model_32x32_p4", dev, "fp32")
+    x = g["x"]
+    batch = {"input": x.permute(0, 1, 3, 4, 2).contiguous().to(dev), "output": torch.zeros(2, 4, 32, 32, 2, device=dev)}
+    fmt = tante_amd.DefaultChannelsFirstFormatter(tante_amd.TanteMetadata(n_fields=2, spatial_resolution=(32, 32)))
+    with torch.no_grad():
+        y, y_ref = tante_amd.rollout_model(m, batch, fmt, 4)
+    assert tuple(y.shape) == (2, 4, 32, 32, 2) and tuple(y_ref.shape) == (2, 4, 32, 32, 2)
+    want = R.rollout(x, sd, 4, 4).permute(0, 1, 3, 4, 2)
+    for t in range(4):
+        close(y[:, t], want[:, t], "fp32", f"rollout step {t + 1}")
+
+
+def test_out_of_scope_cases_raise(dev):
+    import tante_amd
+    import tante_amd.afno as A
+    md = tante_amd.TanteMetadata(n_fields=2, spatial_resolution=(16, 16))
+    x = torch.randn(1, 2, 2, 16, 16, device=dev)
+    m = tante_amd.AFNO(in_T=2, dset_metadata=md, hidden_dim=32, n_blocks=1, cmlp_diagonal_blocks=2, patch_size=4).to(dev)
+    with pytest.raises(NotImplementedError, match="training is out of scope"):
+        m.train()(x)
+    with pytest.raises(NotImplementedError, match="training is out of scope"):
+        m.eval()(x)                                  # grad enabled with trainable parameters
+    d = tante_amd.AFNO(in_T=2, dset_metadata=md, hidden_dim=32, n_blocks=2, cmlp_diagonal_blocks=2, patch_size=4, drop_rate=0.1).to(dev)
+    p = tante_amd.AFNO(in_T=2, dset_metadata=md, hidden_dim=32, n_blocks=2, cmlp_diagonal_blocks=2, patch_size=4, drop_path_rate=0.1).to(dev)
+    with torch.no_grad():
+        for bad in (d, p):
+            with pytest.raises(NotImplementedError, match="drop_rate / drop_path_rate"):
+                bad.train()(x)
+            assert tuple(bad.eval()(x).shape) == (1, 1, 2, 16, 16)
+    with pytest.raises(NotImplementedError, match="n_spatial_dims = 3"):
+        tante_amd.AFNO(in_T=2, dset_metadata=tante_amd.TanteMetadata(n_fields=2, spatial_resolution=(16, 16, 16), n_spatial_dims=3), hidden_dim=32,
+                       n_blocks=1, patch_size=4)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        with torch.no_grad():
+            m.eval()(x.cpu())
+    # a token grid past the kernels' 64 points fails with the library's message, not silently
+    f = A.AFNO_ND(64, [65, 8], cmlp_diagonal_blocks=2).to(dev).eval()
+    with torch.no_grad(), pytest.raises(RuntimeError, match="token grid outside 1..64"):
+        f(torch.randn(1, 65, 8, 64, device=dev))
+    wide = tante_amd.AFNO(in_T=1, dset_metadata=tante_amd.TanteMetadata(n_fields=1, spatial_resolution=(130, 8)), hidden_dim=32, n_blocks=1,
+                          cmlp_diagonal_blocks=2, patch_size=2).to(dev).eval()
+    with torch.no_grad(), pytest.raises(RuntimeError, match="token grid outside 1..64"):
+        wide(torch.randn(1, 1, 1, 130, 8, device=dev))
