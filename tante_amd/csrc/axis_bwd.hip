@@ -113,10 +113,6 @@ __global__ __launch_bounds__(AB_NT, 2) void axis_bwd_fused_kernel(const float* _
       const int g = u >> 1, c = 2 * l15 + (u & 1);
       ug = g; uc = c;
       const int coff = (c >> 2), cw = c & 3;                     // chunk and word of this channel inside a position's 128 bytes
-#ifdef AB_SKIP_BWD
-      for (int mt = 0; mt < MT; ++mt) outk[mt] = zero4;
-      continue;
-#endif
       u32x4 xb[KB], gb[KB];
 #pragma unroll
       for (int ks = 0; ks < KB; ++ks) {
@@ -185,7 +181,6 @@ __global__ __launch_bounds__(AB_NT, 2) void axis_bwd_fused_kernel(const float* _
       const f32x4 lo = *(const f32x4*)(row + (((2 * kk) ^ ab_sw(q)) << 2)), hi = *(const f32x4*)(row + (((2 * kk + 1) ^ ab_sw(q)) << 2));
       return u32x4{pack_bf16x2(lo[0], lo[1]), pack_bf16x2(lo[2], lo[3]), pack_bf16x2(hi[0], hi[1]), pack_bf16x2(hi[2], hi[3])};
     };
-#ifndef AB_SKIP_WGRAD
     if (wave < MT) {
 #pragma unroll
       for (int g = 0; g < AB_NG; ++g) {
@@ -205,7 +200,6 @@ __global__ __launch_bounds__(AB_NT, 2) void axis_bwd_fused_kernel(const float* _
           acc2[t] = ab_mfma(frag(G, g, t), ones, acc2[t]);    // db2
         }
     }
-#endif
     __syncthreads();
     // ---- dx = dy + W1^T dpre into the G plane, then out in row form ----------------------------------------------------------------------
     if (wave < 2 * AB_NG) {
@@ -228,9 +222,6 @@ __global__ __launch_bounds__(AB_NT, 2) void axis_bwd_fused_kernel(const float* _
     __syncthreads();      // the planes are free for the next tile's DMA
   }
   // ---- the workgroup's partial gradients --------------------------------------------------------------------------------------------------
-#ifdef AB_SKIP_EPILOGUE
-  if (acc1[0][0] != 12345.f) return;
-#endif
   if (ws) {
     // the partial goes to the workgroup's slab ([dW1][dW2][db1][db2], plain stores) and ab_reduce_kernel sums the slabs: every workgroup
     // adding its 4 704 values atomically was most of this kernel's time (512 same-address atomics per value: 83 -> 57 us at n = 48 when

@@ -56,9 +56,7 @@ __device__ __forceinline__ f32x4 unpack4(const u32x2& u) { return f32x4{bf16_lo(
 
 template <int NTT>
 __global__ __launch_bounds__(256, 2) void block_tail_bwd_kernel(BtArgs A) {
-#ifdef BT_PRIO
-  if ((__builtin_amdgcn_s_getreg(0x1804) & 1u) == 1u) __builtin_amdgcn_s_setprio(3);      // as FS_PRIO in block_sliced.hip: the odd hardware wave slots
-#endif
+  if ((__builtin_amdgcn_s_getreg(0x1804) & 1u) == 1u) __builtin_amdgcn_s_setprio(3);      // as in block_sliced.hip: the odd hardware wave slots
   constexpr int RT = 4, NW = 4, PF = 2;
   constexpr int IMG = 16 * NTT * FS_ROW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -232,9 +230,7 @@ struct BhArgs {
 
 template <int NTT>
 __global__ __launch_bounds__(256, 2) void block_head_bwd_kernel(BhArgs A) {
-#ifdef BT_PRIO
   if ((__builtin_amdgcn_s_getreg(0x1804) & 1u) == 1u) __builtin_amdgcn_s_setprio(3);
-#endif
   constexpr int RT = 4, NW = 4, PF = 2;
   constexpr int IMG = 16 * NTT * FS_ROW;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -345,11 +341,8 @@ __global__ __launch_bounds__(256, 2) void block_head_bwd_kernel(BhArgs A) {
       const int r = RPI * j + rrow;
       const long t = tok0 + 16 * tt + r;
       const f32x4 v = *(const f32x4*)(sb + r * ROWB + ((rchunk ^ (r & (CPR - 1))) << 4));
-#ifdef BH_PLAIN_STORE
-      if (t < A.M) *(f32x4*)(A.dx + t * FS_C + 16 * RT * wave + 4 * rchunk) = v;
-#else   // write-through (common.hip.h): the launch's only output, written at its very end
+      // write-through (common.hip.h): the launch's only output, written at its very end
       if (t < A.M) st_wt16(A.dx + t * FS_C + 16 * RT * wave + 4 * rchunk, v);
-#endif
     }
   }
 }

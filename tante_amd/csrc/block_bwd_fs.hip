@@ -39,22 +39,12 @@
 #include "fs_common.hip.h"
 #include "block_sliced.h"
 
-// Structure switches (each pair computes the same function; tools/build_variant.sh builds the other forms, tools/ab_train.sh times them on
-// the cfg3 train step on ONE box).  Measured, round 5, B = 8, ms per train step, two interleaved rounds (gpurun_out/r05_ab_train_1.log ->
-// profiles/r05_block_bwd_ab.log): three launches 9.45 / 9.45; DMA rows + burst stores + dx1 in registers 9.34 / 9.40 (the default);
-// everything off (the first form of the round) 9.39 / 9.40; + stores riding the GEMMs 9.38 / 9.48; + dx1 parked in memory 9.71 / 9.67.
-#ifndef BF_DMA_ROWS
-#define BF_DMA_ROWS 1      // 1: hpre / xh2 / xh1 rows take turns in image C by LDS-DMA; 0: accumulator-layout global loads (xh1's image by DMA at the start)
-#endif
-#ifndef BF_HOOK_STORES
-#define BF_HOOK_STORES 0   // 1: bf16 row stores ride the k-steps of the following GEMM; 0: issued together behind the phase that wrote the image
-#endif
-#ifndef BF_LATE_HPRE
-#define BF_LATE_HPRE 1     // 1: the first saved rows (fc1's pre-activation) are requested behind the arrival of the gradient rows; 0: with them
-#endif
-#ifndef BF_PARK_DX1
-#define BF_PARK_DX1 0      // 1: dx1 waits in the output buffer between LayerNorm2's backward and the end (+50 MB per launch); 0: in 48 registers
-#endif
+// The structure below is the one of four measured forms that was kept (round 5, cfg3 train step at B = 8 on one box, ms per step, two
+// interleaved rounds, profiles/r05_block_bwd_ab.log): the saved hpre / xh2 / xh1 rows take turns in image C by LDS-DMA, the bf16 row stores
+// are issued together behind the phase that wrote their image, fc1's pre-activation rows are requested behind the arrival of the gradient
+// rows, dx1 stays in 48 registers -- 9.34 / 9.40.  Three launches 9.45 / 9.45; accumulator-layout global loads of the saved rows, requested
+// with the gradient rows (the first form of the round) 9.39 / 9.40; the row stores riding the k-steps of the following GEMM 9.38 / 9.48;
+// dx1 parked in the output buffer between LayerNorm2's backward and the end (+50 MB per launch) 9.71 / 9.67.
 
 namespace {
 
@@ -130,9 +120,7 @@ struct BfSeqMap {
 // DROP: dropout compiled in (p > 0) or out -- the mask arithmetic is a third of the attention phase's instructions
 template <int TPS, int NTT, bool DROP>
 __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfArgs A) {
-#ifdef BT_PRIO
-  if ((__builtin_amdgcn_s_getreg(0x1804) & 1u) == 1u) __builtin_amdgcn_s_setprio(3);      // as FS_PRIO in block_sliced.hip: the odd hardware wave slots
-#endif
+  if ((__builtin_amdgcn_s_getreg(0x1804) & 1u) == 1u) __builtin_amdgcn_s_setprio(3);      // as in block_sliced.hip: the odd hardware wave slots
   static_assert(NTT % TPS == 0 && 16 * NTT <= 64, "whole sequences, one slot per lane");
   constexpr int RT = 4, NW = 4, PF = 2, HPW = 2, NK = TPS;
   constexpr int IMG = 16 * NTT * FS_ROW;
@@ -192,7 +180,7 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
   // barrier behind its s_waitcnt vmcnt(0) publishes them.  One instruction = 2 rows of the image (32 lanes x 16 B per 512-byte row); it
   // writes lane-linear, so the image's row swizzle is applied to the global SOURCE chunk each lane fetches (chunk c of row r lives at
   // c ^ (r & 15)).  (Round 5, first form: these rows were loaded in ACCUMULATOR layout -- 8 bytes per lane, 16 different rows per
-  // instruction, every 64-byte line fetched twice -- and cost the launch 13-22 us: tools/build_variant.sh + -DBF_EXP_NO_ACCLOADS.)
+  // instruction, every 64-byte line fetched twice -- and cost the launch 13-22 us.)
   auto fresh_lane = [&]() {
     int ln = lane;
     asm volatile("" : "+v"(ln));
@@ -244,60 +232,26 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
       for (int rt = 0; rt < RT; ++rt) acc[rt][tt] = *(const f32x4*)(stg + l15 * ROWB + (((4 * rt + kk) ^ (l15 & (CPR - 1))) << 4));
     }
   };
-  auto slice_store = [&](char* stg, float* __restrict__ dst, const f32x4 (&acc)[RT][NTT], auto wt_c) {
-    BF_RLANE;
-#pragma unroll
-    for (int tt = 0; tt < NTT; ++tt) {
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) *(f32x4*)(stg + l15 * ROWB + (((4 * rt + kk) ^ (l15 & (CPR - 1))) << 4)) = acc[rt][tt];
-#pragma unroll
-      for (int j = 0; j < RT; ++j) {
-        const int r = RPI * j + rrow, t = tok_of(16 * tt + r);
-        const f32x4 v = *(const f32x4*)(stg + r * ROWB + ((rchunk ^ (r & (CPR - 1))) << 4));
-        if (t >= 0) {
-          if constexpr (decltype(wt_c)::value) st_wt16(dst + (long)t * FS_C + 16 * RT * wave + 4 * rchunk, v);      // the launch's last output, at its very end
-          else *(f32x4*)(dst + (long)t * FS_C + 16 * RT * wave + 4 * rchunk) = v;
-        }
-      }
-    }
-  };
   // bf16 rows: this wave's columns of image tile tt -> memory in row form (8 lanes x 16 B per token row, 8 rows per instruction)
   constexpr int CPB = 2 * RT, RPB = 64 / CPB;
-  // one sub-step = one instruction = 8 rows; a tensor's 2 NTT sub-steps ride the k-steps of the GEMM that FOLLOWS the phase that wrote the
-  // image (rows_hook): issued together behind their phase, the 36 row stores of a wave (100 MB per launch at cfg3) formed bursts that the
-  // next GEMM's weight loads queued behind (the wave's memory queue returns in order) -- 15-20 us of the launch (-DBF_EXP_NO_ROWSTORES)
+  // one sub-step = one instruction = 8 rows; a tensor's 2 NTT sub-steps are issued together behind the phase that wrote the image.  The 36
+  // row stores of a wave (100 MB per launch at cfg3) form bursts that the next GEMM's weight loads queue behind (the wave's memory queue
+  // returns in order) -- 15-20 us of the launch -- but spread over the k-steps of the following GEMM they measured no better (above)
   auto img_rows_store1 = [&](const char* img, auto tt_c, auto j_c, unsigned short* __restrict__ dst, long dstride, int dcol) {
     constexpr int tt = decltype(tt_c)::value, j = decltype(j_c)::value;
     BF_BLANE;
     const int r = RPB * j + brow;
     const int t = tok_of(16 * tt + r);
     const u32x4 v = *(const u32x4*)(img + tt * 8192 + r * FS_ROW + (((CPB * wave + bchunk) ^ r) << 4));
-#ifdef BF_EXP_NO_ROWSTORES      // timing experiment only (wrong results): what the bf16 row stores cost
-    if (t >= 0 && v[0] == 0x12345u) *(u32x4*)(dst + (long)t * dstride + dcol + 16 * RT * wave + 8 * bchunk) = v;
-#else
     if (t >= 0) *(u32x4*)(dst + (long)t * dstride + dcol + 16 * RT * wave + 8 * bchunk) = v;
-#endif
   };
-  auto rows_hook = [&](const char* img, unsigned short* __restrict__ dst, long dstride, int dcol) {
-    return [&, img, dst, dstride, dcol](auto ks_c) {
-      constexpr int ks = decltype(ks_c)::value;
-      if constexpr (ks < 2 * NTT) img_rows_store1(img, std::integral_constant<int, ks / 2>{}, std::integral_constant<int, ks % 2>{}, dst, dstride, dcol);
-    };
-  };
-  static_assert(16 / RPB == 2 && 2 * NTT <= 8, "a tensor's row stores fit the k-steps of one GEMM");
-  auto rows_burst = [&](const char* img, unsigned short* __restrict__ dst, long dstride, int dcol) {      // BF_HOOK_STORES == 0: all at once
+  static_assert(16 / RPB == 2, "two row-store instructions per token tile");
+  auto rows_burst = [&](const char* img, unsigned short* __restrict__ dst, long dstride, int dcol) {
     static_for<2 * NTT>([&](auto i_c) {
       constexpr int i = decltype(i_c)::value;
       img_rows_store1(img, std::integral_constant<int, i / 2>{}, std::integral_constant<int, i % 2>{}, dst, dstride, dcol);
     });
   };
-#if BF_HOOK_STORES
-#define BF_HOOK(img, dst, stride, col) rows_hook(img, dst, stride, col)
-#define BF_BURST(img, dst, stride, col)
-#else
-#define BF_HOOK(img, dst, stride, col) FsNoHook{}
-#define BF_BURST(img, dst, stride, col) rows_burst(img, dst, stride, col)
-#endif
 
   // ---- per-lane LDS addressing (block_sliced.hip) ----------------------------------------------------------------------------------------
   int rdo[4], wro[RT];
@@ -330,24 +284,11 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
     f32x4 raw[NTT][RT];
     slice_load(A.dout, raw);      // the rows everything waits for: first in the memory queue
     asm volatile("" ::: "memory");
-#if !BF_LATE_HPRE
-#if BF_DMA_ROWS
-    dma_rows(A.hpre);
-#else
-    dma_rows(A.xh1);
-#endif
-#endif
     slice_to_acc(imgB + wave * (IMG / NW), raw, g);      // image B: first written behind barrier 1
-#if BF_LATE_HPRE
     // the saved rows are requested only now: the single resident round starts in step, and every workgroup asking for its gradient rows AND
     // its saved rows at once made a 37 MB burst that the gradient rows -- the only thing P0 needs -- waited out (stamps: 17.6 k cycles)
     asm volatile("" ::: "memory");
-#if BF_DMA_ROWS
     dma_rows(A.hpre);
-#else
-    dma_rows(A.xh1);
-#endif
-#endif
   }
   BF_STAMP(20);
 #pragma unroll
@@ -356,7 +297,7 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
     for (int rt = 0; rt < RT; ++rt) *(u32x2*)(imgA + tt * 8192 + wro[rt]) = bf_pack4(drop4(g[rt][tt], A.seed_mlp ^ smix, off[tt] + 16 * rt));
   }
   BF_STAMP(21);
-  BF_BURST(imgA, A.dy2, FS_C, 0);
+  rows_burst(imgA, A.dy2, FS_C, 0);
   if (tid < 3 * FS_C / 4) *(f32x4*)(lbias + 4 * tid) = bias_in;
   BF_STAMP(2);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's share of the pre-activation rows has landed in image C (the barrier publishes it)
@@ -370,8 +311,7 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
     for (int tt = 0; tt < NTT; ++tt)
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) acc[rt][tt] = zero4;
-#if BF_DMA_ROWS
-    fs_slice_gemm<0, 24, NTT, RT, false, PF>(wqt, wb, imgA, rdo, acc, BF_HOOK(imgA, A.dy2, FS_C, 0));
+    fs_slice_gemm<0, 24, NTT, RT, false, PF>(wqt, wb, imgA, rdo, acc);
     BF_STAMP(4);
     u32x2 hp[RT][NTT];      // (read together: the compiler cannot move an LDS read over the image writes below)
 #pragma unroll
@@ -384,15 +324,6 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();      // 1b
     dma_rows(A.xh2);
-#else
-    u32x2 hp[RT][NTT];
-#pragma unroll
-    for (int tt = 0; tt < NTT; ++tt)
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) hp[rt][tt] = *(const u32x2*)(A.hpre + off[tt] + 16 * rt);      // in flight under the GEMM
-    fs_slice_gemm<0, 24, NTT, RT, false, PF>(wqt, wb, imgA, rdo, acc, BF_HOOK(imgA, A.dy2, FS_C, 0));
-    BF_STAMP(4);
-#endif
 #pragma unroll
     for (int tt = 0; tt < NTT; ++tt) {
 #pragma unroll
@@ -406,7 +337,7 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
       rstd2[tt] = A.st2[2 * (long)(lv[tt] ? tokidx[tt] : 0) + 1];
     }
   }
-  BF_BURST(imgB, A.dhpre, FS_C, 0);
+  rows_burst(imgB, A.dhpre, FS_C, 0);
   __syncthreads();      // 2
   BF_STAMP(5);
 
@@ -417,8 +348,7 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
     for (int tt = 0; tt < NTT; ++tt)
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) acc[rt][tt] = zero4;
-#if BF_DMA_ROWS
-    fs_slice_gemm<1, 16, NTT, RT, false, PF>(wqt, wb, imgB, rdo, acc, BF_HOOK(imgB, A.dhpre, FS_C, 0));
+    fs_slice_gemm<1, 16, NTT, RT, false, PF>(wqt, wb, imgB, rdo, acc);
     BF_STAMP(6);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();      // 2b: LayerNorm2's rows are in image C
@@ -430,15 +360,6 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();      // 2c: every wave holds LayerNorm2's rows: LayerNorm1's are requested now and land under this epilogue
     dma_rows(A.xh1);
-#else
-    u32x2 xh[RT][NTT];
-#pragma unroll
-    for (int tt = 0; tt < NTT; ++tt)
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) xh[rt][tt] = *(const u32x2*)(A.xh2 + off[tt] + 16 * rt);      // in flight under the GEMM
-    fs_slice_gemm<1, 16, NTT, RT, false, PF>(wqt, wb, imgB, rdo, acc, BF_HOOK(imgB, A.dhpre, FS_C, 0));
-    BF_STAMP(6);
-#endif
 #pragma unroll
     for (int tt = 0; tt < NTT; ++tt) {
       float s1 = 0.f, s2 = 0.f;
@@ -477,17 +398,13 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
       }
       __builtin_amdgcn_sched_barrier(0);      // tile by tile: interleaved, the tiles' hash and LayerNorm temporaries push the phase into scratch
     }
-    // dx1 waits in the OUTPUT buffer for the end of the launch (this wave's own rows, read back by itself: no other workgroup touches them).
-    // Held in 48 registers through the recompute and the attention it pushed the launch into scratch: the compiler spilled half of it
-    // anyway, and every scratch reload in between -- a vector-memory wait in an in-order queue -- drained the row stores and DMAs in flight.
-#if BF_PARK_DX1
-    slice_store(imgB + wave * (IMG / NW), A.dx, g, std::false_type{});      // image B: its readers (P2's GEMM) are behind barrier 3
-#endif
+    // (dx1 stays in g, 48 registers, through the recompute and the attention: parked in the output buffer and read back at the end it cost
+    // +50 MB per launch and 0.3 ms per train step, above)
   }
   // (Wo^T's first k-steps are requested HERE, not inside P2's GEMM: alive across LayerNorm2's backward, those 32 registers were what pushed
   // the phase into scratch -- and a scratch reload drains the wave's whole memory queue, row stores and DMAs included)
   fs_wring_prime<2, RT, PF>(wqt, wb);
-  BF_BURST(imgA, A.dy1, FS_C, 0);
+  rows_burst(imgA, A.dy1, FS_C, 0);
   __syncthreads();      // 4
   BF_STAMP(7);
 
@@ -498,7 +415,7 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
     for (int tt = 0; tt < NTT; ++tt)
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) acc[rt][tt] = zero4;
-    fs_slice_gemm<2, 24, NTT, RT, false, PF>(wqt, wb, imgA, rdo, acc, BF_HOOK(imgA, A.dy1, FS_C, 0));
+    fs_slice_gemm<2, 24, NTT, RT, false, PF>(wqt, wb, imgA, rdo, acc);
     BF_STAMP(8);
     fs_wring_prime<0, RT, PF>(wqf, wb);      // the forward stream's q rows, under the epilogue and the barrier
     // image B (dhpre) died with P2's GEMM (barriers 3, 4): d_o in row-major form, for the plain and the transposing fragment reads
@@ -507,9 +424,7 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) *(u32x2*)(imgB + tt * 8192 + wro[rt]) = bf_pack4(acc[rt][tt]);
   }
-#if BF_DMA_ROWS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
   __syncthreads();      // 5: image A's readers (P3's GEMM) are done, LayerNorm1's rows are in image C
   BF_STAMP(9);
 
@@ -786,24 +701,11 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
   float rstd1[NTT];
 #pragma unroll
   for (int tt = 0; tt < NTT; ++tt) rstd1[tt] = A.st1[2 * (long)(lv[tt] ? tokidx[tt] : 0) + 1];
-#if BF_PARK_DX1
-  f32x4 dx1raw[NTT][RT];      // dx1 back from the output buffer (row form), in flight under the closing GEMMs
-  slice_load(A.dx, dx1raw);
-#endif
-#if !BF_HOOK_STORES
   // (issued per head, right behind each head's image writes, so that head 0's drain under head 1: measured, same box, no gain -- 8.94 ms
   // per train step either way; what the closing GEMMs wait for is not these stores' place in the queue)
-  BF_BURST(imgC, A.dqkv, 3 * FS_C, 0);
-  BF_BURST(imgA, A.dqkv, 3 * FS_C, FS_C);
-  BF_BURST(imgB, A.dqkv, 3 * FS_C, 2 * FS_C);
-#endif
-#if !BF_DMA_ROWS
-  u32x2 xh1r[RT][NTT];      // in flight under the closing GEMMs
-#pragma unroll
-  for (int tt = 0; tt < NTT; ++tt)
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) xh1r[rt][tt] = *(const u32x2*)(A.xh1 + off[tt] + 16 * rt);
-#endif
+  rows_burst(imgC, A.dqkv, 3 * FS_C, 0);
+  rows_burst(imgA, A.dqkv, 3 * FS_C, FS_C);
+  rows_burst(imgB, A.dqkv, 3 * FS_C, 2 * FS_C);
   __syncthreads();      // 7
   BF_STAMP(16);
 
@@ -815,14 +717,11 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) acc[rt][tt] = zero4;
     // dq | dk | dv rows -> memory (the in-projection's weight gradient reads them) under the three GEMMs that read the same images
-    fs_slice_gemm<0, 24, NTT, RT, false, PF>(wqh, wb, imgC, rdo, acc, BF_HOOK(imgC, A.dqkv, 3 * FS_C, 0));
-#if BF_DMA_ROWS
+    fs_slice_gemm<0, 24, NTT, RT, false, PF>(wqh, wb, imgC, rdo, acc);
     __syncthreads();      // 7b: image C (dq) has no reader left: LayerNorm1's rows come back into it under the other two GEMMs (held in
     dma_rows(A.xh1);      // registers through the attention they pushed the launch into scratch)
-#endif
-    fs_slice_gemm<1, 24, NTT, RT, false, PF>(wqh, wb, imgA, rdo, acc, BF_HOOK(imgA, A.dqkv, 3 * FS_C, FS_C));
-    fs_slice_gemm<2, 24, NTT, RT, false, PF>(wqh, wb, imgB, rdo, acc, BF_HOOK(imgB, A.dqkv, 3 * FS_C, 2 * FS_C));
-#if BF_DMA_ROWS
+    fs_slice_gemm<1, 24, NTT, RT, false, PF>(wqh, wb, imgA, rdo, acc);
+    fs_slice_gemm<2, 24, NTT, RT, false, PF>(wqh, wb, imgB, rdo, acc);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();      // 8a
     u32x2 xh1r[RT][NTT];
@@ -830,7 +729,6 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
     for (int tt = 0; tt < NTT; ++tt)
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) xh1r[rt][tt] = *(const u32x2*)(imgC + tt * 8192 + wro[rt]);
-#endif
     BF_STAMP(17);
 #pragma unroll
     for (int tt = 0; tt < NTT; ++tt) {
@@ -872,22 +770,8 @@ __global__ __launch_bounds__(256, NTT <= 3 ? 2 : 1) void block_bwd_fs_kernel(BfA
     BF_RLANE;
 #pragma unroll
     for (int tt = 0; tt < NTT; ++tt) {
-#if BF_PARK_DX1
-#pragma unroll
-      for (int j = 0; j < RT; ++j) {
-        const int r = RPI * j + rrow;
-        *(f32x4*)(stg + r * ROWB + ((rchunk ^ (r & (CPR - 1))) << 4)) = dx1raw[tt][j];
-      }
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-        const int o = l15 * ROWB + (((4 * rt + kk) ^ (l15 & (CPR - 1))) << 4);
-        const f32x4 d = *(const f32x4*)(stg + o) + acc[rt][tt];
-        *(f32x4*)(stg + o) = d;      // (the same lane reads and rewrites its own 16 bytes)
-      }
-#else
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) *(f32x4*)(stg + l15 * ROWB + (((4 * rt + kk) ^ (l15 & (CPR - 1))) << 4)) = g[rt][tt] + acc[rt][tt];
-#endif
 #pragma unroll
       for (int j = 0; j < RT; ++j) {
         const int r = RPI * j + rrow, t = tok_of(16 * tt + r);

@@ -377,10 +377,7 @@ __global__ __launch_bounds__(512, 2) void fused_block16_kernel(float* __restrict
   constexpr int SLOT = (TILEH > TILE2 ? TILEH : TILE2);
   constexpr int NT = NH + TO + T1 + TO;
   constexpr int MAXB = (HB > CB ? HB : CB);
-#ifndef TANTE_RING
-#define TANTE_RING 4
-#endif
-  constexpr int RING = TANTE_RING;  // weight fragments in flight per wave (mfma_stream); 8 measured no faster
+  constexpr int RING = 4;  // weight fragments in flight per wave (mfma_stream); 8 measured no faster
   extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 weight slots, then 2 mailbox sets of 8 x 2 KiB
   char* mbox = smem + 2 * SLOT;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kk = lane >> 4, l15 = lane & 15;
@@ -526,7 +523,7 @@ __global__ __launch_bounds__(512, 2) void fused_block16_kernel(float* __restrict
       unsigned bt[CB];   // per-k-block LDS base of this tile: row + swizzled chunk; the row-tile offset is an immediate
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb) bt[cb] = lds_addr(wt + row_c + xo_c[cb]);
-      mfma_stream<6 * CB, RING>(
+      mfma_stream<6 * CB, RING, true>(
           [&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(i % 6) * 16 * CPR * 16>{bt[i / 6]}; },
           [&](auto ic, const u32x4& wf) {
             constexpr int i = decltype(ic)::value, rt = i % 6, cb = i / 6;
@@ -575,7 +572,7 @@ __global__ __launch_bounds__(512, 2) void fused_block16_kernel(float* __restrict
       unsigned bt[KB];
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb) bt[kb] = lds_addr(wt + ((KB == CB) ? row_c + xo_c[kb < CB ? kb : 0] : row_h + xo_h[kb < HB ? kb : 0]));
-      mfma_stream<4 * KB, RING>(
+      mfma_stream<4 * KB, RING, true>(
           [&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(i % 4) * 16 * cpr * 16>{bt[i / 4]}; },
           [&](auto ic, const u32x4& wf) {
             constexpr int i = decltype(ic)::value, ns = i % 4, kb = i / 4;

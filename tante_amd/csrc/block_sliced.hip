@@ -26,13 +26,6 @@
 #include "fs_common.hip.h"
 #include "block_sliced.h"
 
-// The FS_EXP_* switches are TIMING experiments: they skip work and produce wrong results by design.  They compile only into the diagnostic
-// build (-DTANTE_ABLATE: tools/_ab/ libraries, never tante_amd/lib/libtante_hip.so) -- ADVICE round 5.
-#if (defined(FS_EXP_NO_SAVE) || defined(FS_EXP_LN_ID) || defined(FS_EXP_GELU_ID) || defined(FS_EXP_NO_RESID) || defined(FS_EXP_NO_STORE) || \
-     defined(FS_EXP_TPROP_NO_STORE) || defined(FS_EXP_ROT) || defined(FS_EXP_NO_WLOAD) || defined(FS_EXP_MFMA32)) && !defined(TANTE_ABLATE)
-#error "FS_EXP_* timing experiments produce wrong results on purpose: build them with -DTANTE_ABLATE (tools/build_variant.sh), never into the product library"
-#endif
-
 namespace {
 
 
@@ -174,19 +167,10 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
   static_assert(G == 1 || (G == 2 && NW == 4), "the paired form is two 4-wave groups");
   constexpr int RT = 16 / NW;            // 16-row output tiles per wave
   constexpr int HPW = RT / 2;            // heads per wave
-#ifndef FS_PF8
-#define FS_PF8 3
-#endif
-#ifndef FS_PF4
-#define FS_PF4 2
-#endif
+  constexpr int FS_PF8 = 3, FS_PF4 = 2;      // 8-wave / 4-wave forms (4 waves at 3 k-steps spill: +5.5 us per launch)
   // weight k-steps in flight.  The register-heaviest instantiations (training forward at 4 token tiles, the element-masked any-L forms,
   // the 8-tile 8-wave forms) spilled 20 - 290 bytes per lane at the full depth: they run one k-step shallower (16 RT fewer registers)
-#ifdef FS_NO_TIGHT      // (A/B: every instantiation at the full depth, as in round 2)
-  constexpr bool TIGHT = false;
-#else
   constexpr bool TIGHT = (NW == 4 && NTT == 4 && (TRAIN || TPS == 0)) || (NW == 8 && NTT == 8);
-#endif
   constexpr int PF = (NW == 8 ? FS_PF8 : FS_PF4) - (TIGHT ? 1 : 0);
   constexpr int IMG = 16 * NTT * FS_ROW;
   constexpr int LDS_G = 2 * IMG + 16 * NTT * NW * 8 + FS_BIAS_FLOATS * 4;      // bytes of LDS per group
@@ -199,25 +183,15 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
   float* const lbias = (float*)(stat + 16 * NTT * NW * 8);   // the 4 x 256 biases (a global load per GEMM start would expose its latency)
   const int tid = threadIdx.x & (64 * NW - 1), lane = tid & 63, kk = lane >> 4, l15 = lane & 15;      // thread within the group
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef FS_XCD_SAMPLE   // experiment: consecutive workgroup ids go to consecutive XCDs; give XCD k a CONTIGUOUS eighth of the sequences (at B = 8:
-  // sample k, in every letter's launch and in the propagator pass), so that a launch finds the rows the previous one wrote in its own L2
-  const int vblock = (G == 1 && gridDim.x % 8 == 0) ? (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)) : (int)blockIdx.x * G + grp;
-#else
   const int vblock = (int)blockIdx.x * G + grp;      // the group's index = the workgroup index of the unpaired form
-#endif
-#ifndef FS_SKEW
-#define FS_SKEW 1      // 0: experiment -- the two groups of the paired form in step (same barriers, no offset, no alignment barriers)
-#endif
-  if constexpr (G == 2 && FS_SKEW) {
+  if constexpr (G == 2) {
     if (grp == 1) __builtin_amdgcn_s_barrier();      // one segment behind group 0 from here on (group 0 takes its extra barrier at exit)
   }
-#ifdef FS_PRIO
-  // experiment: the two workgroups of a CU run in lockstep through MFMA-only and VALU-only phases.  Waves in odd hardware slots (HW_ID
-  // bits 3:0) get issue priority for the whole kernel, so that the pair drifts apart instead of sharing every phase
+  // the two workgroups of a CU run in lockstep through MFMA-only and VALU-only phases.  Waves in odd hardware slots (HW_ID bits 3:0) get
+  // issue priority for the whole kernel, so that the pair drifts apart instead of sharing every phase (without it +0.3...1.1 us per launch)
   if constexpr (G == 1) {
-    if ((__builtin_amdgcn_s_getreg(0x1804) & 1u) == (FS_PRIO & 1)) __builtin_amdgcn_s_setprio(3);
+    if ((__builtin_amdgcn_s_getreg(0x1804) & 1u) == 1u) __builtin_amdgcn_s_setprio(3);
   }
-#endif
   if constexpr (!TRAIN && G == 1) {
     if (A.skew > 0 && blockIdx.x >= (gridDim.x >> 1)) {
       for (int i = 0; i < A.skew; ++i) __builtin_amdgcn_s_sleep(8);
@@ -272,14 +246,8 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
   static_assert((IMG / NW) >= TILEB, "staging piece too small");
   char* const stg = bufA + wave * (IMG / NW);
   const int rrow = lane / CPR, rchunk = lane % CPR;            // row form: this lane's row within an instruction and its chunk
-  // row of a tile that instruction j of a lane's row group touches: 4 consecutive rows per instruction, or -- in the kernels that carry the
-  // temporal propagator (L = 4: rows 4 s .. 4 s + 3 are the four time steps of sequence s) -- row 4 rrow + j, so that a LANE holds the four
-  // time steps of one sequence in its four registers (the propagator then needs no cross-lane traffic)
-#ifdef FS_TPROP_RECOMPUTE      // measured, round 3: the T launch 46 us this way against 41 us with the rows rewritten in phase 0 -- off
-  auto srow = [&](int j) { return TPROP ? 4 * rrow + j : RPI * j + rrow; };
-#else
+  // row of a tile that instruction j of a lane's row group touches: RPI consecutive rows per instruction
   auto srow = [&](int j) { return RPI * j + rrow; };
-#endif
   auto slice_load = [&](const float* __restrict__ src, f32x4 (&raw)[NTT][RT]) {      // row form, straight from memory
 #pragma unroll
     for (int tt = 0; tt < NTT; ++tt)
@@ -316,11 +284,7 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
       // (ordinary stores: written through they buy nothing -- 9.65 ms per train step either way.  The first attempt gave NaN losses: the
       // write-through store is an asm statement, and a GELU that reused its data registers right behind it hit the store-data hazard the
       // compiler's recognizer does not see inside asm -- st_wt16 carries the wait states now, common.hip.h)
-#ifdef FS_EXP_NO_SAVE      // timing experiment only (wrong results): what the saved tensors' row stores cost the training forward
-      if (t >= 0 && v[0] == 0x12345u) *(u32x4*)(dst + (long)t * dstride + dcol + 16 * RT * wave + 8 * bchunk) = v;
-#else
       if (t >= 0) *(u32x4*)(dst + (long)t * dstride + dcol + 16 * RT * wave + 8 * bchunk) = v;
-#endif
     }
   };
   auto slice_store = [&](float* __restrict__ dst, const f32x4 (&acc)[RT][NTT]) {
@@ -333,15 +297,12 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
       for (int j = 0; j < RT; ++j) {
         const int r = RPI * j + rrow, t = tok_of(16 * tt + r);
         const f32x4 v = *(const f32x4*)(sb + r * ROWB + ((rchunk ^ (r & (CPR - 1))) << 4));
-#ifdef FS_NT_STORE      // experiment: streaming (non-temporal) stores of the block's output rows
-        if (t >= 0) __builtin_nontemporal_store(v, (f32x4*)(dst + (long)t * FS_C + 16 * RT * wave + 4 * rchunk));
-#else                   // write-through (common.hip.h): 38.4 -> 37.2 us per launch and +2.4 % on the rollout, three interleaved rounds
-        // the inference form only (the training form's launches are bound by their saved-tensor traffic, not by the release)
+        // write-through (common.hip.h): 38.4 -> 37.2 us per launch and +2.4 % on the rollout, three interleaved rounds (non-temporal
+        // stores: +- 0); the inference form only (the training form's launches are bound by their saved-tensor traffic, not by the release)
         if (t >= 0 && (!LASTQ || (r & 3) == 3)) {      // (L = 4: row r of a tile is slot r & 3 of its sequence)
           if constexpr (TRAIN) *(f32x4*)(dst + (long)t * FS_C + 16 * RT * wave + 4 * rchunk) = v;
           else st_wt16(dst + (long)t * FS_C + 16 * RT * wave + 4 * rchunk, v);
         }
-#endif
       }
     }
   };
@@ -379,15 +340,11 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
           const f32x4 y = xv[i][t];
           const int tk = tok_of(4 * (wave * GPW + i) + t);      // (wave-uniform; cheaper to fetch again than to keep 16 of them)
           const bool live = tk >= 0;
-#ifndef FS_TPROP_RECOMPUTE
           // The propagated row goes back to x: the residual slices are re-read from there behind the barriers below (workgroup-scope
           // release / acquire of __syncthreads; the rows of a workgroup are its own).  The alternative -- leave x alone and run the
-          // residual slices through the propagator a second time (-DFS_TPROP_RECOMPUTE) -- costs the contraction + 64 GELUs per lane
-          // once more on the critical path: 46 us per launch against 41 us (the extra 33 MB of stores drain under the q, k, v GEMMs).
-#ifndef FS_EXP_TPROP_NO_STORE      // timing experiment only (wrong results): what the propagated rows' store and re-read cost
+          // residual slices through the propagator a second time -- costs the contraction + 64 GELUs per lane once more on the
+          // critical path: measured 46 us per launch against 41 us (the extra 33 MB of stores drain under the q, k, v GEMMs).
           if (live && (!LASTQ || t == 3)) *(f32x4*)(x + (long)tk * FS_C + 4 * lane) = y;
-#endif
-#endif
           float sm = (y[0] + y[1]) + (y[2] + y[3]);
           float sq = fmaf(y[0], y[0], fmaf(y[1], y[1], fmaf(y[2], y[2], y[3] * y[3])));
           sm = rows_sum(row16_sum(sm));
@@ -446,11 +403,7 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
         const int chunk = (l15 >> 1) + 8 * j;
         *(u32x2*)(bufA + slot * FS_ROW + ((chunk ^ t15) << 4) + (l15 & 1) * 8) = o2;
         if constexpr (TRAIN) {
-#ifdef FS_EXP_NO_SAVE
-          if (lv[i] && o2[0] == 0x12345u) *(u32x2*)(A.xh1 + (long)tis[i] * FS_C + 4 * (l15 + 16 * j)) = o2;
-#else
           if (lv[i]) *(u32x2*)(A.xh1 + (long)tis[i] * FS_C + 4 * (l15 + 16 * j)) = o2;
-#endif
         }
       }
       if constexpr (TRAIN) {
@@ -574,7 +527,7 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
           vtf[hh][dt][p] = (2 * p + 1 < NTT) ? pack8(av[2 * hh + dt][2 * p], av[2 * hh + dt][2 * p + 1]) : pack8(av[2 * hh + dt][2 * p], zero4);
   }
   FS_STAMP(6);
-  if constexpr (G == 2 && FS_SKEW) __builtin_amdgcn_s_barrier();      // alignment only: MATRIX segment (q, k, v) | vector segment (attention)
+  if constexpr (G == 2) __builtin_amdgcn_s_barrier();      // alignment only: MATRIX segment (q, k, v) | vector segment (attention)
 
   // ---- attention: per head and query tile, S^T = K Q^T over its key tiles, softmax down the accumulator rows, O^T = V^T P^T ----
   {
@@ -740,20 +693,8 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
   asm volatile("" ::: "memory");   // keep the residual loads below the attention (they would double its register pressure)
   // residual slice of this wave: x[token][16 RT w .. + 16 RT), row form; the loads fly while the out-proj GEMM runs
   f32x4 xraw[NTT][RT];
-#ifndef FS_RESID_FIRST
   fs_wring_prime<3, RT, PF>(wq, wb);      // ahead of the residual rows in the wave's (in-order) memory queue: the out-proj GEMM starts on them
-#endif
-#ifdef FS_EXP_NO_RESID     // timing experiment only (wrong results)
-#pragma unroll
-  for (int tt = 0; tt < NTT; ++tt)
-#pragma unroll
-    for (int j = 0; j < RT; ++j) xraw[tt][j] = f32x4{(float)tt, 1.f, 2.f, (float)j};
-#else
-  slice_load(x, xraw);
-#endif
-#ifdef FS_RESID_FIRST
-  fs_wring_prime<3, RT, PF>(wq, wb);      // (round-2 order, kept for the A/B)
-#endif
+  slice_load(x, xraw);                    // (the other order measured the same)
   FS_STAMP(8);
   __syncthreads();
   FS_STAMP(9);
@@ -791,15 +732,6 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
 #pragma unroll
       for (int tt = 0; tt < NTT; ++tt) acc[rt][tt] += res[rt][tt];
   };
-#ifdef FS_TPROP_RECOMPUTE
-  if constexpr (TPROP) {      // the residual is the PROPAGATED row: the same contraction on this wave's feature slice (see srow) -- here,
-    static_assert(!TPROP || RT == 4, "a lane's row group = the four time steps of a sequence");      // behind the out-proj GEMM the loads flew under
-    TpropW tw;
-    tprop_weights(A.tprop, lane, tw);
-#pragma unroll
-    for (int tt = 0; tt < NTT; ++tt) tprop_apply(tw, xraw[tt]);
-  }
-#endif
   {
     f32x4 xr[RT][NTT];
     slice_to_acc(xraw, xr);      // bufA: LayerNorm1's image died with the q/k/v GEMMs (barrier 2), LayerNorm2's comes after barrier 3
@@ -843,13 +775,8 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
       u32x2 o2;
-#ifdef FS_EXP_LN_ID        // timing experiment only (wrong results): the price of LayerNorm2's normalise pass
-      o2[0] = pack_bf16x2(x1[rt][tt][0], x1[rt][tt][1]);
-      o2[1] = pack_bf16x2(x1[rt][tt][2], x1[rt][tt][3]);
-#else
       o2[0] = pack_bf16x2(fmaf(x1[rt][tt][0], rstd, sh), fmaf(x1[rt][tt][1], rstd, sh));
       o2[1] = pack_bf16x2(fmaf(x1[rt][tt][2], rstd, sh), fmaf(x1[rt][tt][3], rstd, sh));
-#endif
       *(u32x2*)(bufA + tt * 8192 + wro[rt]) = o2;
     }
     if constexpr (TRAIN) {
@@ -871,7 +798,7 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
     }
     fs_slice_gemm<4, 48, NTT, RT, false, PF>(wq, wb, bufA, rdo, h);
     FS_STAMP(13);
-    if constexpr (G == 2 && FS_SKEW) __builtin_amdgcn_s_barrier();    // alignment only: MATRIX segment (fc1) | vector segment (GELU)
+    if constexpr (G == 2) __builtin_amdgcn_s_barrier();    // alignment only: MATRIX segment (fc1) | vector segment (GELU)
 #pragma unroll
     for (int tt = 0; tt < NTT; ++tt) {
       if constexpr (TRAIN) {     // the pre-activation passes through the image columns the GELU-ed values take next
@@ -886,11 +813,7 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
       }
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
-#ifdef FS_EXP_GELU_ID      // timing experiment only (wrong results): the whole price of the GELU arithmetic (round-5 verdict item 4)
-        const f32x4 g = h[rt][tt];
-#else
         const f32x4 g = gelu_poly4<true>(h[rt][tt]);
-#endif
         u32x2 o2;
         o2[0] = pack_bf16x2(g[0], g[1]);
         o2[1] = pack_bf16x2(g[2], g[3]);
@@ -931,21 +854,9 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
 #ifdef TANTE_ABLATE
     if (A.stamps && lane == 0) A.stamps[((long)vblock * 8 + wave) * 20 + 19] = __builtin_amdgcn_s_memrealtime();
 #endif
-#ifdef FS_EXP_NO_STORE     // timing experiment only (wrong results): one store per tile keeps the accumulators alive
-#pragma unroll
-    for (int tt = 0; tt < NTT; ++tt)
-      if (tokidx[tt] >= 0) {
-        float* row = (TRAIN ? A.out : x) + (long)tokidx[tt] * FS_C + 16 * RT * wave + 4 * kk;
-        f32x4 sacc = x1[0][tt];
-#pragma unroll
-        for (int rt = 1; rt < RT; ++rt) sacc += x1[rt][tt];
-        if (sacc[0] == 1.2345f) *(f32x4*)row = sacc;
-      }
-#else
     slice_store(TRAIN ? A.out : x, x1);      // bufA: LayerNorm2's image died with the fc1 GEMM (barrier 5)
-#endif
   }
-  if constexpr (G == 2 && FS_SKEW) {
+  if constexpr (G == 2) {
     if (grp == 0) __builtin_amdgcn_s_barrier();      // pairs with group 1's entry barrier: both groups execute the same number
   }
 }
@@ -1070,7 +981,7 @@ void fs_launch_last(const FsArgs& A, int nwg, hipStream_t s) {
 // TANTE_FS_GROUPS = 2 (tante_set_option) selects the paired form; the default is the unpaired one.  Both compute the same function, bit for
 // bit (tools/fs_ab.py asserts it).  MEASURED (round 3, one box, interleaved rounds, cfg2 B = 8): the paired form is 1.2 - 2.3 us SLOWER per
 // launch (T 36.3 -> 38.1, H 35.3 -> 37.5, W 34.3 -> 36.5 us), also with the weight stream served from L1 and without the x loads / stores
-// (timing builds: 26.0 -> 26.8 us), and with the two groups in step instead of offset (-DFS_SKEW=0: 34.0 -> 35.3 us).  Anti-phase by
+// (timing builds: 26.0 -> 26.8 us), and with the two groups in step instead of offset (same barriers, no offset, no alignment barriers: 34.0 -> 35.3 us).  Anti-phase by
 // construction buys nothing: what the launch waits for is not the matrix pipe being idle in vector phases.
 // the training form exists for the 4-wave kernels (sequences up to 64 tokens: every shipped axis letter); longer ones train unfused
 template <int TPS, int NTT, int NW>

@@ -117,24 +117,16 @@ __device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u 
 // of the kernel's compute (MI355X_MICROARCH.md, kernel boundary; measured here: 33.5 MB of block-kernel output = 5.6 us, its timing build
 // without the store).  A store with sc0 sc1 goes to memory as it is issued, so results that are final when they are written -- a kernel's
 // output rows, the saved tensors of a training forward -- stream out under the rest of the kernel and the release finds nothing to do.
-// Only for data no other workgroup of the SAME launch reads back.  (-DTANTE_PLAIN_STORES: ordinary stores, for A/B.)
+// Only for data no other workgroup of the SAME launch reads back.
 __device__ __forceinline__ void st_wt16(void* p, const u32x4& v) {
-#ifdef TANTE_PLAIN_STORES
-  *(u32x4*)p = v;
-#else
   // (s_nop 1: a VALU write to the data registers of a store wider than 64 bits needs wait states behind it; the compiler's hazard
   // recognizer covers its own stores, not the inside of an asm statement -- without it a GELU that reused these registers right behind
   // the store corrupted the saved pre-activations of the training forward)
   asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-#endif
 }
 __device__ __forceinline__ void st_wt16(void* p, const f32x4& v) { st_wt16(p, __builtin_bit_cast(u32x4, v)); }
 __device__ __forceinline__ void st_wt8(void* p, const u32x2& v) {
-#ifdef TANTE_PLAIN_STORES
-  *(u32x2*)p = v;
-#else
   asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-#endif
 }
 
 // ---- activations (always evaluated in fp32) ---------------------------------------------------

@@ -35,9 +35,7 @@ __host__ __device__ constexpr int x_img(int ntt) { return 16 * ntt * XROW; }
 __host__ __device__ constexpr int x_lds(int ntt) { return 2 * x_img(ntt) + 8 * 16 * ntt * 2 * 4 + (ntt < 4 ? 8 * ntt * 1024 : 0); }
 // weight ring, k-steps ahead: 2 where a k-step is 16 MFMAs per wave (64 tokens); 6 for the 16-token form, whose k-step is 4 MFMAs = 64
 // clocks against an L2 round trip of many hundred (its 129 registers leave the room)
-#ifndef X_PF_SMALL
-#define X_PF_SMALL 6
-#endif
+constexpr int X_PF_SMALL = 6;
 __host__ __device__ constexpr int x_pf(int ntt) { return ntt >= 4 ? 2 : X_PF_SMALL; }
 constexpr int XMAT = XC * XC * 2;    // one packed matrix: 512 KiB
 
@@ -64,7 +62,7 @@ __host__ __device__ constexpr long x_woff(int g, int j) { return (long)(g >> 4) 
 template <int M, int GEND, int NTT>
 __device__ __forceinline__ void x_gemm(const FsW& wu, u32x4 (&wb)[x_pf(NTT) + 1][4], const unsigned (&ab)[4], f32x4 (&acc)[4][NTT]) {
   constexpr int XPF = x_pf(NTT);
-  mfma_stream<16 * NTT, 4>(
+  mfma_stream<16 * NTT, 4, true>(
       [&](auto ic) {
         constexpr int i = decltype(ic)::value, ks = i / NTT, tt = i % NTT;
         return LdsAddr<tt * 16384 + (ks >> 2) * 256>{ab[ks & 3]};

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(512, 2) void enc23_kernel(const EncArgs A) {
       f32x4 acc[NH2];
 #pragma unroll
       for (int ns = 0; ns < NH2; ++ns) acc[ns] = *(const f32x4*)(bias2 + (hh * NH2 + ns) * 16 + kk * 4);
-      mfma_stream<NH2 * G::KB2, 4>(
+      mfma_stream<NH2 * G::KB2, 4, false>(
           [&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(hh * NH2 + i % NH2) * 16 * G::CPR2 * 16>{bt2[i / NH2]}; },
           [&](auto ic, const u32x4& wf) {
             constexpr int i = decltype(ic)::value, ns = i % NH2, kb = i / NH2;
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(512, 2) void enc23_kernel(const EncArgs A) {
     f32x4 acc[2];
 #pragma unroll
     for (int ns = 0; ns < 2; ++ns) acc[ns] = *(const f32x4*)(bias3 + tg * 32 + ns * 16 + kk * 4);
-    mfma_stream<2 * G::KB3, 4>(
+    mfma_stream<2 * G::KB3, 4, false>(
         [&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(t & 1) * G::T3B + (i % 2) * 16 * G::CPR3 * 16>{bt3[i / 2]}; },
         [&](auto ic, const u32x4& wf) {
           constexpr int i = decltype(ic)::value, ns = i % 2, kb = i / 2;

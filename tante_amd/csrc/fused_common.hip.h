@@ -50,13 +50,13 @@ template <int N>
 __device__ __forceinline__ void lds_wait2(u32x4& f0, u32x4& f1) {  // one wait for two fragments
   asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(f0), "+v"(f1) : "n"(N));
 }
-template <int N, int D, class AddrF, class UseF>
+// PRIO: the wave raises its issue priority (s_setprio 1) for the length of the stream.  The block, sliced-block and CViT kernels ship
+// with it, the encoder / head / operator kernels without; every caller says which.
+template <int N, int D, bool PRIO, class AddrF, class UseF>
 __device__ __forceinline__ void mfma_stream(AddrF&& addr, UseF&& use) {
   static_assert(D <= 15 && D % 2 == 0, "lgkmcnt is a 4-bit field; fragments are consumed in pairs");
   u32x4 ring[D];
-#ifdef TANTE_MFMA_SETPRIO
-  __builtin_amdgcn_s_setprio(1);
-#endif
+  if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   static_for<(D < N ? D : N)>([&](auto ic) { ring[decltype(ic)::value] = lds_read128(addr(ic)); });
   // fragments are consumed in pairs behind ONE counted wait: the kernels that use this are bound by instruction issue, and an
@@ -75,9 +75,7 @@ __device__ __forceinline__ void mfma_stream(AddrF&& addr, UseF&& use) {
     lds_wait<0>(c0);
     use(std::integral_constant<int, N - 1>{}, c0);
   }
-#ifdef TANTE_MFMA_SETPRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
+  if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
 }
 
 __device__ __forceinline__ u32x4 pack8(const f32x4& a, const f32x4& b) {

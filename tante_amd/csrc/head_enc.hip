@@ -25,10 +25,6 @@
 #include "fused_common.hip.h"
 #include <stdlib.h>
 
-#if defined(HE_EXP_GELU_ID) && !defined(TANTE_ABLATE)
-#error "HE_EXP_GELU_ID is a timing experiment (wrong results on purpose): build it with -DTANTE_ABLATE, never into the product library"
-#endif
-
 namespace {
 
 constexpr int HE_HB = 1024;                          // bias block of a tile (one LDS-DMA pass)
@@ -79,11 +75,7 @@ __device__ __forceinline__ void he_glds(const char* __restrict__ g, char* l, int
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + off + lane * 16),
                                      (__attribute__((address_space(3))) void*)(l + off), 16, 0, 0);
 }
-#ifdef HE_EXP_GELU_ID      // timing experiment only (wrong results): the whole price of the GELU arithmetic (round-5 verdict item 4)
-__device__ __forceinline__ f32x4 he_gelu(const f32x4& v) { return v; }
-#else
 __device__ __forceinline__ f32x4 he_gelu(const f32x4& v) { return gelu_poly4<false>(v); }
-#endif
 // agent-scope (sc1) 16-byte accesses to the hand-off buffer: the load misses this CU's L1, the store is written through (and waits the
 // two states a VALU write to the data registers of a >64-bit store needs behind it: common.hip.h, st_wt16)
 __device__ __forceinline__ u32x4 he_ld_agent(const u32x4* p) {
@@ -108,10 +100,7 @@ __device__ __forceinline__ void he_pin(f32x4& v) { asm volatile("" : "+v"(v)); }
 template <int NWV, int TT, bool ENC, int NDT>
 __global__ __launch_bounds__(NWV * 64, 1) void head_enc_kernel(const HeArgs A) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifndef HE_RING
-#define HE_RING 4
-#endif
-  constexpr int RD = TT == 2 ? HE_RING : 4;      // fragments in flight per wave in the LDS read ring
+  constexpr int RD = 4;      // fragments in flight per wave in the LDS read ring
   char* w3s = smem;
   char* w1s = smem + HE_T3;
   char* w2s = w1s + HE_T1;
@@ -240,7 +229,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void head_enc_kernel(const HeArgs A) {
 #pragma unroll
           for (int tt = 0; tt < TT; ++tt) acc[tt][ns] = b;
         }
-        mfma_stream<32, RD>([&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(4 * hh + i % 4) * 8192>{a1[i / 4]}; },
+        mfma_stream<32, RD, false>([&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(4 * hh + i % 4) * 8192>{a1[i / 4]}; },
                            [&](auto ic, const u32x4& wf) {
                              constexpr int i = decltype(ic)::value;
 #pragma unroll
@@ -293,7 +282,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void head_enc_kernel(const HeArgs A) {
 #pragma unroll
         for (int tt = 0; tt < TT; ++tt) acc2[tt][ns] = b;
       }
-      mfma_stream<16, RD>([&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<q * HE_T2 + (i % 4) * 4096>{a2[i / 4]}; },
+      mfma_stream<16, RD, false>([&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<q * HE_T2 + (i % 4) * 4096>{a2[i / 4]}; },
                          [&](auto ic, const u32x4& wf) {
                            constexpr int i = decltype(ic)::value;
 #pragma unroll
@@ -312,7 +301,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void head_enc_kernel(const HeArgs A) {
 #pragma unroll
         for (int tt = 0; tt < TT; ++tt) d[tt][ns] = b;
       }
-      mfma_stream<2 * NDT, RD>([&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(i % NDT) * 2048>{a3[i / NDT]}; },
+      mfma_stream<2 * NDT, RD, false>([&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(i % NDT) * 2048>{a3[i / NDT]}; },
                               [&](auto ic, const u32x4& wf) {
                                 constexpr int i = decltype(ic)::value;
 #pragma unroll
@@ -391,7 +380,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void head_enc_kernel(const HeArgs A) {
 #pragma unroll
           for (int tt = 0; tt < TT; ++tt) acc[tt][ns] = b;
         }
-        mfma_stream<4 * KB1, RD>([&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(i % 4) * 2048>{ae1[i / 4]}; },
+        mfma_stream<4 * KB1, RD, false>([&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(i % 4) * 2048>{ae1[i / 4]}; },
                                 [&](auto ic, const u32x4& wf) {
                                   constexpr int i = decltype(ic)::value;
 #pragma unroll
@@ -419,7 +408,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void head_enc_kernel(const HeArgs A) {
 #pragma unroll
           for (int tt = 0; tt < TT; ++tt) acc[tt][ns] = b;
         }
-        mfma_stream<32, RD>([&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(4 * hh + i % 4) * 8192>{a1[i / 4]}; },
+        mfma_stream<32, RD, false>([&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(4 * hh + i % 4) * 8192>{a1[i / 4]}; },
                            [&](auto ic, const u32x4& wf) {
                              constexpr int i = decltype(ic)::value, kb = i / 4;
 #pragma unroll
@@ -496,7 +485,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void head_enc_kernel(const HeArgs A) {
         for (int b = 0; b < 4; ++b) he_pin(hs[t][tt][b]);          // (asm-volatile loads: the optimiser must see them defined here)
       static_for<2>([&](auto hc) {
         constexpr int hh = decltype(hc)::value;
-        mfma_stream<32, RD>([&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(8 * hh + i % 8) * 4096>{a3e[t % 2][i / 8]}; },
+        mfma_stream<32, RD, false>([&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(8 * hh + i % 8) * 4096>{a3e[t % 2][i / 8]}; },
                            [&](auto ic, const u32x4& wf) {
                              constexpr int i = decltype(ic)::value;
 #pragma unroll

@@ -576,7 +576,7 @@ __global__ __launch_bounds__(XWAVES * 64, 2) void xattn_mfma_kernel(const unsign
         for (int bb = 0; bb < NB; ++bb) kc[bb] = kb[bb] + lrow * ROWB;
         f32x4 s[XQG][8];
         // S^T tiles: 8 NB K fragments (tile t, dim block bb), each feeding both query groups, through the counted LDS read ring
-        mfma_stream<8 * NB, 4>(
+        mfma_stream<8 * NB, 4, false>(
             [&](auto ic) { constexpr int i = decltype(ic)::value; return LdsAddr<(i / NB) * 16 * ROWB>{kc[i % NB]}; },
             [&](auto ic, const u32x4& kf) {
               constexpr int i = decltype(ic)::value, t = i / NB, bb = i % NB;

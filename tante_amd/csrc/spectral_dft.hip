@@ -186,11 +186,11 @@ __global__ void spectral_mix_kernel(const float2* __restrict__ X, const float* _
 
 // ---- D: inverse column DFT.  block = (image n, DFT_D_HB rows h); a thread owns (o, j), keeps its 2 m1 coefficients in registers and walks
 // the block's rows.  Z[n][h][k][o] (o innermost: the A operand rows of kernel E are contiguous), k = j (real part) | m2 + j (imaginary).
+// DFT_D_HB = rows per workgroup: a thread's pass is a serial chain over its rows (8 rows: 31 us per launch at cfg5 on 128 workgroups;
+// 4 / 2 / 1 rows: cfg5 3 080 -> 3 124 / 3 150 / 3 137 frames/s, profiles/r05_ab_fno_idft_cols_rows.log)
+constexpr int DFT_D_HB = 2;
 template <int M1X2>
 __global__ __launch_bounds__(256) void idft_cols_kernel(const float2* __restrict__ Y, int H, int Cout, int m2, float* __restrict__ Z) {
-#ifndef DFT_D_HB
-#define DFT_D_HB 2      // rows per workgroup: a thread's pass is a serial chain over its rows (8 rows: 31 us per launch at cfg5 on 128 workgroups;
-#endif                  // 4 / 2 / 1 rows: cfg5 3 080 -> 3 124 / 3 150 / 3 137 frames/s, profiles/r05_ab_fno_idft_cols_rows.log)
   constexpr int HB = DFT_D_HB;
   __shared__ float2 cs[HB][M1X2];
   const int m1 = M1X2 / 2;

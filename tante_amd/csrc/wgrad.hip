@@ -604,10 +604,8 @@ struct WgJobs {
   WgJob j[WJOBS];
   int n;
 };
-#ifndef WGJ_NBUF
-#define WGJ_NBUF 4      // ring depth of the jobs kernel (x 16 KB) ...
-#define WGJ_OCC 2       // ... and the workgroups per CU it is sized for (192 VGPRs; 3 / 3 and 2 / 4 spill: train step 10.8 / 18.4 against 8.58 ms)
-#endif
+constexpr int WGJ_NBUF = 4;      // ring depth of the jobs kernel (x 16 KB) ...
+constexpr int WGJ_OCC = 2;       // ... and the workgroups per CU it is sized for (192 VGPRs; 3 / 3 and 2 / 4 spill: train step 10.8 / 18.4 against 8.58 ms)
 __global__ __launch_bounds__(256, WGJ_OCC) void wgrad_tr_jobs_kernel(const WgJobs JB) {
   int k = 0;
 #pragma unroll

@@ -410,6 +410,34 @@ def test_library_option_allow_list_matches_the_sources():
     assert "TANTE_CVIT_FUSED" in host and "TANTE_CVIT_CHAIN_QKV" in host and "TANTE_TRAIN_FUSED_BLOCK_BWD" in host
 
 
+def test_kernel_sources_hold_the_shipped_form_only():
+    """The sources under csrc/ say what ships: the only preprocessor conditionals are include guards and tests of TANTE_ABLATE (the
+    diagnostic build's stamps and ablations), and build.py passes compiler flags, no -D.  An experiment lives on a branch or behind
+    TANTE_ABLATE, not as a second version of a kernel behind a macro the product never defines."""
+    import glob
+    from tante_amd import build as B
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    files = sorted(glob.glob(os.path.join(root, "tante_amd", "csrc", "*")))
+    assert {os.path.basename(f) for f in files} >= set(B.SOURCES)
+    cond = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif)\b(.*)$")
+    stray = []
+    for f in files:
+        with open(f) as fh:
+            lines = fh.read().splitlines()
+        for i, line in enumerate(lines):
+            m = cond.match(line)
+            if not m or "TANTE_ABLATE" in m.group(2):
+                continue
+            name = m.group(2).split()[0] if m.group(2).split() else ""
+            guard = m.group(1) == "ifndef" and i + 1 < len(lines) and re.match(r"^\s*#\s*define\s+%s\s*$" % re.escape(name), lines[i + 1])
+            if not (guard and re.fullmatch(r"\w+_H(_|PP)?_*", name)):
+                stray.append(f"{os.path.basename(f)}:{i + 1}: {line.strip()}")
+    assert not stray, stray
+    flags = [x for fl in B.EXTRA_FLAGS.values() for x in fl]
+    assert flags and not [x for x in B.FLAGS + flags if x.startswith("-D")], B.EXTRA_FLAGS
+    assert set(B.EXTRA_FLAGS) <= set(B.SOURCES)
+
+
 def test_fno_refuses_neuralop_state_dicts_and_has_the_as_written_mode():
     """models.FNO as shipped drops its Fourier blocks' outputs (models/fno.py:48-51); the port documents that, offers
     `reference_as_written=True`, and refuses neuralop-named checkpoints instead of mis-loading them."""

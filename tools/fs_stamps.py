@@ -87,7 +87,7 @@ def main():
                   f"start offset g1-g0 {np.median(s[g1, k]) - np.median(s[~g1, k]):8.0f}")
         return
     # the two workgroups of a CU sit in hardware wave slots of different parity (HW_ID bits 3:0); the product build gives the odd ones
-    # issue priority (FS_PRIO): how far apart do the two run?
+    # issue priority (s_setprio 3 at the entry of block_fs_kernel): how far apart do the two run?
     odd = (hw & 1) == 1
     if odd.any() and (~odd).any():
         print(f"wave slot parity: {odd.sum()} odd / {(~odd).sum()} even; span median odd {np.median(tot[odd]):.0f} even {np.median(tot[~odd]):.0f}")

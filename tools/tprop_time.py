@@ -1,5 +1,6 @@
 """Launch time of the T-letter block kernel with and without the fused temporal propagator (cfg2: B x 4 x 32 x 32 tokens, C = 256), back to back;
-TANTE_LIB selects a timing-experiment build (tools/build_variant.sh ... block_sliced.hip "-DFS_EXP_TPROP_NO_STORE").   python tools/tprop_time.py"""
+TANTE_LIB selects another build of the library.  (The timing build -DFS_EXP_TPROP_NO_STORE this was written for was removed from the source;
+its measurement is in profiles/r04_tprop_price.log, its code in history.)   python tools/tprop_time.py"""
 import os, statistics, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
