@@ -628,6 +628,18 @@ int tante_enc23_fused(const void* h1, int n_img, int Hp, int Wp, int C, const vo
  * (b, f) with f < frames, and image (b, f) is written to the frame-major row block (f * (n_img / frames) + b) * Hp * Wp of out
  * (the cache tante_axis_hw_film reads). */
 int tante_enc23_frames(const void* h1, int n_img, int frames, int Hp, int Wp, int C, const void* enc_stream, float* out, void* stream);
+/* The rollout's first window straight from the channels-last batch: raw (B, T, H, W, D) fp32 as the datamodule yields it -> z, the
+ * (T, B, H/8 * W/8, C) frame cache tante_format_input + tante_gemm (stage 1) + tante_enc23_frames(frames = T) produce, byte for byte, and
+ * the nan_to_num-ed channels-first frame of slot T - 1 at frame_out + b * frame_bstride (elements); the channels-first copies of slots
+ * 0 .. T - 2 are not written.  Two launches: stage 1 reads the batch where it lies (its k order, paddings and roundings are those of
+ * the tante_gemm path), then the stage 2 + 3 kernel.  enc1_stream: tante_pack_enc1_raw of conv 1 (C/4, D, 2, 2); h1: B T H/2 W/2 C/4
+ * bf16 of scratch.  C = 256, 4 D <= 64, H % 8 == W % 8 == 0, raw 16-byte aligned.  (Added at ABI 14 without a bump.)
+ * Option "TANTE_RAW_ENCODE_ONE_LAUNCH" = 1: stage 1 inside the stage 2 + 3 kernel, one launch, h1 unused; the same bits, measured slower. */
+int tante_enc1_raw_supported(int C, int D);
+int64_t tante_enc1_raw_stream_bytes(void);
+int tante_pack_enc1_raw(const float* w1, const float* b1, int C, int D, void* enc1_stream, void* stream);
+int tante_encode_window_raw(const float* raw, int B, int T, int H, int W, int D, int C, const void* enc1_stream, const void* enc_stream,
+                            void* h1, float* z, float* frame_out, int64_t frame_bstride, void* stream);
 
 /* ---- losses / metrics / optimiser step of the harness ------------------------------------------------
  * pred is addressed as pred[b*pb + t*pt + s*ps + c*pc] (so the channels-first rollout buffer needs no permute copy),

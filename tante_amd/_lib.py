@@ -151,6 +151,10 @@ SIGNATURES = {
     "tante_pack_enc23": ([c_vp] * 4 + [c_i32, c_vp, c_vp], c_i32),
     "tante_enc23_fused": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp], c_i32),
     "tante_enc23_frames": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp], c_i32),
+    "tante_enc1_raw_supported": ([c_i32, c_i32], c_i32),
+    "tante_enc1_raw_stream_bytes": ([], c_i64),
+    "tante_pack_enc1_raw": ([c_vp, c_vp, c_i32, c_i32, c_vp, c_vp], c_i32),
+    "tante_encode_window_raw": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp], c_i32),
     "tante_im2col": ([c_vp, c_i32, c_i32, c_i64] + [c_i32] * 10 + [c_vp, c_i32, c_vp], c_i32),
     "tante_avgpool_nhwc": ([c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp], c_i32),
     "tante_avgpool_nhwc_bwd": ([c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp], c_i32),
@@ -271,13 +275,13 @@ LIB_OPTIONS = ("TANTE_ATTN_BWD_HG", "TANTE_ATTN_BWD_NO_SPLIT", "TANTE_ATTN_BWD_V
                "TANTE_AXIS_BLOCKS", "TANTE_AXIS_BWD_WGS", "TANTE_AXIS_CT", "TANTE_AXIS_FILM", "TANTE_AXIS_GENERIC", "TANTE_AXIS_MFMA", "TANTE_AXIS_NT", "TANTE_AXIS_WGRAD_WGS",
                "TANTE_BLOCK_KERNEL", "TANTE_COLSUM_ROWS", "TANTE_CVIT_CHAIN_TOKENS", "TANTE_ENC23_SPLIT", "TANTE_FILM_BWD_ROWS",
                "TANTE_FS_GROUPS", "TANTE_FS_HALF", "TANTE_FS_SKEW", "TANTE_FS_WAVES", "TANTE_GEMM_NO_LITE", "TANTE_GEMM_SMALLM", "TANTE_GEMM_WGS", "TANTE_HEAD_WAVES",
-               "TANTE_IM2COL_TILED", "TANTE_RESIZE_TILED", "TANTE_SPECTRAL_BF16OUT", "TANTE_SPECTRAL_DFT", "TANTE_SPECTRAL_X3", "TANTE_WGRAD_DEEP",
+               "TANTE_IM2COL_TILED", "TANTE_RAW_ENCODE_ONE_LAUNCH", "TANTE_RESIZE_TILED", "TANTE_SPECTRAL_BF16OUT", "TANTE_SPECTRAL_DFT", "TANTE_SPECTRAL_X3", "TANTE_WGRAD_DEEP",
                "TANTE_WGRAD_JOBS", "TANTE_WGRAD_JOBS_WGS", "TANTE_WGRAD_NO_SLAB", "TANTE_WGRAD_NO_TR", "TANTE_WGRAD_REDUCE_NY",
                "TANTE_WGRAD_RG", "TANTE_WGRAD_SLAB_WGS", "TANTE_WGRAD_TR_WGS", "TANTE_WGRAD_WGS", "TANTE_XATTN_GPW", "TANTE_XATTN_STREAM", "TANTE_XATTN_VALU",)
 
 
 _lib = None
-ABI_VERSION = 14     # include/tante_hip.h: bumped whenever an entry point is added or changes (round 4: 6 tante_head_enc_*, 7 tante_pos_embed_tmajor + tante_spectral_*bf16out*; round 5: 8 tante_block_bwd_fused, 9 TanteGemm.a_pad; round 6: 10 tante_tail_*, 11 tante_attention_masked_bwd, 12 tante_spectral_layer_x, tante_axis_mlp_film; round 7: 13 tante_block_fused_last; 14 tante_attention_flash*; still 14: tante_attention_flash_masked + tante_attention_flash_masked_bwd were ADDED without a bump -- nothing that existed changed its signature or meaning, so a caller built against 14 runs unchanged, and the suite pins 14 (test_abi_version_is_14); a caller that needs the two looks the symbols up; the same holds for the six tante_adaptive_* / tante_head_adaptive entries of the adaptive-step tail, for tante_cross_attention_route, and for the four tante_afno_* entries of the AFNO filter)
+ABI_VERSION = 14     # include/tante_hip.h: bumped whenever an entry point is added or changes (round 4: 6 tante_head_enc_*, 7 tante_pos_embed_tmajor + tante_spectral_*bf16out*; round 5: 8 tante_block_bwd_fused, 9 TanteGemm.a_pad; round 6: 10 tante_tail_*, 11 tante_attention_masked_bwd, 12 tante_spectral_layer_x, tante_axis_mlp_film; round 7: 13 tante_block_fused_last; 14 tante_attention_flash*; still 14: tante_attention_flash_masked + tante_attention_flash_masked_bwd were ADDED without a bump -- nothing that existed changed its signature or meaning, so a caller built against 14 runs unchanged, and the suite pins 14 (test_abi_version_is_14); a caller that needs the two looks the symbols up; the same holds for the six tante_adaptive_* / tante_head_adaptive entries of the adaptive-step tail, for tante_cross_attention_route, for the four tante_afno_* entries of the AFNO filter, and for tante_encode_window_raw with its three tante_*enc1_raw* helpers)
 
 
 def lib():

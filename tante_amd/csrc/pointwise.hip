@@ -1378,3 +1378,4 @@ extern "C" int tante_set_option(const char* name, int value) {
 }
 extern "C" int tante_get_option(const char* name, int dflt) { return name ? tante_opt(name, dflt) : dflt; }
 extern "C" int tante_abi_version(void) { return 14; }      // = tante_amd/_lib.py ABI_VERSION; bumped with every added / changed entry point
+// (still 14 with tante_encode_window_raw and its tante_*enc1_raw* helpers: purely additive, and the suite pins 14)

@@ -732,6 +732,39 @@ def enc23_frames(h1: torch.Tensor, n_img: int, frames: int, Hp: int, Wp: int, C_
     return out
 
 
+def enc1_raw_supported(C_: int, D: int) -> bool:
+    return bool(L.lib().tante_enc1_raw_supported(C_, D))
+
+
+def pack_enc1_raw(params: Sequence[torch.Tensor], C_: int, D: int) -> torch.Tensor:
+    """params = (conv1.w, conv1.b) -> the stage-1 weight stream of encode_window_raw."""
+    ps = [p.detach() for p in params]
+    _dev(*ps)
+    st = torch.empty(L.lib().tante_enc1_raw_stream_bytes(), dtype=torch.uint8, device=ps[0].device)
+    L.check(L.lib().tante_pack_enc1_raw(_p(ps[0]), _p(ps[1]), C_, D, _p(st), _stream()), "tante_pack_enc1_raw")
+    return st
+
+
+def encode_window_raw(raw: torch.Tensor, C_: int, enc1_stream: torch.Tensor, enc_stream: torch.Tensor, z: torch.Tensor,
+                      frame_out: torch.Tensor) -> torch.Tensor:
+    """raw (B, T, H, W, D) fp32 channels-last -> z (T, B, H/8 * W/8, C) fp32, the frame cache of the window, and frame_out (B, D, H, W)
+    (any batch stride), the nan_to_num-ed channels-first frame of slot T - 1: the bits of tante_format_input + the encoder's
+    forward_frames, without the channels-first copies of slots 0 .. T - 2."""
+    _dev(raw, enc1_stream, enc_stream, z)
+    if not frame_out.is_cuda:
+        raise RuntimeError("tante_amd kernels need CUDA/HIP tensors (no CPU fallback)")
+    B, T, H, W, D = raw.shape
+    if raw.dtype != torch.float32 or not raw.is_contiguous() or z.dtype != torch.float32 or not z.is_contiguous() \
+            or tuple(z.shape) != (T, B, (H // 8) * (W // 8), C_):
+        raise RuntimeError("encode_window_raw: contiguous fp32 (B, T, H, W, D) batch and (T, B, Hp*Wp, C) cache expected")
+    if frame_out.dtype != torch.float32 or tuple(frame_out.shape) != (B, D, H, W) or frame_out.stride()[1:] != (H * W, W, 1):
+        raise RuntimeError("encode_window_raw: frame_out must be a (B, D, H, W) fp32 view with contiguous frames")
+    h1 = torch.empty(B * T * (H // 2) * (W // 2), C_ // 4, dtype=torch.bfloat16, device=raw.device)
+    L.check(L.lib().tante_encode_window_raw(_p(raw), B, T, H, W, D, C_, _p(enc1_stream), _p(enc_stream), _p(h1), _p(z), _p(frame_out),
+                                            frame_out.stride(0), _stream()), "tante_encode_window_raw")
+    return z
+
+
 # ---- general conv stages, spectral layer, CViT operators (operators.hip) ---------------------------------------------------------
 def im2col(x: torch.Tensor, nchw: bool, n_img: int, C_: int, H: int, W: int, kh: int, kw: int, sh: int, sw: int, ph: int, pw: int,
            korder: int, out_dtype: torch.dtype) -> torch.Tensor:

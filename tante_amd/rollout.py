@@ -21,6 +21,10 @@ NO_FUSED_FORMAT = _O.register("TANTE_NO_FUSED_FORMAT", False, __name__, "NO_FUSE
 # B = 4 and 8 % at B = 1 -- its workgroups take CU slots from block launches that need the whole chip for their one resident round, and
 # the fork / join is tens of microseconds of a small-batch rollout.  Opt-in now.
 SIDE_STREAM = _O.register("TANTE_SIDE_STREAM", False, __name__, "SIDE_STREAM")
+# the first window of a rollout encoded straight from the channels-last batch (kernels.encode_window_raw): the encoder's first stage reads
+# the batch where it lies and only slot T - 1 -- the one frame a call reads as pixels -- is written channels-first.  0: tante_format_input
+# of all T frames, then the encoder launches on them (same bits).
+RAW_ENCODE = _O.register("TANTE_RAW_ENCODE", True, __name__, "RAW_ENCODE")
 
 
 class DefaultChannelsFirstFormatter:
@@ -85,6 +89,14 @@ def _rollout_in_place(model, x: torch.Tensor, n_steps: int, raw_input: torch.Ten
     ol = model.output_length
     n_calls = -(-n_steps // ol)
     buf = torch.empty(B, T + n_calls * ol, *frame_shape, dtype=torch.float32, device=dev)
+    if raw_input is not None and _raw_encode_route(model, raw_input):
+        # the window's pixels are read by the encoder's first stage (here, from the batch) and at slot T - 1 (the Taylor base of the
+        # calls): slots 0 .. T - 2 of buf stay unwritten, and nothing reads them
+        from .attn_backbone import resolve_compute
+        HW, C_ = model.H_p * model.W_p, model.C
+        z = torch.empty(T + n_calls * ol, B, HW, C_, dtype=torch.float32, device=dev)
+        model.encoder.forward_window_raw(raw_input, resolve_compute(model.compute), z[:T], buf[:, T - 1])
+        return _rollout_cached(model, buf, z, T, n_calls, n_steps, encoded=T)
     if raw_input is not None:     # the default formatter's permute + nan_to_num, fused into the one copy that fills the buffer
         from . import _lib as L
         from . import kernels as K
@@ -97,23 +109,40 @@ def _rollout_in_place(model, x: torch.Tensor, n_steps: int, raw_input: torch.Ten
         # every frame (input or predicted) is encoded once, when it first enters a window; the windows read the frame-major cache
         HW, C_ = model.H_p * model.W_p, model.C
         z = torch.empty(T + n_calls * ol, B, HW, C_, dtype=torch.float32, device=dev)
-        encoded = 0
-        # one output frame per call: the launch that writes the predicted frame also writes its encoding for the next call's window
-        # (csrc/head_enc.hip) -- only the initial window goes through the encoder kernels
-        tail = ol == 1 and model.tail_fused_supported() and not NO_TAIL_ENC
-        for s in range(n_calls):
-            need = s * ol + T
-            if need > encoded:                       # the first call encodes the whole window, later calls the `ol` new frames
-                model.encode_frames(buf[:, encoded: need], z[encoded: need])
-            encoded = need
-            nxt = z[T + s] if (tail and s + 1 < n_calls) else None
-            model(buf[:, s * ol: s * ol + T], out=buf[:, T + s * ol: T + (s + 1) * ol], enc_cache=(z[s * ol:], B * HW * C_, HW * C_),
-                  **({"enc_next": nxt} if nxt is not None else {}))
-            if nxt is not None:
-                encoded = need + 1
-        return buf[:, T: T + n_steps]
+        return _rollout_cached(model, buf, z, T, n_calls, n_steps, encoded=0)
     for s in range(n_calls):
         model(buf[:, s * ol: s * ol + T], out=buf[:, T + s * ol: T + (s + 1) * ol])
+    return buf[:, T: T + n_steps]
+
+
+def _raw_encode_route(model, raw: torch.Tensor) -> bool:
+    """The first window goes through kernels.encode_window_raw: the switch is on, the model runs the fused frame cache (bf16, the
+    stage 2 + 3 encoder kernel at patch_scale 8 without overlap), 4 D <= 64 and the batch is 16-byte aligned."""
+    if not RAW_ENCODE or NO_ENC_CACHE or not model._enc_cache_fused():
+        return False
+    from .attn_backbone import resolve_compute
+    return bool(model.encoder.raw_window_supported(resolve_compute(model.compute)) and raw.data_ptr() % 16 == 0
+                and raw.shape[2] % 8 == 0 and raw.shape[3] % 8 == 0)
+
+
+def _rollout_cached(model, buf: torch.Tensor, z: torch.Tensor, T: int, n_calls: int, n_steps: int, encoded: int) -> torch.Tensor:
+    """The calls of _rollout_in_place on the frame cache z, of which the first `encoded` frames exist."""
+    B = buf.shape[0]
+    ol = model.output_length
+    HW, C_ = model.H_p * model.W_p, model.C
+    # one output frame per call: the launch that writes the predicted frame also writes its encoding for the next call's window
+    # (csrc/head_enc.hip) -- only the initial window goes through the encoder kernels
+    tail = ol == 1 and model.tail_fused_supported() and not NO_TAIL_ENC
+    for s in range(n_calls):
+        need = s * ol + T
+        if need > encoded:                       # the first call encodes the whole window, later calls the `ol` new frames
+            model.encode_frames(buf[:, encoded: need], z[encoded: need])
+        encoded = need
+        nxt = z[T + s] if (tail and s + 1 < n_calls) else None
+        model(buf[:, s * ol: s * ol + T], out=buf[:, T + s * ol: T + (s + 1) * ol], enc_cache=(z[s * ol:], B * HW * C_, HW * C_),
+              **({"enc_next": nxt} if nxt is not None else {}))
+        if nxt is not None:
+            encoded = need + 1
     return buf[:, T: T + n_steps]
 
 

@@ -160,6 +160,25 @@ class enc_CNN(nn.Module):
         st = self._cache.get(-3, params, lambda: K.pack_enc23(params, self.embed_dim))
         return K.enc23_frames(h1, n_img, F, H // 8, W // 8, self.embed_dim, st, z)
 
+    def raw_window_supported(self, compute: int) -> bool:
+        """forward_window_raw applies: the fused bf16 stages at patch_scale 8 without overlap, and a first stage with K = 4 D <= 64."""
+        return bool(self.fuses_23(compute) and K.enc1_raw_supported(self.embed_dim, self.chans[0]))
+
+    def forward_window_raw(self, raw: torch.Tensor, compute: int, z: torch.Tensor, frame_out: torch.Tensor) -> torch.Tensor:
+        """raw (B, T, H, W, D) fp32 channels-last, as the datamodule yields it -> z (T, B, Hp*Wp, C): what forward_frames gives for the
+        formatted window, bit for bit; frame_out (B, D, H, W) receives the formatted frame of slot T - 1 (kernels.encode_window_raw)."""
+        B, T, H, W, D = raw.shape
+        if (H, W) != (self.H, self.W) or D != self.chans[0]:
+            raise ValueError(f"encoder built for {self.chans[0]} fields at {(self.H, self.W)}, got {tuple(raw.shape)}")
+        if not self.raw_window_supported(compute):
+            raise RuntimeError("forward_window_raw needs the fused stage 2 + 3 encoder path and 4 D <= 64")
+        c1, c23 = self.enc_conv_1.conv, [self.enc_conv_2.conv, self.enc_conv_3.conv]
+        p1 = [c1.weight, c1.bias]
+        st1 = self._cache.get(-6, p1, lambda: K.pack_enc1_raw(p1, self.embed_dim, D))
+        params = [q for c in c23 for q in (c.weight, c.bias)]
+        st = self._cache.get(-3, params, lambda: K.pack_enc23(params, self.embed_dim))
+        return K.encode_window_raw(raw, self.embed_dim, st1, st, z, frame_out)
+
     def forward_tokens(self, inp: torch.Tensor, compute: int, film: Optional[tuple], item_stride: Optional[int] = None,
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """inp (B,T,D,H,W) fp32 -> tokens (B*T*Hp*Wp, C) fp32; `film` = (a, b, s_emb, T, HW) is applied in the
