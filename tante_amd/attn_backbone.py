@@ -370,27 +370,24 @@ class Attn_Backbone(nn.Module):
         query still sees all T keys) and the H / W / L letters after it run on the (b, T - 1) planes alone.  The slot-(T - 1) rows come out
         bit for bit as on the full path; the other slots are left part-way (not meaningful).  Any other backbone takes the full path."""
         T, H, W, C_ = self.T, self.H, self.W, self.C
-        vp, hp, tp = self.vertical_propagator, self.horizontal_propagator, self.temporal_propagator
+        vp, hp, tp = ((p[0].weight, p[0].bias, p[2].weight, p[2].bias)      # (w1, b1, w2, b2) of each axis propagator
+                      for p in (self.vertical_propagator, self.horizontal_propagator, self.temporal_propagator))
         if film_frames is not None:
             import ctypes as C
             fr, _keep, fa, fb, se = film_frames
             L.check(L.lib().tante_axis_mlp_film(x.data_ptr(), C.byref(fr), fa.data_ptr(), fb.data_ptr(), se.data_ptr(), B, T, H, W * C_, C_,
-                                                vp[0].weight.data_ptr(), vp[0].bias.data_ptr(), vp[2].weight.data_ptr(), vp[2].bias.data_ptr(),
-                                                K._stream()), "tante_axis_mlp_film")
-            K.axis_mlp(x, B * T * H, W, C_, hp[0].weight, hp[0].bias, hp[2].weight, hp[2].bias, compute)      # l.142-143
+                                                *(q.data_ptr() for q in vp), K._stream()), "tante_axis_mlp_film")
+            K.axis_mlp(x, B * T * H, W, C_, *hp, compute)      # l.142-143
         elif x_in is not None:
-            K.axis_hw_oop(x_in, x, B * T, H, W, C_, (vp[0].weight, vp[0].bias, vp[2].weight, vp[2].bias),
-                          (hp[0].weight, hp[0].bias, hp[2].weight, hp[2].bias), compute)
+            K.axis_hw_oop(x_in, x, B * T, H, W, C_, vp, hp, compute)
         elif film_src is not None:
             z, ts, bs, film = film_src
-            K.axis_hw_film(x, z, ts, bs, film, B * T, H, W, C_, (vp[0].weight, vp[0].bias, vp[2].weight, vp[2].bias),
-                           (hp[0].weight, hp[0].bias, hp[2].weight, hp[2].bias), compute)
+            K.axis_hw_film(x, z, ts, bs, film, B * T, H, W, C_, vp, hp, compute)
         elif K.axis_hw_supported(H, W, C_, compute):      # both axes in one pass over x, contractions on MFMA     l.140-143
-            K.axis_hw(x, B * T, H, W, C_, (vp[0].weight, vp[0].bias, vp[2].weight, vp[2].bias),
-                      (hp[0].weight, hp[0].bias, hp[2].weight, hp[2].bias), compute)
+            K.axis_hw(x, B * T, H, W, C_, vp, hp, compute)
         else:
-            K.axis_mlp(x, B * T, H, W * C_, vp[0].weight, vp[0].bias, vp[2].weight, vp[2].bias, compute)      # l.140-141
-            K.axis_mlp(x, B * T * H, W, C_, hp[0].weight, hp[0].bias, hp[2].weight, hp[2].bias, compute)      # l.142-143
+            K.axis_mlp(x, B * T, H, W * C_, *vp, compute)      # l.140-141
+            K.axis_mlp(x, B * T * H, W, C_, *hp, compute)      # l.142-143
         # l.144-145: the temporal propagator -- inside the first block's launch when that block is a T letter on the fused kernel (the four
         # time steps of a sequence are the four lane groups of its row loads), a launch of its own otherwise
         tprop = None
@@ -398,7 +395,7 @@ class Attn_Backbone(nn.Module):
                 and self.blocks[0].takes_tprop(T, compute)):
             tprop = self._packed_tprop()
         else:
-            K.axis_mlp(x, B, T, H * W * C_, tp[0].weight, tp[0].bias, tp[2].weight, tp[2].bias, compute)
+            K.axis_mlp(x, B, T, H * W * C_, *tp, compute)
         jl = self._last_slot_plan(B, compute) if last_slot_only else None
         ci = 0
         for i, axis in enumerate(self.attn_axes):

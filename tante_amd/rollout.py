@@ -11,6 +11,8 @@ from typing import Dict, Tuple
 import torch
 
 from . import options as _O
+from . import route as _R
+from .attn_backbone import resolve_compute
 
 # A/B switches (tante_amd.set_option): each falls back to the form the default replaced
 NO_ENC_CACHE = _O.register("TANTE_NO_ENC_CACHE", False, __name__, "NO_ENC_CACHE")          # window-by-window encoder
@@ -76,10 +78,19 @@ def _side_stream(device: torch.device) -> "torch.cuda.Stream":
     return st
 
 
-def _rollout_in_place(model, x: torch.Tensor, n_steps: int, raw_input: torch.Tensor = None) -> torch.Tensor:
+def _plan(model, raw: torch.Tensor = None, out_T=None) -> _R.RolloutRoute:
+    """route.plan_rollout under the model's compute mode and the switches above, as they are now."""
+    return _R.plan_rollout(model, resolve_compute(model.compute), raw, out_T, raw_encode=RAW_ENCODE, no_enc_cache=NO_ENC_CACHE,
+                           no_tail_enc=NO_TAIL_ENC, no_fused_format=NO_FUSED_FORMAT)
+
+
+def _rollout_in_place(model, x: torch.Tensor, n_steps: int, raw_input: torch.Tensor = None, plan: _R.RolloutRoute = None) -> torch.Tensor:
     """The reference's loop without its copies: one (B, T + frames, D, H, W) buffer holds the input window and every
     predicted frame; each model call reads its window in place (strided view) and writes its prediction into the next
-    slots, so `torch.cat([moving[:, k:], y])` and the per-step output concatenation disappear."""
+    slots, so `torch.cat([moving[:, k:], y])` and the per-step output concatenation disappear.  `plan` (route.plan_rollout) says how the
+    first window arrives, whether every frame is encoded once into a frame-major cache the windows read, and whether the launch that
+    writes a predicted frame also writes its encoding (csrc/head_enc.hip: then only the initial window goes through the encoder)."""
+    plan = plan or _plan(model, raw_input)
     if raw_input is not None:     # (B, T, H, W, D) channels-last, as the datamodule yields it
         B, T = raw_input.shape[:2]
         frame_shape, dev = (raw_input.shape[4], raw_input.shape[2], raw_input.shape[3]), raw_input.device
@@ -88,16 +99,16 @@ def _rollout_in_place(model, x: torch.Tensor, n_steps: int, raw_input: torch.Ten
         frame_shape, dev = tuple(x.shape[2:]), x.device
     ol = model.output_length
     n_calls = -(-n_steps // ol)
+    HW, C_ = model.H_p * model.W_p, model.C
     buf = torch.empty(B, T + n_calls * ol, *frame_shape, dtype=torch.float32, device=dev)
-    if raw_input is not None and _raw_encode_route(model, raw_input):
+    z = torch.empty(T + n_calls * ol, B, HW, C_, dtype=torch.float32, device=dev) if plan.cache else None
+    encoded = 0                   # frames of the cache that exist
+    if plan.first == "raw":
         # the window's pixels are read by the encoder's first stage (here, from the batch) and at slot T - 1 (the Taylor base of the
         # calls): slots 0 .. T - 2 of buf stay unwritten, and nothing reads them
-        from .attn_backbone import resolve_compute
-        HW, C_ = model.H_p * model.W_p, model.C
-        z = torch.empty(T + n_calls * ol, B, HW, C_, dtype=torch.float32, device=dev)
         model.encoder.forward_window_raw(raw_input, resolve_compute(model.compute), z[:T], buf[:, T - 1])
-        return _rollout_cached(model, buf, z, T, n_calls, n_steps, encoded=T)
-    if raw_input is not None:     # the default formatter's permute + nan_to_num, fused into the one copy that fills the buffer
+        encoded = T
+    elif plan.first == "format":  # the default formatter's permute + nan_to_num, fused into the one copy that fills the buffer
         from . import _lib as L
         from . import kernels as K
         Bq, Tq, H, W, D = raw_input.shape
@@ -105,44 +116,18 @@ def _rollout_in_place(model, x: torch.Tensor, n_steps: int, raw_input: torch.Ten
                 "tante_format_input")
     else:
         buf[:, :T].copy_(x)       # the formatter's 'b t h w c -> b t c h w' is materialised here, once
-    if model.enc_cache_supported() and not NO_ENC_CACHE:
-        # every frame (input or predicted) is encoded once, when it first enters a window; the windows read the frame-major cache
-        HW, C_ = model.H_p * model.W_p, model.C
-        z = torch.empty(T + n_calls * ol, B, HW, C_, dtype=torch.float32, device=dev)
-        return _rollout_cached(model, buf, z, T, n_calls, n_steps, encoded=0)
     for s in range(n_calls):
-        model(buf[:, s * ol: s * ol + T], out=buf[:, T + s * ol: T + (s + 1) * ol])
-    return buf[:, T: T + n_steps]
-
-
-def _raw_encode_route(model, raw: torch.Tensor) -> bool:
-    """The first window goes through kernels.encode_window_raw: the switch is on, the model runs the fused frame cache (bf16, the
-    stage 2 + 3 encoder kernel at patch_scale 8 without overlap), 4 D <= 64 and the batch is 16-byte aligned."""
-    if not RAW_ENCODE or NO_ENC_CACHE or not model._enc_cache_fused():
-        return False
-    from .attn_backbone import resolve_compute
-    return bool(model.encoder.raw_window_supported(resolve_compute(model.compute)) and raw.data_ptr() % 16 == 0
-                and raw.shape[2] % 8 == 0 and raw.shape[3] % 8 == 0)
-
-
-def _rollout_cached(model, buf: torch.Tensor, z: torch.Tensor, T: int, n_calls: int, n_steps: int, encoded: int) -> torch.Tensor:
-    """The calls of _rollout_in_place on the frame cache z, of which the first `encoded` frames exist."""
-    B = buf.shape[0]
-    ol = model.output_length
-    HW, C_ = model.H_p * model.W_p, model.C
-    # one output frame per call: the launch that writes the predicted frame also writes its encoding for the next call's window
-    # (csrc/head_enc.hip) -- only the initial window goes through the encoder kernels
-    tail = ol == 1 and model.tail_fused_supported() and not NO_TAIL_ENC
-    for s in range(n_calls):
-        need = s * ol + T
-        if need > encoded:                       # the first call encodes the whole window, later calls the `ol` new frames
-            model.encode_frames(buf[:, encoded: need], z[encoded: need])
-        encoded = need
-        nxt = z[T + s] if (tail and s + 1 < n_calls) else None
-        model(buf[:, s * ol: s * ol + T], out=buf[:, T + s * ol: T + (s + 1) * ol], enc_cache=(z[s * ol:], B * HW * C_, HW * C_),
-              **({"enc_next": nxt} if nxt is not None else {}))
-        if nxt is not None:
-            encoded = need + 1
+        kw = {}
+        if plan.cache:
+            need = s * ol + T
+            if need > encoded:    # the first call encodes the whole window, later calls the `ol` new frames
+                model.encode_frames(buf[:, encoded: need], z[encoded: need])
+            encoded = need
+            kw["enc_cache"] = (z[s * ol:], B * HW * C_, HW * C_)
+            if plan.tail_enc and s + 1 < n_calls:
+                kw["enc_next"] = z[T + s]
+                encoded = need + 1
+        model(buf[:, s * ol: s * ol + T], out=buf[:, T + s * ol: T + (s + 1) * ol], **kw)
     return buf[:, T: T + n_steps]
 
 
@@ -151,8 +136,10 @@ def rollout_model(model, batch: Dict, formatter, n_steps: int, device=None):
     device = device or next(model.parameters()).device
     from .tante import TANTE
     raw = batch["input"]
-    if (not NO_FUSED_FORMAT and type(formatter) is DefaultChannelsFirstFormatter and isinstance(model, TANTE) and model.deg and not torch.is_grad_enabled()
-            and raw.dim() == 5 and raw.shape[1] == model.T and raw.dtype == torch.float32 and raw.is_cuda and raw.is_contiguous()):
+    fused = (type(formatter) is DefaultChannelsFirstFormatter and isinstance(model, TANTE) and model.deg and not torch.is_grad_enabled()
+             and raw.dim() == 5 and raw.shape[1] == model.T and raw.dtype == torch.float32 and raw.is_cuda and raw.is_contiguous())
+    plan = _plan(model, raw) if fused else None
+    if fused and plan.first != "copy":
         # same result as formatter.process_input + the in-place rollout below, without the two extra passes over the window
         out_ref = batch["output"]
         if out_ref.is_cuda and SIDE_STREAM:
@@ -166,11 +153,11 @@ def rollout_model(model, batch: Dict, formatter, n_steps: int, device=None):
                 y_ref = _nan_to_num(out_ref)
             if not torch.cuda.is_current_stream_capturing():
                 y_ref.record_stream(main)
-            y = _rollout_in_place(model, None, n_steps, raw_input=raw)
+            y = _rollout_in_place(model, None, n_steps, raw, plan)
             main.wait_stream(side)
             return formatter.process_output(y), y_ref.to(device)
         y_ref = _nan_to_num(out_ref)
-        return formatter.process_output(_rollout_in_place(model, None, n_steps, raw_input=raw)), y_ref.to(device)
+        return formatter.process_output(_rollout_in_place(model, None, n_steps, raw, plan)), y_ref.to(device)
     if (not NO_FUSED_FORMAT and type(formatter) is DefaultChannelsFirstFormatter and raw.dim() == 5 and raw.dtype == torch.float32 and raw.is_cuda
             and raw.is_contiguous() and raw.data_ptr() % 16 == 0 and not raw.requires_grad and not batch["output"].requires_grad):
         # the default formatter's 'b t h w c -> b t c h w' + nan_to_num as ONE HIP pass, also on the training path (as torch ops: a
@@ -191,7 +178,6 @@ def rollout_model(model, batch: Dict, formatter, n_steps: int, device=None):
     preds, produced = [], 0
     if isinstance(model, TANTE) and torch.is_grad_enabled() and moving.shape[1] == model.T and moving.dtype == torch.float32:
         from .train_forward import encode_frames_train, tante_train_forward, train_enc_cache_ok
-        from .attn_backbone import resolve_compute
         if train_enc_cache_ok(model) and any(p.requires_grad for p in model.parameters()):
             # BPTT with every frame encoded ONCE: the windows of consecutive calls share T - output_length frames and the encoder is
             # frame-wise, so a window is assembled from cached per-frame encodings (autograd sums the gradients a frame's encoding
@@ -354,7 +340,7 @@ def _rollout_adaptive_in_place(model, x: torch.Tensor, n_steps: int, out_T: floa
     total = T + n_steps + n_cap - 1
     buf = torch.empty(B, total, *x.shape[2:], dtype=torch.float32, device=x.device)
     buf[:, :T].copy_(x)           # the formatter's 'b t h w c -> b t c h w' is materialised here, once
-    cache = model.enc_cache_supported(out_T) and not NO_ENC_CACHE
+    cache = _plan(model, None, out_T).cache
     HW, C_ = model.H_p * model.W_p, model.C
     z = torch.empty(total, B, HW, C_, dtype=torch.float32, device=x.device) if cache else None
     pos, encoded, rts = 0, 0, []

@@ -27,6 +27,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import options as _O
 from . import kernels as K
+from . import route as R
 from . import stages as S
 from .attn_backbone import Attn_Backbone, _PackCache, _gpu_only, _no_autograd, _wants_grad, resolve_compute
 
@@ -135,7 +136,7 @@ class enc_CNN(nn.Module):
         return s_ != self.P[i] or p_ != 0 or self.chans[i] * self.P[i] ** 2 > S.KMAX
 
     def fuses_23(self, compute: int) -> bool:
-        return (compute == L.BF16 and self.fused and self.P == (2, 2, 2) and self.overlap == 0.0 and K.enc23_supported(self.embed_dim))
+        return bool(compute == L.BF16 and self.fused and R.stages_2x2(self) and K.enc23_supported(self.embed_dim))
 
     def packed_head_enc(self):
         """Encoder stream of the one-launch rollout tail (kernels.head_enc_fused), rebuilt when a conv parameter changes."""
@@ -518,28 +519,21 @@ class TANTE(nn.Module):
     # kernel apply FiLM while it loads the planes.  Same arithmetic per token, term for term.
     def enc_cache_supported(self, out_T=None) -> bool:
         """deg=False: only for calls that take the adaptive tail (adaptive_tail_route(out_T)); give the out_T the calls will use."""
-        if not self.deg:
-            return bool(out_T is not None and self.adaptive_tail_route(out_T) and (self._enc_cache_fused(True) or self._enc_cache_frames(True)))
-        return self._enc_cache_fused() or self._enc_cache_frames()
+        if not self.deg and not (out_T is not None and self.adaptive_tail_route(out_T)):
+            return False
+        return R.cache_source(self, resolve_compute(self.compute)) is not None
 
-    def _enc_cache_fused(self, any_deg: bool = False) -> bool:
-        """enc_CNN with the fused stages: the first propagator launch applies FiLM while it loads the cached planes."""
-        compute = resolve_compute(self.compute)
-        return bool((self.deg or any_deg) and type(self.encoder).__name__ == "enc_CNN" and self.encoder.fuses_23(compute)
-                    and K.axis_hw_supported(self.H_p, self.W_p, self.C))
-
-    def _enc_cache_frames(self, any_deg: bool = False) -> bool:
-        """The spectral encoder (round 5): enc_FNO is per frame too (enc_dec_fno.py:224-273: every layer acts on (B T) images), so the
-        rollout encodes each frame once and a window is T cached encodings + one FiLM / positional pass over them
-        (tante_film_pos_fwd_frames: the same expression per token as the dense pass).  At cfg5 the encoder was 42 % of a model call and
-        three of its four frames had been encoded by the previous calls."""
-        return bool((self.deg or any_deg) and type(self.encoder).__name__ == "enc_FNO" and self.C == 256 and 1 <= self.T <= 8)
+    def route(self, out_T=1, enc_cache: bool = False, enc_next: bool = False, B: int = 1) -> R.Route:
+        """The kernels an inference call of B items with these arguments takes (route.Route), under the compute mode, the grad mode and
+        the switches as they are now.  Raises as the call would where it has no path for enc_cache / enc_next."""
+        return R.plan_route(self, resolve_compute(self.compute), out_T, enc_cache, enc_next, torch.is_grad_enabled(), B, head_multi=HEAD_MULTI,
+                            head_streams=HEAD_STREAMS, head_enc=HEAD_ENC, last_slot=LAST_SLOT, adaptive_tail=ADAPTIVE_TAIL)
 
     def encode_frames(self, frames: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
         """frames: (B, F, D, H, W) fp32 view (contiguous frames, any batch stride) -> z (F, B, Hp*Wp, C) fp32, the encoder output before
         FiLM in the frame-major layout forward(enc_cache=...) reads (one launch pair for the F frames)."""
         compute = resolve_compute(self.compute)
-        if self._enc_cache_frames(True) and not self._enc_cache_fused(True):
+        if R.cache_source(self, compute) == "cache_film_pass":      # the spectral encoder: its own launches, without FiLM
             B, F = frames.shape[:2]
             # one frame: the rows (b, hw) ARE the cache entry -- the encoder's last GEMM writes them there
             want = z.view(B * self.H_p * self.W_p, self.C) if (F == 1 and z.is_contiguous()) else None
@@ -557,25 +551,14 @@ class TANTE(nn.Module):
     def tail_fused_supported(self) -> bool:
         """The token-local tail of a call -- every order's derivative head, the Taylor sum and (in a rollout) the re-encoding of the
         predicted frame -- as ONE launch (csrc/head_enc.hip): bf16, C = 256, the three 2 x 2 stages of patch_scale 8, one output frame."""
-        compute = resolve_compute(self.compute)
-        return bool(HEAD_ENC and self.deg and self.output_length == 1 and 1 <= self.taylor_order <= 4 and compute == L.BF16 and self.fused_head
-                    and type(self.encoder).__name__ == "enc_CNN" and getattr(self.decoders[0], 'P', None) == (2, 2, 2)
-                    and self.decoders[0].overlap == 0.0 and K.head_enc_supported(self.C, self.D, self.H_p, self.W_p)
-                    and all(b.takes_x_in(compute) for b in self.blocks[1:self.taylor_order]))
+        return R.tail_fused(self, resolve_compute(self.compute), HEAD_ENC)
 
     def adaptive_tail_route(self, out_T) -> bool:
         """A deg=False inference call with this out_T runs its tail as tante_adaptive_rt + tante_head_adaptive (csrc/adaptive_tail.hip):
         the switch TANTE_ADAPTIVE_TAIL is on, compute is bf16, the heads are the three 2 x 2 stages of patch_scale 8 at C = 128 / 256,
         whole 16-token tiles per image, at most 4 orders and n_cap = floor(out_T - 1 + ep) <= 8 frames.  Everything else keeps the
         launches and the bits it had."""
-        if self.deg or not ADAPTIVE_TAIL or resolve_compute(self.compute) != L.BF16 or not self.fused_head:
-            return False
-        if getattr(self.decoders[0], 'P', None) != (2, 2, 2) or self.decoders[0].overlap != 0.0:
-            return False
-        ep = self.interprators[0].ep
-        if any(ip.ep != ep for ip in self.interprators):
-            return False
-        return K.adaptive_tail_supported(self.C, self.D, self.H_p, self.W_p, self.taylor_order, K.adaptive_n_cap(out_T, ep))
+        return R.adaptive_cap(self, resolve_compute(self.compute), out_T, ADAPTIVE_TAIL) > 0
 
     def _adaptive_packs(self, device):
         """(modifier FiLM weights of every order as one buffer, Taylor coefficients (n_ord, 8) on the device)."""
@@ -587,40 +570,78 @@ class TANTE(nn.Module):
         key = (self.taylor_order, float(self.frame_interval), device)
         hit = getattr(self, "_adaptive_coefs", None)
         if hit is None or hit[0] != key:
-            rows = [[(j * self.frame_interval) ** (k + 1) / math.factorial(k + 1) for j in range(1, 9)] for k in range(self.taylor_order)]
+            rows = [R.taylor_coefs(self.frame_interval, k, 8) for k in range(self.taylor_order)]
             hit = (key, torch.tensor(rows, dtype=torch.float32, device=device).contiguous())
             self._adaptive_coefs = hit
         return film, hit[1]
 
-    def _adaptive_tail(self, x, inp, out_T, n_cap, out, enc_cache, film, film_frames, per_sample_counts, compute):
+    def _backbones(self, x, B, compute, route, film_src, film_frames):
+        """The backbones of every order (tante.py:146, chained), one step per order: yields the order's token stream once its backbone is
+        enqueued.  route.streams: orders after the first write a buffer of their own (the first launch, the H + W propagator pass, runs
+        out of place: tante_axis_hw_oop) and the earlier streams stay intact; else every order updates x in place, and whatever the
+        head needs of an order is read or copied before the next step."""
+        for i, blk in enumerate(self.blocks):
+            ls = route.last_slot and i + 1 == self.taylor_order
+            if route.streams and i > 0:
+                x_prev, x = x, torch.empty_like(x)
+                blk.forward_tokens(x, B, compute, x_in=x_prev, last_slot_only=ls)
+            else:
+                blk.forward_tokens(x, B, compute, film_src=film_src if i == 0 else None, film_frames=film_frames if i == 0 else None,
+                                   last_slot_only=ls)
+            yield x
+
+    def _slot_rows(self, x, B):
+        """A dense copy of the last-slot rows of stream x (a COPY also at B = 1): 8 MB per order at cfg2."""
+        T, HW, C_ = self.T, self.H_p * self.W_p, self.C
+        return x.view(B, T, HW * C_)[:, T - 1].clone(memory_format=torch.contiguous_format).view(B * HW, C_)
+
+    def _adaptive_tail(self, orders, inp, out_T, route, out, per_sample_counts):
         """deg=False inference on the fused head path (tante.py:145-176): the backbones as ever, then rt -> head with no host read between."""
         B, T, D, H, W = inp.shape
-        Hp, Wp, C_, n_ord = self.H_p, self.W_p, self.C, self.taylor_order
+        Hp, Wp, C_, n_cap = self.H_p, self.W_p, self.C, route.n_cap
         HW, frame = Hp * Wp, D * H * W
-        # each order's last-slot rows must survive the later backbones, as on the deg=True multi-head route: out-of-place streams when
-        # every later backbone can write a buffer of its own, else dense copies of the last-slot rows
-        streams = all(b.takes_x_in(compute) for b in self.blocks[1:n_ord])
-        rows = []
-        for i in range(n_ord):
-            if streams and i > 0:
-                x_prev, x = x, torch.empty_like(x)
-                self.blocks[i].forward_tokens(x, B, compute, x_in=x_prev)
-            else:
-                self.blocks[i].forward_tokens(x, B, compute, film_src=(enc_cache + (film,)) if (enc_cache is not None and i == 0) else None,
-                                              film_frames=film_frames if i == 0 else None)                      # l.146 (chained)
-            rows.append(x if streams else x.view(B, T, HW * C_)[:, T - 1].clone(memory_format=torch.contiguous_format).view(B * HW, C_))
-        addr = (HW, T * HW * C_, C_, (T - 1) * HW * C_) if streams else (B * HW, 0, C_, 0)
-        film_pack, coefs = self._adaptive_packs(x.device)
+        rows = [x if route.streams else self._slot_rows(x, B) for x in orders]
+        addr = (HW, T * HW * C_, C_, (T - 1) * HW * C_) if route.streams else (B * HW, 0, C_, 0)
+        film_pack, coefs = self._adaptive_packs(inp.device)
         _, R_t, count, fa, fs = K.adaptive_rt(rows, *addr, B, Hp, Wp, C_, [ip.packed_rt() for ip in self.interprators], film_pack, out_T,
                                               self.interprators[0].ep)                                          # l.148-152, 157
         if out is None:
-            out = torch.empty(B, n_cap, D, H, W, dtype=torch.float32, device=x.device)
+            out = torch.empty(B, n_cap, D, H, W, dtype=torch.float32, device=inp.device)
         K.head_adaptive(rows, *addr, B, Hp, Wp, C_, D, [d.packed_head() for d in self.decoders], fa, fs, count, per_sample_counts, coefs,
                         n_cap, out, out.stride(0), inp, (T - 1) * frame, inp.stride(0))                          # l.147,153,163-171
         # l.163: the one host read, after everything is enqueued -- it only sizes the returned view
         counts = count.tolist()
         n_out = min(max(counts) if per_sample_counts else counts[0], n_cap)
         return out[:, :max(n_out, 0)], R_t
+
+    def _unfused_tail(self, orders, inp, out_T, route, per_sample_counts, compute):
+        """deg=False off the adaptive tail: per order a GEMM chain, a reduction, a FiLM table and a FiLM pass; a host read; then the heads.
+        Intended semantics of tante.py:148-152 (the shipped glue raises): d3 = last slot as (B, L, C); rt = interprator(d3, out_T);
+        d3 = film3d(d3, rt); decode."""
+        B, T, D, H, W = inp.shape
+        Hp, Wp, C_ = self.H_p, self.W_p, self.C
+        HW, frame = Hp * Wp, D * H * W
+        r_t, srcs = [], []
+        for i, x in enumerate(orders):
+            rt = self.interprators[i].forward_tokens(x, B, out_T, compute, a_n0=HW, a_s1=T * HW * C_, a_s0=C_, a_off=(T - 1) * HW * C_)
+            r_t.append(rt)
+            ma, mb = self.modifiers[i].tables(rt)
+            d3 = torch.empty(B * HW, C_, dtype=torch.float32, device=x.device)
+            K.film_apply(x, (T - 1) * HW * C_, T * HW * C_, d3, B * HW, C_, HW, ma, mb)
+            srcs.append(d3)
+        R_t = torch.stack(r_t, dim=1).mean(dim=1)
+        # l.163: sample 0 decides for the batch (host sync, as in the reference); per_sample_counts: enough frames for every sample
+        n_out = int(torch.floor(R_t).max()) if per_sample_counts else math.floor(float(R_t[0]))
+        out = torch.empty(B, max(n_out, 0), D, H, W, dtype=torch.float32, device=inp.device)
+        if route.heads and 1 <= n_out <= 8:
+            for i, d3 in enumerate(srcs):
+                K.head_fused(d3, B * HW, 0, C_, 0, B, Hp, Wp, C_, D, self.decoders[i].packed_head(), out, out.stride(0),
+                             R.taylor_coefs(self.frame_interval, i, n_out), inp if i == 0 else None, (T - 1) * frame, inp.stride(0))
+            return out, R_t
+        derivs = [self.decoders[i].forward_tokens(d3, B, compute, B * HW, 0, C_, 0) for i, d3 in enumerate(srcs)]
+        if n_out >= 1:
+            K.taylor(inp, (T - 1) * frame, inp.stride(0), derivs, self.frame_interval, n_out, out, B, frame, out_bstride=out.stride(0))
+        return out, R_t
 
     def forward(self, input: torch.Tensor, out_T=1, out: Optional[torch.Tensor] = None, enc_cache: Optional[tuple] = None,
                 enc_next: Optional[torch.Tensor] = None, per_sample_counts: bool = False):
@@ -640,6 +661,7 @@ class TANTE(nn.Module):
         host read (of floor(R_t), to size the returned view) comes after everything is enqueued.  Against TANTE_ADAPTIVE_TAIL=0 the
         results differ in bf16 rounding ORDER only: the same operand roundings, another summation order in the step-size mean and in the
         Taylor sum.
+        Which launches a call takes is decided once, by route() (route.plan_route); the code below executes that record.
         With autograd enabled the differentiable path (train_forward.py: HIP forward + HIP backward kernels) runs."""
         if not input.is_cuda:
             raise RuntimeError("tante_amd.TANTE runs on the GPU only (no CPU fallback); move the input to cuda")
@@ -660,15 +682,18 @@ class TANTE(nn.Module):
         compute = resolve_compute(self.compute)
         Hp, Wp, C_ = self.H_p, self.W_p, self.C
         HW = Hp * Wp
+        route = self.route(out_T, enc_cache is not None, enc_next is not None, B)
         fa, fb = self._time_tables()
-        film = (fa, fb, self.s_emb.view(HW, C_), T, HW)
-        film_frames = None
-        adaptive = self.adaptive_tail_route(out_T)
-        if enc_cache is not None:
-            if not (self.enc_cache_supported() if self.deg else (adaptive and self.enc_cache_supported(out_T))):
-                raise RuntimeError("enc_cache: this model / compute mode has no frame-encoding cache path")
+        se = self.s_emb.view(HW, C_)
+        film = (fa, fb, se, T, HW)
+        film_src = film_frames = None
+        if route.source == "encoder":
+            x = self.encoder.forward_tokens(inp, compute, film, bstride)                               # tante.py:132-141
+        else:
             x = torch.empty(B * T * HW, C_, dtype=torch.float32, device=inp.device)
-            if not self._enc_cache_fused(True):      # cached frames + FiLM / positional terms in one pass (tante.py:136-141 over the window)
+            if route.source == "cache_fused":
+                film_src = enc_cache + (film,)
+            else:      # cached frames + FiLM / positional terms in one pass (tante.py:136-141 over the window)
                 zc = enc_cache[0]
                 fr = L.Frames()
                 for t in range(T):
@@ -676,114 +701,49 @@ class TANTE(nn.Module):
                     if tuple(f.shape) != (B, HW, C_) or f.dtype != torch.float32 or f.stride(2) != 1 or f.stride(1) != C_ or f.data_ptr() % 16:
                         raise ValueError("enc_cache: frames must be (B, Hp*Wp, C) fp32 with contiguous rows")
                     fr.f[t], fr.bstride[t] = f.data_ptr(), f.stride(0)
-                vp0 = self.blocks[0].vertical_propagator
-                if (compute == L.BF16 and not K.axis_hw_supported(Hp, Wp, C_, compute)
-                        and L.lib().tante_axis_mlp_film_supported(B, T, Hp, Wp * C_, C_)
-                        and all(q.data_ptr() % 16 == 0 for q in (vp0[0].weight, vp0[0].bias, vp0[2].weight, vp0[2].bias, fa, fb, self.s_emb))):
-                    # the first backbone's vertical propagator applies FiLM + the positional terms while it loads its tiles
-                    # (tante_axis_mlp_film): x is produced by that launch, the pass below is not run
-                    film_frames = (fr, zc, fa, fb, self.s_emb.view(HW, C_))
+                if route.source == "cache_film_vp":      # x is produced by the first backbone's tante_axis_mlp_film launch
+                    film_frames = (fr, zc, fa, fb, se)
                 else:
-                    L.check(L.lib().tante_film_pos_fwd_frames(C.byref(fr), fa.data_ptr(), fb.data_ptr(), self.s_emb.view(HW, C_).data_ptr(), B, T, HW, C_,
-                                                              x.data_ptr(), K._stream()), "tante_film_pos_fwd_frames")
-                enc_cache = None
-        else:
-            x = self.encoder.forward_tokens(inp, compute, film, bstride)                               # tante.py:132-141
-        last_slot = dict(a_n0=HW, a_s1=T * HW * C_, a_s0=C_, a_off=(T - 1) * HW * C_)               # x[:, -1:] by stride
-        fused_head = (compute == L.BF16 and self.fused_head and getattr(self.decoders[0], 'P', None) == (2, 2, 2) and self.decoders[0].overlap == 0.0
-                      and K.head_fused_supported(C_, D))
-        n_cap = K.adaptive_n_cap(out_T, self.interprators[0].ep) if adaptive else 0
+                    L.check(L.lib().tante_film_pos_fwd_frames(C.byref(fr), fa.data_ptr(), fb.data_ptr(), se.data_ptr(), B, T, HW, C_, x.data_ptr(),
+                                                              K._stream()), "tante_film_pos_fwd_frames")
         if out is not None:
-            if not self.deg and not adaptive:
+            if not self.deg and not route.n_cap:
                 raise ValueError("out= is only meaningful with a fixed output length (deg=True) or on the adaptive tail (adaptive_tail_route)")
-            if tuple(out.shape) != (B, self.output_length if self.deg else n_cap, D, H, W) or out.dtype != torch.float32 or not out.is_cuda \
+            if tuple(out.shape) != (B, self.output_length if self.deg else route.n_cap, D, H, W) or out.dtype != torch.float32 or not out.is_cuda \
                     or out.stride()[1:] != (frame, H * W, W, 1) or out.stride(0) % 4 or out.data_ptr() % 16:
                 raise ValueError("out must be a (B, output_length, D, H, W) fp32 CUDA view with contiguous frames (deg=False: n_cap frames)")
-        if adaptive:
-            if enc_next is not None:
-                raise RuntimeError("enc_next: this model / compute mode has no fused head + re-encoding path (tail_fused_supported())")
-            return self._adaptive_tail(x, inp, out_T, n_cap, out, enc_cache, film, film_frames, per_sample_counts, compute)
-        derivs, r_t, srcs = [], [], []
-        # one prediction frame, several Taylor orders: ONE head launch after the last backbone (tante_head_fused_multi) instead of one per
-        # order -- the frame is read and written once instead of taylor_order times.  The earlier orders' last-slot rows are copied aside
-        # (8 MB each at cfg2) because the later backbones update the stream in place.  TANTE_HEAD_MULTI=0: one launch per order (A/B).
-        tail_fused = self.tail_fused_supported()
-        if enc_next is not None:
-            if not tail_fused or not self.encoder.fuses_23(compute):
-                raise RuntimeError("enc_next: this model / compute mode has no fused head + re-encoding path (tail_fused_supported())")
-            if tuple(enc_next.shape) != (B, HW, C_) or enc_next.dtype != torch.float32 or not enc_next.is_cuda or not enc_next.is_contiguous():
-                raise ValueError("enc_next must be a contiguous (B, Hp*Wp, C) fp32 CUDA tensor")
-        multi_head = (self.deg and fused_head and self.output_length == 1 and 2 <= self.taylor_order <= 4 and HEAD_MULTI) or tail_fused
-        saved_rows = []
-        # ... or not copied at all: every later backbone writes a stream buffer of its own (its first launch, the H + W propagator pass,
-        # runs out of place: tante_axis_hw_oop), so the earlier orders' streams stay intact for the head.  TANTE_HEAD_STREAMS=0: copies.
-        streams = tail_fused or (multi_head and HEAD_STREAMS and all(b.takes_x_in(compute) for b in self.blocks[1:self.taylor_order]))
-        # the last order's stream is read at slot T - 1 only (by the one head launch): its backbone may leave the other slots unfinished
-        slot_only = LAST_SLOT and self.deg and multi_head and self.output_length == 1 and not torch.is_grad_enabled()
-        for i in range(self.taylor_order):
-            ls = slot_only and i + 1 == self.taylor_order
-            if streams and i > 0:
-                x_prev, x = x, torch.empty_like(x)
-                self.blocks[i].forward_tokens(x, B, compute, x_in=x_prev, last_slot_only=ls)
-            else:
-                self.blocks[i].forward_tokens(x, B, compute, film_src=(enc_cache + (film,)) if (enc_cache is not None and i == 0) else None,
-                                              film_frames=film_frames if i == 0 else None, last_slot_only=ls)  # l.146 (chained)
-            if self.deg:
-                if multi_head:
-                    if i + 1 < self.taylor_order:
-                        saved_rows.append(x if streams else
-                                          x.view(B, T, HW * C_)[:, T - 1].clone(memory_format=torch.contiguous_format).view(B * HW, C_))      # (a COPY also at B = 1)
-                        continue
-                    if out is None:
-                        out = torch.empty(B, 1, D, H, W, dtype=torch.float32, device=x.device)
-                    coefs = [self.frame_interval ** (k + 1) / math.factorial(k + 1) for k in range(self.taylor_order)]
-                    if tail_fused:      # heads + Taylor sum (+ the predicted frame's encoding for the next call) in one launch
-                        K.head_enc_fused(saved_rows + [x], HW, T * HW * C_, C_, (T - 1) * HW * C_, B, Hp, Wp, C_, D,
-                                         [self.decoders[k].packed_head() for k in range(self.taylor_order)], coefs, out, out.stride(0),
-                                         inp, (T - 1) * frame, bstride,
-                                         enc_stream=self.encoder.packed_head_enc() if enc_next is not None else None, z=enc_next)
-                        continue
-                    K.head_fused_multi(saved_rows + [x], HW, T * HW * C_, C_, (T - 1) * HW * C_, B, Hp, Wp, C_, D,
-                                       [self.decoders[k].packed_head() for k in range(self.taylor_order)], coefs, out, out.stride(0),
-                                       inp, (T - 1) * frame, bstride, streams=streams)                          # l.147,153,165-171
-                elif fused_head:
-                    if out is None:
-                        out = torch.empty(B, self.output_length, D, H, W, dtype=torch.float32, device=x.device)
-                    coefs = [(j * self.frame_interval) ** (i + 1) / math.factorial(i + 1) for j in range(1, self.output_length + 1)]
-                    K.head_fused(x, HW, T * HW * C_, C_, (T - 1) * HW * C_, B, Hp, Wp, C_, D, self.decoders[i].packed_head(), out,
-                                 out.stride(0), coefs, inp if i == 0 else None, (T - 1) * frame, bstride)     # l.147,153,165-171
-                else:
-                    derivs.append(self.decoders[i].forward_tokens(x, B, compute, **last_slot))      # l.147,153
-            else:
-                # intended semantics of l.148-152 (the shipped glue raises): d3 = last slot as (B, L, C);
-                # rt = interprator(d3, out_T); d3 = film3d(d3, rt); decode
-                rt = self.interprators[i].forward_tokens(x, B, out_T, compute, **last_slot)
-                r_t.append(rt)
-                ma, mb = self.modifiers[i].tables(rt)
-                d3 = torch.empty(B * HW, C_, dtype=torch.float32, device=x.device)
-                K.film_apply(x, (T - 1) * HW * C_, T * HW * C_, d3, B * HW, C_, HW, ma, mb)
-                srcs.append(d3)
-        if self.deg:
-            n_out, R_t = self.output_length, None
-            if fused_head:
-                return out
-        else:
-            R_t = torch.stack(r_t, dim=1).mean(dim=1)
-            # l.163: sample 0 decides for the batch (host sync, as in the reference); per_sample_counts: enough frames for every sample
-            n_out = int(torch.floor(R_t).max()) if per_sample_counts else math.floor(float(R_t[0]))
-            if n_out >= 1 and fused_head and n_out <= 8:
-                out = torch.empty(B, n_out, D, H, W, dtype=torch.float32, device=x.device)
-                for i, d3 in enumerate(srcs):
-                    coefs = [(j * self.frame_interval) ** (i + 1) / math.factorial(i + 1) for j in range(1, n_out + 1)]
-                    K.head_fused(d3, B * HW, 0, C_, 0, B, Hp, Wp, C_, D, self.decoders[i].packed_head(), out, out.stride(0), coefs,
-                                 inp if i == 0 else None, (T - 1) * frame, bstride)
-                return out, R_t
-            derivs = [self.decoders[i].forward_tokens(d3, B, compute, B * HW, 0, C_, 0) for i, d3 in enumerate(srcs)]
-        if n_out < 1:
-            out = torch.empty(B, 0, D, H, W, dtype=torch.float32, device=x.device)
-        else:
+        if enc_next is not None and (tuple(enc_next.shape) != (B, HW, C_) or enc_next.dtype != torch.float32 or not enc_next.is_cuda
+                                     or not enc_next.is_contiguous()):
+            raise ValueError("enc_next must be a contiguous (B, Hp*Wp, C) fp32 CUDA tensor")
+        orders = self._backbones(x, B, compute, route, film_src, film_frames)
+        if route.tail == "adaptive":
+            return self._adaptive_tail(orders, inp, out_T, route, out, per_sample_counts)
+        if route.tail == "unfused":
+            return self._unfused_tail(orders, inp, out_T, route, per_sample_counts, compute)
+        n_ord, n_out, dt = self.taylor_order, self.output_length, self.frame_interval
+        slot = (HW, T * HW * C_, C_, (T - 1) * HW * C_)               # x[:, -1:] by stride
+        if route.tail == "decoders":
+            derivs = [self.decoders[i].forward_tokens(x, B, compute, *slot) for i, x in enumerate(orders)]      # l.147,153
             if out is None:
-                out = torch.empty(B, n_out, D, H, W, dtype=torch.float32, device=x.device)
-            K.taylor(inp, (T - 1) * frame, bstride, derivs, self.frame_interval, n_out, out, B, frame,
-                     out_bstride=out.stride(0))                                                     # l.165-171
-        return out if self.deg else (out, R_t)
+                out = torch.empty(B, n_out, D, H, W, dtype=torch.float32, device=inp.device)
+            K.taylor(inp, (T - 1) * frame, bstride, derivs, dt, n_out, out, B, frame, out_bstride=out.stride(0))      # l.165-171
+            return out
+        if out is None:
+            out = torch.empty(B, n_out, D, H, W, dtype=torch.float32, device=inp.device)
+        if route.tail == "head_per_order":                                                               # l.147,153,165-171
+            for i, x in enumerate(orders):
+                K.head_fused(x, *slot, B, Hp, Wp, C_, D, self.decoders[i].packed_head(), out, out.stride(0), R.taylor_coefs(dt, i, n_out),
+                             inp if i == 0 else None, (T - 1) * frame, bstride)
+            return out
+        # one prediction frame: ONE head launch after the last backbone instead of one per order -- the frame is read and written once.
+        # The earlier orders' last-slot rows are the streams themselves (route.streams) or copies; the last order's stream is read in place.
+        rows = [x if (route.streams or i + 1 == n_ord) else self._slot_rows(x, B) for i, x in enumerate(orders)]
+        heads = [d.packed_head() for d in self.decoders]
+        coefs = [R.taylor_coefs(dt, k, 1)[0] for k in range(n_ord)]
+        if route.tail == "head_enc":      # ... + the predicted frame's encoding for the next call, in the same launch
+            K.head_enc_fused(rows, *slot, B, Hp, Wp, C_, D, heads, coefs, out, out.stride(0), inp, (T - 1) * frame, bstride,
+                             enc_stream=self.encoder.packed_head_enc() if enc_next is not None else None, z=enc_next)
+        else:
+            K.head_fused_multi(rows, *slot, B, Hp, Wp, C_, D, heads, coefs, out, out.stride(0), inp, (T - 1) * frame, bstride,
+                               streams=route.streams)
+        return out

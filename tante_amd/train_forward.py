@@ -8,7 +8,6 @@ detach), the tape being torch.autograd's.
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import NamedTuple, Optional
 
 import torch
@@ -18,6 +17,7 @@ from . import options as _O
 from . import kernels as K
 from . import attn_flash as FA
 from . import stages as S
+from .route import taylor_coefs
 from .autograd import (EncTailFn, TailCfg, TailFn, FilmTableFn, ActFn, AttentionFn, BlockFn, BlockTailFn, block_tail_ready, AxisHWFn, AxisMlpFn, BranchOutFn, DeconvFn, DropoutAddFn, FilmPosFn, FilmPosFramesFn, FoldFn, LayerNormFn, LayerNormSkipFn, LinearFn, MaskedAttentionFn, MaskedFlashAttentionFn,
                        PatchEmbedFn, RtReduceFn, TaylorFn, _grad_slot, next_seed)
 
@@ -103,7 +103,7 @@ def tail_train_cfg(model, B: int, compute: int, want_z: bool):
     if rec is False:
         return None
     ep, dps, es, dss = rec
-    coefs = [float(model.frame_interval) ** (k + 1) / math.factorial(k + 1) for k in range(model.taylor_order)]
+    coefs = [taylor_coefs(float(model.frame_interval), k, 1)[0] for k in range(model.taylor_order)]
     return TailCfg(B, model.T, model.H_p, model.W_p, model.C, D, coefs, dps, dss, ep, es, want_z)
 
 

@@ -611,7 +611,7 @@ def test_spectral_encoder_frame_cache_in_the_rollout(dev, mode, tol):
     md = tante_amd.TanteMetadata(n_fields=3, spatial_resolution=(64, 64))
     m = tante_amd.TANTE(in_T=4, dset_metadata=md, taylor_order=1, attn_axes="THW", n_head=8, embed_dim=256, patch_scale=8, overlap_ratio=0.0,
                         enc_dec_type="fno", modes1=8, modes2=8).to(dev).eval().set_compute(mode)
-    assert m.enc_cache_supported() and m._enc_cache_frames() and not m._enc_cache_fused()
+    assert m.enc_cache_supported() and m.route(enc_cache=True, B=2).source == "cache_film_pass"
     x = torch.randn(2, 4, 3, 64, 64, device=dev)
     with torch.no_grad():
         y1 = R._rollout_in_place(m, x, 5).clone()
