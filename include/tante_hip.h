@@ -596,6 +596,38 @@ int64_t tante_afno_twiddle_floats(int H, int W);
 int64_t tante_afno_filter_workspace_bytes(int64_t B, int H, int W, int C);
 int tante_afno_filter(const float* x, const float* residual, int64_t B, int H, int W, int C, int bs, const float* twiddles, const float* w1,
                       const float* w2, float lambda, float* out, void* work, int64_t work_bytes, void* stream);
+
+/* ---- DPOT: GroupNorm and the truncated-mode mixer (dpot_mixer.hip; added without an ABI bump: nothing that existed changed) ----
+ * tante_groupnorm: torch.nn.GroupNorm(G, C) as Block.norm1 / norm2 use it (dpot.py:138, 147, 160, 167) on channels-last fp32 rows
+ * x (B, HW, C): per (sample, group) the statistics run over HW x C/G elements, biased variance, eps inside the root; y = the normalised
+ * rows times gamma plus beta (either may be NULL), fp32 or bf16 (y_dtype).  The mean is taken first and the variance about it, per slab
+ * of rows, and the slabs are combined exactly in a fixed order: no E[x^2] - mean^2, no atomics.  Served: 1 <= HW <= 4096, any C that is
+ * a multiple of G (C / G need not be a multiple of 4); otherwise -2 with the reason.  work: _workspace_bytes(B, HW, C, G) bytes. */
+int tante_groupnorm_supported(int64_t B, int HW, int C, int G);
+int64_t tante_groupnorm_workspace_bytes(int64_t B, int HW, int C, int G);
+int tante_groupnorm(const float* x, int64_t B, int HW, int C, int G, float eps, const float* gamma, const float* beta, void* y, int y_dtype,
+                    void* work, int64_t work_bytes, void* stream);
+/* tante_dpot_filter: AFNO2D.forward (dpot.py:47-102) on channels-last fp32 rows x (B, H, W, C), with k1 = min(modes, H) and
+ * k2 = min(modes, W/2 + 1):
+ *   X = rfft2(x, 'ortho')[:k1, :k2]                                     (dpot.py:55, 67-68: axis 1 keeps its first k1 non-negative
+ *                                                                        frequencies only, the negative ones are dropped)
+ *   Y = (gelu(Re U) + i gelu(Im U)) W2 + b2,  U = X W1 + b1             complex, per channel block of bs = C / num_blocks (dpot.py:67-89)
+ *   out = irfft2(Y zero-extended, s=(H, W), 'ortho') + x (+ residual)   (dpot.py:91-98; residual: Block.forward's double_skip, l.163-164)
+ * Everything outside the kept corner is zero, not the bias.  Six launches of v_mfma_f32_16x16x4_f32 products (fp32 in both compute
+ * modes); the block MLP's grid is cut by weight bytes (16 output columns of one block per workgroup, every weight element read once per
+ * 192 spectrum rows).  Served: 1 <= H, W <= 64, 1 <= bs <= 512, C a multiple of bs, modes >= 1, hidden_size_factor 1, B <= 65535 --
+ * _supported says so, the call returns -2 with the reason in the last-error string otherwise.
+ *   twiddles: T1 (k2, W) = e^{-2 pi i l w / W} / sqrt(W), T2 (k1, H) = e^{-2 pi i k h / H} / sqrt(H), T3 (H, k1) = e^{+2 pi i k h / H} /
+ *     sqrt(H), T4 (W, k2) = c_l e^{+2 pi i l w / W} / sqrt(W) with c_l = 1 for l = 0 and l = W/2 (W even), 2 otherwise; each a real plane
+ *     then an imaginary plane, rows padded to 16 and columns to 4 with zeros, fp32, back to back: _twiddle_floats(H, W, modes) floats.
+ *   w1, w2 (2, nb, bs, bs) and b1, b2 (2, nb, bs) as the state dict holds them: [0] real, [1] imaginary parts, rows = input channel.
+ *   residual: (B, H, W, C) or NULL; out may alias residual, not x.  work: _workspace_bytes(...) bytes, 16-byte aligned. */
+int tante_dpot_filter_supported(int64_t B, int H, int W, int C, int bs, int modes, int hidden_factor);
+int64_t tante_dpot_twiddle_floats(int H, int W, int modes);
+int64_t tante_dpot_filter_workspace_bytes(int64_t B, int H, int W, int C, int bs, int modes);
+int tante_dpot_filter(const float* x, const float* residual, int64_t B, int H, int W, int C, int bs, int modes, int hidden_factor,
+                      const float* twiddles, const float* w1, const float* b1, const float* w2, const float* b2, float* out, void* work,
+                      int64_t work_bytes, void* stream);
 /* Backward of tante_cross_attention.  o is the forward output; dq gets the query gradient in the layout of q; the key / value gradients
  * are ADDED (fp32 atomics) to dk / dv, rows (b, j) at (b*Lk + j)*ldg + h*D -- zero them first.  stats: n_batch*n_head*Lq*3 floats of
  * scratch (softmax max, 1 / sum, dO . O per query). */

@@ -1,0 +1,525 @@
+"""DPOT baseline on the HIP kernels  (reference models/dpot.py, configs/dpot.yaml: the other Fourier-mixer model of the comparison table).
+
+Same constructor arguments, attributes, `state_dict` keys / shapes and forward contract (`b t c h w -> b out_timesteps c h w`, so the
+sliding-window rollout re-feeds it `out_timesteps` frames per call) as the reference's models.DPOT.  The model is channels-last inside and
+every arithmetic step is a C-ABI call of libtante_hip:
+  patch embed   tante_im2col + chunked tante_gemm with the erf-GELU epilogue, then tante_gemm with the positional embedding riding its
+                residual operand (dpot.py:187-191, 254, 332); the three coordinate channels of get_grid_3d are constants kept in a cached
+                staging image, into which the fields are copied -- ONE strided copy per call, layout only, no arithmetic;
+  time agg      one GEMM with K = T C, K-chunked per t, reading the ((b t), x, y, C) rows in place and accumulating through the
+                residual operand; 'exp_mlp' folds cos(linspace(0, 1, T)[t] gamma[i]) into w[t, i, :] in float64 at pack time;
+  Block         tante_groupnorm (norm1), tante_dpot_filter (the truncated-mode mixer, its inner skip, and the first skip under
+                double_skip), tante_groupnorm in the activation dtype (norm2), chunked tante_gemm + erf GELU, chunked tante_gemm with
+                the skip as the residual (dpot.py:158-172, the 1 x 1 convolutions run as linears);
+  out_layer     the transposed conv as one scatter GEMM with GELU (embed_dim <= 512) or as a chunked tap GEMM + tante_col2im_nhwc +
+                tante_act_fwd, then two pixel-row linears; the last one writes (b, (t c), h, w), which IS b t c h w.
+torch allocates, reshapes and makes the one copy named above.
+
+`cls_head` holds its parameters for the state dict and is NEVER evaluated: the reference computes cls_pred and discards it
+(dpot.py:343-344).
+
+Inference only (eval mode under no_grad).  Training, n_spatial_dims = 3, act other than 'gelu', mixing_type other than 'afno' and
+hidden_size_factor != 1 raise NotImplementedError; there is no CPU fallback."""
+from __future__ import annotations
+
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib as L
+from . import kernels as K
+from . import stages as S
+from .attn_backbone import _PackCache, resolve_compute
+
+MAX_GRID = 64       # token-grid points per axis the mixer serves
+MAX_BLOCK = 512     # channels per block
+MAX_TOKENS = 4096   # tokens per sample tante_groupnorm serves
+GROUPS = 8          # torch.nn.GroupNorm(8, width)  (dpot.py:138, 147)
+
+
+def _r(n: int, m: int) -> int:
+    return (n + m - 1) // m * m
+
+
+# ---- host side of tante_groupnorm / tante_dpot_filter: the predicates' mirrors, the twiddle tables -----------------------------------------
+def groupnorm_supported_py(B: int, HW: int, C_: int, G: int) -> bool:
+    """Python mirror of tante_groupnorm_supported."""
+    return 1 <= HW <= MAX_TOKENS and G >= 1 and 1 <= C_ <= (1 << 24) and C_ % G == 0 and 0 <= B and B * G <= 2 ** 31 - 1
+
+
+def filter_supported_py(B: int, H: int, W: int, C_: int, bs: int, modes: int, hidden_factor: int = 1) -> bool:
+    """Python mirror of tante_dpot_filter_supported."""
+    return (1 <= H <= MAX_GRID and 1 <= W <= MAX_GRID and 1 <= bs <= MAX_BLOCK and C_ >= 1 and C_ % bs == 0 and C_ // bs <= 65535
+            and modes >= 1 and hidden_factor == 1 and 0 <= B <= 65535)
+
+
+def kept_modes(H: int, W: int, modes: int) -> Tuple[int, int]:
+    """(k1, k2): the rows / columns of the half spectrum the mixer keeps -- a `modes` past the grid clamps, as Python slicing does."""
+    return min(modes, H), min(modes, W // 2 + 1)
+
+
+def _cis(num: np.ndarray, n: int, sign: int) -> np.ndarray:
+    """e^{sign 2 pi i num / n} in float64 with the angle reduced in integers (so the entries that are real / imaginary are exactly so)."""
+    m = np.mod(num, n).astype(np.float64)
+    z = np.cos(2.0 * np.pi * m / n) + sign * 1j * np.sin(2.0 * np.pi * m / n)
+    z.real[np.abs(z.real) < 1e-15] = 0.0
+    z.imag[np.abs(z.imag) < 1e-15] = 0.0
+    return z
+
+
+def twiddle_tables(H: int, W: int, modes: int) -> List[np.ndarray]:
+    """The four complex128 tables of tante_dpot_filter (include/tante_hip.h), unpadded: T1 (k2, W), T2 (k1, H), T3 (H, k1), T4 (W, k2)."""
+    k1, k2 = kept_modes(H, W, modes)
+    k, l, h, w = np.arange(k1), np.arange(k2), np.arange(H), np.arange(W)
+    cl = np.where((l == 0) | ((W % 2 == 0) & (l == W // 2)), 1.0, 2.0)
+    return [_cis(np.outer(l, w), W, -1) / np.sqrt(W), _cis(np.outer(k, h), H, -1) / np.sqrt(H),
+            _cis(np.outer(h, k), H, +1) / np.sqrt(H), _cis(np.outer(w, l), W, +1) * cl[None, :] / np.sqrt(W)]
+
+
+def pack_twiddles(H: int, W: int, modes: int) -> np.ndarray:
+    """-> the float32 buffer tante_dpot_filter reads: per table a real then an imaginary plane, rows padded to 16, columns to 4."""
+    planes = []
+    for t in twiddle_tables(H, W, modes):
+        p = np.zeros((2, _r(t.shape[0], 16), _r(t.shape[1], 4)), dtype=np.float32)
+        p[0, :t.shape[0], :t.shape[1]] = t.real
+        p[1, :t.shape[0], :t.shape[1]] = t.imag
+        planes.append(p.reshape(-1))
+    return np.concatenate(planes)
+
+
+_TWIDDLES = {}     # (H, W, k1, k2, device) -> packed tables on the device: weight independent, built once per shape
+
+
+def _twiddles(H: int, W: int, modes: int, device) -> torch.Tensor:
+    key = (H, W) + kept_modes(H, W, modes) + (str(device),)
+    t = _TWIDDLES.get(key)
+    if t is None:
+        host = pack_twiddles(H, W, modes)
+        n = int(L.lib().tante_dpot_twiddle_floats(H, W, modes))
+        if n != host.size:
+            raise RuntimeError(f"twiddle tables for a {H} x {W} grid with {modes} modes: {host.size} floats packed, the library expects {n}")
+        t = torch.from_numpy(host).to(device)
+        _TWIDDLES[key] = t
+    return t
+
+
+def fold_time_weight(w: torch.Tensor, gamma: Optional[torch.Tensor]) -> torch.Tensor:
+    """TimeAggregator's weight (T, C, C) with 'exp_mlp's cos(linspace(0, 1, T)[t] gamma[i]) folded into row i (dpot.py:216-219), in float64,
+    rounded to fp32 once.  gamma None ('mlp'): w itself."""
+    w64 = w.detach().double()
+    if gamma is not None:
+        t = torch.linspace(0, 1, w.shape[0]).double().to(w.device)                  # the reference's fp32 linspace
+        w64 = w64 * torch.cos(t[:, None] * gamma.detach().double().reshape(1, -1))[:, :, None]
+    return w64.float()
+
+
+def groupnorm(x: torch.Tensor, G: int, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float,
+              out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """tante_groupnorm on channels-last fp32 rows x (B, ..., C): GroupNorm(G, C) over (all tokens x channels in group) per sample."""
+    K._dev(x, gamma, beta)
+    if x.dtype != torch.float32 or x.dim() < 2:
+        raise RuntimeError("GroupNorm takes fp32 channels-last rows (B, ..., C)")
+    B, C_ = x.shape[0], x.shape[-1]
+    HW = x.numel() // max(B * C_, 1)
+    lib = L.lib()
+    y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    nbytes = max(int(lib.tante_groupnorm_workspace_bytes(B, HW, C_, G)), 0)      # (-1: the call below refuses by name)
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    L.check(lib.tante_groupnorm(K._p(x), B, HW, C_, G, float(eps), K._p(gamma), K._p(beta), K._p(y), K._DT[out_dtype], K._p(work), nbytes,
+                                K._stream()), "tante_groupnorm")
+    return y
+
+
+def dpot_filter(x: torch.Tensor, residual: Optional[torch.Tensor], w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+                modes: int, out: Optional[torch.Tensor] = None, hidden_factor: int = 1) -> torch.Tensor:
+    """tante_dpot_filter on x (B, H, W, C) fp32 channels-last: filter(x) (+ residual); w1 / w2 (2, nb, bs, bs), b1 / b2 (2, nb, bs) as the
+    state dict holds them."""
+    K._dev(x, residual, w1, b1, w2, b2, out)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError("the DPOT filter takes fp32 channels-last rows (B, H, W, C)")
+    B, H, W, C_ = x.shape
+    bs = w1.shape[2]
+    if tuple(w1.shape) != (2, C_ // max(bs, 1), bs, bs) or w2.shape != w1.shape or tuple(b1.shape) != (2, C_ // max(bs, 1), bs) or b2.shape != b1.shape:
+        raise RuntimeError(f"the DPOT filter's weights {tuple(w1.shape)} / biases {tuple(b1.shape)} do not belong to {C_} channels")
+    lib = L.lib()
+    if not lib.tante_dpot_filter_supported(B, H, W, C_, bs, modes, hidden_factor):
+        # the call itself refuses with the reason; made here without touching the device
+        L.check(lib.tante_dpot_filter(None, None, B, H, W, C_, bs, modes, hidden_factor, None, None, None, None, None, None, None, 0, None),
+                "tante_dpot_filter")
+    if out is None:
+        out = torch.empty_like(x)
+    nbytes = int(lib.tante_dpot_filter_workspace_bytes(B, H, W, C_, bs, modes))
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    L.check(lib.tante_dpot_filter(K._p(x), K._p(residual), B, H, W, C_, bs, modes, hidden_factor, K._p(_twiddles(H, W, modes, x.device)), K._p(w1),
+                                  K._p(b1), K._p(w2), K._p(b2), K._p(out), K._p(work), nbytes, K._stream()), "tante_dpot_filter")
+    return out
+
+
+# ---- the reference's modules -------------------------------------------------------------------------------------------------------
+def _gpu(x: torch.Tensor):
+    if not x.is_cuda:
+        raise RuntimeError("tante_amd.DPOT runs on the GPU only (no CPU fallback); move the model and its input to cuda")
+
+
+def _inference_only(module: nn.Module):
+    if module.training or (torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters())):
+        raise NotImplementedError("tante_amd.DPOT is inference only: training is out of scope (the mixer's and GroupNorm's backward are "
+                                  "kernels of their own that are not built); call .eval() under torch.no_grad()")
+
+
+def _gelu_only(act: str):
+    if act != "gelu":
+        raise NotImplementedError(f"act = {act!r} is out of scope: the HIP path evaluates the erf GELU of the reference's config (act 'gelu')")
+
+
+class AFNO2D(nn.Module):
+    """The truncated-mode Fourier mixer  (dpot.py:21-102): tante_dpot_filter."""
+
+    def __init__(self, width=32, num_blocks=8, channel_first=False, sparsity_threshold=0.01, modes=32, hard_thresholding_fraction=1,
+                 hidden_size_factor=1, act="gelu"):
+        super().__init__()
+        assert width % num_blocks == 0, f"hidden_size {width} should be divisble by num_blocks {num_blocks}"
+        _gelu_only(act)
+        if hidden_size_factor != 1:
+            raise NotImplementedError(f"hidden_size_factor = {hidden_size_factor} is out of scope: tante_dpot_filter serves square blocks "
+                                      "(hidden_size_factor 1, the value the reference's Block passes)")
+        self.hidden_size = width
+        self.sparsity_threshold = sparsity_threshold
+        self.num_blocks = num_blocks
+        self.block_size = self.hidden_size // self.num_blocks
+        self.channel_first = channel_first
+        self.modes = modes
+        self.hidden_size_factor = hidden_size_factor
+        self.scale = 1 / (self.block_size * self.block_size * self.hidden_size_factor)
+        self.act = nn.GELU()
+        bs = self.block_size
+        self.w1 = nn.Parameter(self.scale * torch.rand(2, num_blocks, bs, bs * hidden_size_factor))
+        self.b1 = nn.Parameter(self.scale * torch.rand(2, num_blocks, bs * hidden_size_factor))
+        self.w2 = nn.Parameter(self.scale * torch.rand(2, num_blocks, bs * hidden_size_factor, bs))
+        self.b2 = nn.Parameter(self.scale * torch.rand(2, num_blocks, bs))
+
+    def run(self, x: torch.Tensor, residual: Optional[torch.Tensor]) -> torch.Tensor:
+        """x (B, H, W, C) fp32 channels-last -> filter(x) (+ residual); the weights are read where the parameters lie."""
+        return dpot_filter(x, residual, self.w1.detach(), self.b1.detach(), self.w2.detach(), self.b2.detach(), self.modes,
+                           hidden_factor=self.hidden_size_factor)
+
+    def forward(self, x: torch.Tensor, spatial_size=None) -> torch.Tensor:
+        """(B, H, W, C), or (B, C, H, W) with channel_first, -> the same layout  (dpot.py:47-102).  Inference only."""
+        _inference_only(self)
+        if x.dim() != 4:
+            raise NotImplementedError("the DPOT mixer is two-dimensional here: n_spatial_dims = 3 is out of scope")
+        _gpu(x)
+        xl = x.detach().to(torch.float32)
+        if self.channel_first:
+            xl = xl.permute(0, 2, 3, 1)
+        y = self.run(xl.contiguous(), None)
+        if self.channel_first:
+            y = y.permute(0, 3, 1, 2)
+        return y.to(x.dtype)
+
+
+class Mlp(nn.Module):
+    """fc2(gelu_erf(fc1(x)))  (dpot.py:105-118); no module of the reference's DPOT uses it."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act="gelu", drop=0.0):
+        super().__init__()
+        _gelu_only(act)
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        self.fc1 = nn.Linear(in_features, hidden_features)
+        self.act = nn.GELU()
+        self.fc2 = nn.Linear(hidden_features, out_features)
+
+
+class Block(nn.Module):
+    """n1 = GN1(x); f = filter(n1) (+ x under double_skip); y = mlp(GN2(f)) + (f if double_skip else x)   (dpot.py:121-172)."""
+
+    def __init__(self, mixing_type="afno", double_skip=True, width=32, n_blocks=4, mlp_ratio=1.0, channel_first=True, modes=32, drop=0.0,
+                 drop_path=0.0, act="gelu", h=14, w=8):
+        super().__init__()
+        _gelu_only(act)
+        if mixing_type != "afno":
+            raise NotImplementedError(f"mixing_type = {mixing_type!r} is out of scope: the reference's Block builds a filter for 'afno' only")
+        self.norm1 = torch.nn.GroupNorm(GROUPS, width)
+        self.width = width
+        self.modes = modes
+        self.act = nn.GELU()
+        self.filter = AFNO2D(width=width, num_blocks=n_blocks, sparsity_threshold=0.01, channel_first=channel_first, modes=modes,
+                             hard_thresholding_fraction=1, hidden_size_factor=1, act=act)
+        self.norm2 = torch.nn.GroupNorm(GROUPS, width)
+        mlp_hidden_dim = int(width * mlp_ratio)
+        self.mlp = nn.Sequential(nn.Conv2d(in_channels=width, out_channels=mlp_hidden_dim, kernel_size=1, stride=1), self.act,
+                                 nn.Conv2d(in_channels=mlp_hidden_dim, out_channels=width, kernel_size=1, stride=1))
+        self.double_skip = double_skip
+        self._cache = _PackCache()
+
+    def _packed(self, compute: int):
+        fc1, fc2 = self.mlp[0], self.mlp[2]
+        return self._cache.get(compute, [fc1.weight, fc1.bias, fc2.weight, fc2.bias], lambda: (
+            S.pack_linear_chunks(fc1.weight.detach().reshape(fc1.weight.shape[0], -1), fc1.bias, compute),
+            S.pack_linear_chunks(fc2.weight.detach().reshape(fc2.weight.shape[0], -1), fc2.bias, compute)))
+
+    def run(self, x: torch.Tensor, compute: int) -> torch.Tensor:
+        """x (B, H, W, C) fp32 channels-last -> block(x), same shape."""
+        B, H, W, C_ = x.shape
+        M = B * H * W
+        fc1, fc2 = self._packed(compute)
+        n1 = groupnorm(x, GROUPS, self.norm1.weight.detach(), self.norm1.bias.detach(), self.norm1.eps)
+        if self.double_skip:
+            f = self.filter.run(n1, x)               # the filter's store epilogue adds the first skip
+            skip = f
+        else:
+            f = self.filter.run(n1, None)
+            skip = x
+        n2 = groupnorm(f, GROUPS, self.norm2.weight.detach(), self.norm2.bias.detach(), self.norm2.eps, K.act_torch_dtype(compute))
+        h = S.linear_chunks(n2.view(M, C_), fc1, K.act_torch_dtype(compute), L.ACT_GELU_ERF)
+        y = torch.empty(M, C_, dtype=torch.float32, device=x.device)
+        k0, Kt = 0, h.shape[1]
+        for i, pw in enumerate(fc2):                 # K-chunks accumulate through the residual operand; the first one carries the skip
+            K.linear(h, pw, y, M=M, a_n0=M, a_s0=Kt, a_off=k0, residual=skip.view(M, C_) if i == 0 else y)
+            k0 += pw.K
+        return y.view(B, H, W, C_)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, C, H, W) -> (B, C, H, W), as the reference's Block takes its images (GroupNorm and the 1 x 1 convs act on dim 1)."""
+        _inference_only(self)
+        if x.dim() != 4:
+            raise NotImplementedError("the DPOT block is two-dimensional here: n_spatial_dims = 3 is out of scope")
+        if not self.filter.channel_first:
+            raise NotImplementedError("Block(channel_first=False) hands its channel-first image to a channels-last filter in the reference; "
+                                      "that mixes channels with rows and is not reproduced")
+        _gpu(x)
+        y = self.run(x.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous(), resolve_compute(None))
+        return y.permute(0, 3, 1, 2).to(x.dtype)
+
+
+class PatchEmbed(nn.Module):
+    """Conv(p x p / p) -> GELU -> Conv(1 x 1)  (dpot.py:175-197): tante_im2col + two GEMMs, channels-last rows out."""
+
+    def __init__(self, img_size, patch_size=16, in_chans=3, embed_dim=768, out_dim=128, act="gelu"):
+        super().__init__()
+        _gelu_only(act)
+        patch_size = (patch_size, patch_size)
+        self.img_size = img_size
+        self.patch_size = patch_size
+        self.num_patches = (img_size[1] // patch_size[1]) * (img_size[0] // patch_size[0])
+        self.out_size = (img_size[0] // patch_size[0], img_size[1] // patch_size[1])
+        self.out_dim = out_dim
+        self.act = nn.GELU()
+        self.proj = nn.Sequential(nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size), self.act,
+                                  nn.Conv2d(embed_dim, out_dim, kernel_size=1, stride=1))
+        self._cache = _PackCache()
+
+    def _packed(self, compute: int):
+        c0, c2 = self.proj[0], self.proj[2]
+        return self._cache.get(compute, [c0.weight, c0.bias, c2.weight, c2.bias], lambda: (
+            S.pack_linear_chunks(c0.weight.detach().reshape(c0.weight.shape[0], -1), c0.bias, compute),
+            S.pack_linear_chunks(c2.weight.detach().reshape(c2.weight.shape[0], -1), c2.bias, compute)))
+
+    def run(self, x: torch.Tensor, compute: int, residual: Optional[torch.Tensor]) -> torch.Tensor:
+        """x (n, C, H, W) fp32 contiguous -> rows (n H' W', out_dim) fp32 (+ residual rows)."""
+        n, cin, h, w = x.shape
+        p = self.patch_size[0]
+        c0, c2 = self._packed(compute)
+        adt = K.act_torch_dtype(compute)
+        cols = K.im2col(x, True, n, cin, h, w, p, p, p, p, 0, 0, 0, adt)
+        h1 = S.linear_chunks(cols, c0, adt, L.ACT_GELU_ERF)
+        M = h1.shape[0]
+        y = torch.empty(M, self.out_dim, dtype=torch.float32, device=x.device)
+        k0, Kt = 0, h1.shape[1]
+        for i, pw in enumerate(c2):
+            K.linear(h1, pw, y, M=M, a_n0=M, a_s0=Kt, a_off=k0, residual=residual if i == 0 else y)
+            k0 += pw.K
+        return y
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, C, H, W) -> (B, out_dim, H', W')  (dpot.py:193-197).  Inference only."""
+        _inference_only(self)
+        _gpu(x)
+        B, C_, H, W = x.shape
+        assert H == self.img_size[0] and W == self.img_size[1], \
+            f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
+        y = self.run(x.detach().to(torch.float32).contiguous(), resolve_compute(None), None)
+        return y.view(B, self.out_size[0], self.out_size[1], self.out_dim).permute(0, 3, 1, 2).to(x.dtype)
+
+
+class TimeAggregator(nn.Module):
+    """out[..., j] = sum_t sum_i w[t, i, j] x[..., t, i] (cos(t gamma_i) for 'exp_mlp')  (dpot.py:200-221): one K = T C GEMM."""
+
+    def __init__(self, n_channels, n_timesteps, out_channels, type="mlp"):
+        super().__init__()
+        self.n_channels = n_channels
+        self.n_timesteps = n_timesteps
+        self.out_channels = out_channels
+        self.type = type
+        if type not in ("mlp", "exp_mlp"):
+            raise ValueError(f"time_agg must be 'mlp' or 'exp_mlp', got {type!r}")
+        self.w = nn.Parameter(1 / (n_timesteps * out_channels ** 0.5) * torch.randn(n_timesteps, out_channels, out_channels))
+        if type == "exp_mlp":
+            self.gamma = nn.Parameter(2 ** torch.linspace(-10, 10, out_channels).unsqueeze(0))
+        self._cache = _PackCache()
+
+    def _packed(self, compute: int):
+        gamma = self.gamma if self.type == "exp_mlp" else None
+        params = [self.w] + ([gamma] if gamma is not None else [])
+
+        def build():
+            wf = fold_time_weight(self.w, gamma)                           # (T, C_in, C_out)
+            return [S.pack_linear_chunks(wf[t].t().contiguous(), None, compute) for t in range(wf.shape[0])]
+        return self._cache.get(compute, params, build)
+
+    def run(self, rows: torch.Tensor, B: int, T: int, HW: int, compute: int) -> torch.Tensor:
+        """rows ((b t) HW, C) fp32 -> (b HW, C) fp32: the K-chunks of every t read their rows in place."""
+        C_ = self.out_channels
+        if T != self.n_timesteps:
+            raise ValueError(f"the time aggregator holds {self.n_timesteps} steps, the input has {T}")
+        out = torch.empty(B * HW, C_, dtype=torch.float32, device=rows.device)
+        first = True
+        for t, chunks in enumerate(self._packed(compute)):
+            k0 = 0
+            for pw in chunks:
+                K.linear(rows, pw, out, M=B * HW, a_n0=HW, a_s1=T * HW * C_, a_s0=C_, a_off=t * HW * C_ + k0, residual=None if first else out)
+                first = False
+                k0 += pw.K
+        return out
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, X, Y, T, C) -> (B, X, Y, C)  (dpot.py:213-221).  Inference only."""
+        _inference_only(self)
+        _gpu(x)
+        B, X, Y, T, C_ = x.shape
+        rows = x.detach().to(torch.float32).permute(0, 3, 1, 2, 4).contiguous().view(B * T * X * Y, C_)
+        return self.run(rows, B, T, X * Y, resolve_compute(None)).view(B, X, Y, C_).to(x.dtype)
+
+
+class DPOT(nn.Module):
+    """models/dpot.py:223-350 -- same constructor, attributes, parameters and forward contract."""
+
+    def __init__(self, in_T: int, dset_metadata, patch_size=16, mixing_type="afno", out_timesteps=1, n_blocks=4, embed_dim=768,
+                 out_layer_dim=32, depth=12, modes=32, mlp_ratio=1.0, n_cls=12, act="gelu", time_agg="exp_mlp"):
+        super().__init__()
+        img_size = tuple(dset_metadata.spatial_resolution)
+        n_channel = dset_metadata.n_fields
+        if getattr(dset_metadata, "n_spatial_dims", 2) == 3 or len(img_size) == 3:
+            raise NotImplementedError("DPOT with n_spatial_dims = 3 is out of scope: the HIP mixer and the reference's model are "
+                                      "two-dimensional")
+        if len(img_size) != 2:
+            raise ValueError(f"spatial_resolution must have two entries, got {img_size}")
+        _gelu_only(act)
+        if mixing_type != "afno":
+            raise NotImplementedError(f"mixing_type = {mixing_type!r} is out of scope: the reference's Block builds a filter for 'afno' only")
+        self.in_channels = n_channel
+        self.out_channels = n_channel
+        self.in_timesteps = in_T
+        self.out_timesteps = out_timesteps
+        self.n_blocks = n_blocks
+        self.modes = modes
+        self.num_features = self.embed_dim = embed_dim
+        self.mlp_ratio = mlp_ratio
+        self.act = nn.GELU()
+        self.patch_embed = PatchEmbed(img_size=img_size, patch_size=patch_size, in_chans=self.in_channels + 3,
+                                      embed_dim=self.out_channels * patch_size + 3, out_dim=embed_dim, act=act)
+        self.latent_size = self.patch_embed.out_size
+        self.pos_embed = nn.Parameter(torch.zeros(1, embed_dim, self.patch_embed.out_size[0], self.patch_embed.out_size[1]))
+        self.time_agg = time_agg
+        self.n_cls = n_cls
+        h, w = img_size
+        self.blocks = nn.ModuleList([Block(mixing_type=mixing_type, modes=modes, width=embed_dim, mlp_ratio=mlp_ratio, channel_first=True,
+                                           n_blocks=n_blocks, double_skip=False, h=h, w=w, act=act) for _ in range(depth)])
+        # held for the state dict, never evaluated: the reference computes cls_pred and discards it (dpot.py:343-344)
+        self.cls_head = nn.Sequential(nn.Linear(embed_dim, embed_dim), self.act, nn.Linear(embed_dim, embed_dim), self.act,
+                                      nn.Linear(embed_dim, n_cls))
+        self.time_agg_layer = TimeAggregator(self.in_channels, in_T, embed_dim, time_agg)
+        self.out_layer = nn.Sequential(
+            nn.ConvTranspose2d(in_channels=embed_dim, out_channels=out_layer_dim, kernel_size=patch_size, stride=patch_size), self.act,
+            nn.Conv2d(in_channels=out_layer_dim, out_channels=out_layer_dim, kernel_size=1, stride=1), self.act,
+            nn.Conv2d(in_channels=out_layer_dim, out_channels=self.out_channels * self.out_timesteps, kernel_size=1, stride=1))
+        torch.nn.init.trunc_normal_(self.pos_embed, std=0.02)
+        self.mixing_type = mixing_type
+        self.patch_size, self.img_size, self.out_layer_dim = patch_size, img_size, out_layer_dim
+        self.output_length = out_timesteps
+        self.compute: Optional[str] = None
+        self._cache = _PackCache()
+        self._pos = _PackCache()
+        self._stage = {}
+
+    def set_compute(self, mode: Optional[str]):
+        if mode is not None and mode not in K.COMPUTE:
+            raise ValueError("compute must be None, 'fp32' or 'bf16'")
+        self.compute = mode
+        return self
+
+    def get_grid_3d(self, T: int, device) -> torch.Tensor:
+        """The three coordinate channels (T, 3, h, w) fp32: linspace(0, 1, n) over x, y and t  (dpot.py:309-319)."""
+        h, w = self.img_size
+        gx = torch.tensor(np.linspace(0, 1, h), dtype=torch.float).view(1, h, 1).expand(T, h, w)
+        gy = torch.tensor(np.linspace(0, 1, w), dtype=torch.float).view(1, 1, w).expand(T, h, w)
+        gt = torch.tensor(np.linspace(0, 1, T), dtype=torch.float).view(T, 1, 1).expand(T, h, w)
+        return torch.stack([gx, gy, gt], dim=1).to(device)
+
+    def _staging(self, b: int, T: int, device) -> torch.Tensor:
+        """The (b T, c + 3, h, w) image the patch embed reads: the coordinate channels are written once, the fields per call."""
+        key = (b, T, str(device))
+        st = self._stage.get(key)
+        if st is None:
+            h, w = self.img_size
+            st = torch.empty(b, T, self.in_channels + 3, h, w, dtype=torch.float32, device=device)
+            st[:, :, self.in_channels:] = self.get_grid_3d(T, device)
+            self._stage = {key: st}
+        return st
+
+    def _packed(self, compute: int):
+        d, a, z = self.out_layer[0], self.out_layer[2], self.out_layer[4]
+        p = self.patch_size
+
+        def build():
+            if self.embed_dim <= S.KMAX:
+                dec = K.pack_weight(d.weight, d.bias, compute, L.W_DECONV_NHWC, N=d.weight.shape[1] * p * p, K=d.weight.shape[0], P=p,
+                                    C_other=d.weight.shape[1])
+            else:       # the tap matrix (P P Cout, Cin), columns (kh, kw, co), K-chunked; the bias is added by the gather
+                dec = S.pack_linear_chunks(d.weight.detach().permute(2, 3, 1, 0).reshape(-1, d.weight.shape[0]).contiguous(), None, compute)
+            return (dec, S.pack_linear_chunks(a.weight.detach().reshape(a.weight.shape[0], -1), a.bias, compute),
+                    S.pack_linear_chunks(z.weight.detach().reshape(z.weight.shape[0], -1), z.bias, compute))
+        return self._cache.get(compute, [d.weight, d.bias, a.weight, a.bias, z.weight, z.bias], build)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x (b, t, c, h, w) -> (b, out_timesteps, c, h, w)   (dpot.py:323-350)."""
+        _inference_only(self)
+        if x.dim() != 5 or x.shape[1] != self.in_timesteps or x.shape[2] != self.in_channels:
+            raise ValueError(f"expected (B, {self.in_timesteps}, {self.in_channels}, H, W), got {tuple(x.shape)}")
+        _gpu(x)
+        b, T, c, h, w = x.shape
+        if (h, w) != tuple(self.img_size):
+            raise ValueError(f"Input image size ({h}*{w}) doesn't match model ({self.img_size[0]}*{self.img_size[1]}).")
+        compute = resolve_compute(self.compute)
+        adt = K.act_torch_dtype(compute)
+        p, C_ = self.patch_size, self.embed_dim
+        Hp, Wp = self.latent_size
+        HW = Hp * Wp
+        stage = self._staging(b, T, x.device)
+        stage[:, :, :c].copy_(x.detach())                                        # the one strided copy: the fields beside the cached coordinates
+        pos = self._pos.get((b, T), [self.pos_embed], lambda: self.pos_embed.detach()[0].permute(1, 2, 0).reshape(1, HW, C_)
+                            .expand(b * T, -1, -1).reshape(b * T * HW, C_).contiguous())
+        rows = self.patch_embed.run(stage.view(b * T, c + 3, h, w), compute, pos)   # ((b t) x y, C): x + pos_embed
+        y = self.time_agg_layer.run(rows, b, T, HW, compute).view(b, Hp, Wp, C_)
+        for blk in self.blocks:
+            y = blk.run(y, compute)
+        dec, mid, last = self._packed(compute)
+        od = self.out_layer_dim
+        if isinstance(dec, K.PackedWeight):
+            img = torch.empty(b, h, w, od, dtype=adt, device=x.device)
+            K.deconv(y.view(b * HW, C_), dec, img, n_img=b, Hi=Hp, Wi=Wp, P=p, Cout=od, nchw_out=False, act=L.ACT_GELU_ERF)
+        else:
+            taps = S.linear_chunks(y.view(b * HW, C_), dec, torch.float32)
+            pre = K.col2im_nhwc(taps, b, Hp, Wp, p, p, 0, od, self.out_layer[0].bias.detach(), torch.float32)
+            img = torch.empty(b, h, w, od, dtype=adt, device=x.device)
+            L.check(L.lib().tante_act_fwd(pre.data_ptr(), L.F32, img.data_ptr(), K._DT[adt], pre.numel(), L.ACT_GELU_ERF, K._stream()), "tante_act_fwd")
+        px = S.linear_chunks(img.view(b * h * w, od), mid, adt, L.ACT_GELU_ERF)
+        if len(last) != 1:
+            raise NotImplementedError("out_layer_dim above 512 is out of scope: the last pixel-row linear writes channels first from one GEMM")
+        nout = self.out_channels * self.out_timesteps
+        out = torch.empty(b, nout, h, w, dtype=torch.float32, device=x.device)
+        K.deconv(px, last[0], out, n_img=b, Hi=h, Wi=w, P=1, Cout=nout, nchw_out=True, act=L.ACT_NONE)     # (b, (t c), h, w) IS b t c h w
+        return out.view(b, self.out_timesteps, self.out_channels, h, w)
