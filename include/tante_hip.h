@@ -953,6 +953,52 @@ int tante_tail_pack_enc(const float* w1, const float* b1, const float* w2, const
 int tante_tail_fwd(const TanteTailFwd* args, void* stream);
 int tante_tail_bwd(const TanteTailBwd* args, void* stream);
 
+/* ---- AViT: instance norms, axial / time attention, field statistics (avit_ops.hip; added without an ABI bump: nothing that existed
+ * changed) ----
+ * tante_instnorm: the two norms over the token plane of channels-last fp32 rows x (n_img, HW, C), statistics per (image, channel):
+ *   TANTE_INSTNORM_INSTANCE  nn.InstanceNorm2d(affine=True) (avit.py:292-293, 314, 327): (x - mean) / sqrt(var_biased + eps) * weight + bias
+ *   TANTE_INSTNORM_RMS       RMSInstanceNorm2d.forward (avit.py:134-139): x / (std_unbiased + eps) * weight; the mean is NOT subtracted and
+ *                            `bias` is ignored, as the reference holds it and never applies it
+ * then act (TANTE_ACT_*, the nn.GELU() behind the stem's and the head's norms, avit.py:181, 184, 205, 208), then -- when residual and
+ * gamma are given -- out = residual + gamma[c] * value as one more fp32 multiply-add (avit.py:283-284); y (fp32 or bf16) may alias
+ * residual, not x.  weight / bias may be NULL.  The mean is taken first and the sum of squares about it, per slab of rows, and the slabs
+ * are combined exactly in a fixed order: no E[x^2] - mean^2, no atomics.  Served: 2 <= HW <= 4096, any C; otherwise -2 with the reason.
+ * work: _workspace_bytes(n_img, HW, C) bytes. */
+#define TANTE_INSTNORM_INSTANCE 0
+#define TANTE_INSTNORM_RMS 1
+int tante_instnorm_supported(int64_t n_img, int HW, int C);
+int64_t tante_instnorm_workspace_bytes(int64_t n_img, int HW, int C);
+int tante_instnorm(const float* x, int64_t n_img, int HW, int C, int form, float eps, const float* weight, const float* bias, int act,
+                   const float* residual, const float* gamma, void* y, int y_dtype, void* work, int64_t work_bytes, void* stream);
+/* tante_axial_attention: avit.py:257-273 on the rows qkv (n_img H W, 3 E) fp32 that input_head's GEMM left, E = heads hd, channel order
+ * (head, [q | k | v], hd) as the reference's rearrange reads it: q and k pass LayerNorm(hd) (qw, qb, kw, kb; eps), softmax attention
+ * (scale hd^-0.5, row maximum subtracted, fp32) runs along W for every (image, head, row) and along H for every column from the same
+ * q, k, v, and out (n_img H W, E) fp32 = (xx + xy) / 2 in (head, hd) channel order.  Both products are v_mfma_f32_16x16x4_f32.  Two
+ * launches (rows, then columns adding and halving).  qkv must be 16-byte aligned (both attention entries).  out is ALWAYS fp32, by
+ * decision: the RMS norm that reads it (norm2) takes fp32 rows, the second launch accumulates into it, and the attention blocks'
+ * projections stay fp32 in bf16 mode, so no activation-dtype form has a reader.  The same holds for tante_time_attention.
+ * Served: 1 <= H, W <= 64, hd in {16, 32, 64}; otherwise -2 with the reason. */
+int tante_axial_attention_supported(int64_t n_img, int heads, int H, int W, int hd);
+int tante_axial_attention(const float* qkv, int64_t n_img, int heads, int H, int W, int hd, const float* qw, const float* qb, const float* kw,
+                          const float* kb, float eps, float* out, void* stream);
+/* tante_time_attention: avit.py:317-326 on rows ordered ((t b), h, w): row t nseq + s is step t of sequence s (nseq = b h w), same channel
+ * order and q / k LayerNorm; logits q k^T hd^-0.5 + bias[head, tq, tk] (the relative-position bias the host tabulates, (heads, T, T) fp32),
+ * softmax in fp32; out (T nseq, E) fp32 in the same row order.  Served: 1 <= T <= 16, hd in {16, 32, 64}; otherwise -2 with the reason. */
+int tante_time_attention_supported(int64_t nseq, int T, int heads, int hd);
+int tante_time_attention(const float* qkv, int64_t nseq, int T, int heads, int hd, const float* qw, const float* qb, const float* kw,
+                         const float* kb, float eps, const float* bias, float* out, void* stream);
+/* tante_field_stats: torch.std_mean(x, dim=(t, h, w)) per (b, c) of x (B, T, C, HW) fp32 (avit.py:423-426): stats (B, C, 2) =
+ * [mean, std_unbiased + eps], mean first, centred squares, slabs combined exactly in a fixed order; xn (unless NULL) = (x - mean) / std
+ * as channels-last images ((t b), HW, C) -- the layout and image order the stem reads.  work: _workspace_bytes(B, T, C, HW) bytes.
+ * tante_field_affine: avit.py:448 on the head's channels-first images y ((t b), C, HW), t < Tk: out (B, Tk, C, HW) = y * std + mean.
+ * Served: up to 2^31 - 1 (b, c) pairs and 2^38 values per call; otherwise -2 with the reason. */
+int tante_field_stats_supported(int64_t B, int T, int C, int64_t HW);
+int64_t tante_field_stats_workspace_bytes(int64_t B, int T, int C, int64_t HW);
+int tante_field_stats(const float* x, int64_t B, int T, int C, int64_t HW, float eps, float* stats, float* xn, void* work, int64_t work_bytes,
+                      void* stream);
+int tante_field_affine_supported(int64_t B, int Tk, int C, int64_t HW);
+int tante_field_affine(const float* y, const float* stats, int64_t B, int Tk, int C, int64_t HW, float* out, void* stream);
+
 const char* tante_last_error(void);
 int tante_abi_version(void);
 

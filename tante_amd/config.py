@@ -19,6 +19,8 @@ _TARGET_ALIASES = {
     "models.afno.AFNO": "tante_amd.afno.AFNO",
     "models.DPOT": "tante_amd.dpot.DPOT",
     "models.dpot.DPOT": "tante_amd.dpot.DPOT",
+    "models.AViT": "tante_amd.avit.AViT",
+    "models.avit.AViT": "tante_amd.avit.AViT",
     "models.enc_dec_fno.SpectralLayer": "tante_amd.spectral.SpectralLayer",
     "models.attn_backbone.Attn_Backbone": "tante_amd.attn_backbone.Attn_Backbone",
     "models.attn_backbone.TransformerBlock": "tante_amd.attn_backbone.TransformerBlock",
