@@ -449,7 +449,9 @@ int tante_attention_flash_masked_bwd(const void* qkv, const void* o, const void*
  * ZEROED ONCE by the caller before the first use (the four pixel workgroups of a token group hand their encoder stage-2 outputs over
  * through it as bf16 operand fragments; the last to arrive runs stage 3 over the whole K = 512 in a fixed tap order: deterministic --
  * followed by one arrival counter per group, which the kernel leaves at zero).  One workspace per stream of concurrent launches.
- * enc_stream == NULL: heads + Taylor sum only (z, ws unused). */
+ * enc_stream == NULL: heads + Taylor sum only (z, ws unused).
+ * The kernel works on whole 16-token tiles that never straddle an image or an addressing block: tante_head_enc_fused returns -2, with a
+ * message and before anything is launched, when Hp * Wp % 16 != 0 or a_n0 % 16 != 0 (tante_head_enc_supported looks at C and D only). */
 int tante_head_enc_supported(int C, int D);
 int64_t tante_head_enc_stream_bytes(int C);
 int64_t tante_head_enc_ws_bytes(int64_t rows);

@@ -185,8 +185,13 @@ __device__ __forceinline__ float apply_act(float x, int act) {
 // lane l -> (row l&15, chunk 4*cb + (l>>4)).  XOR-ing the chunk index with the row makes every
 // 16-lane ds_read_b128 service group hit 16 distinct 16-byte slots of the 256-byte bank row
 // (cdna_hip_programming.md 5.5 T2; group lists in MI355X_MICROARCH.md "LDS").
+// The swizzled chunk stays inside its own row: with cpr == 4 (the head's W3 tile at C = 128, K = 32) the cpr == 8 form gave chunk indices
+// up to 7 -- rows 8 k + 7 and 8 k + 8 of a tile then shared a slot and the last row lay behind the tile, on its bias block: wrong
+// derivatives for C = 128 with D > 4 (tests/test_hip_tail_enc.py).
 __host__ __device__ __forceinline__ int swz_chunk(int r, int c, int cpr) {
-  return (cpr >= 16) ? (c ^ (r & 15)) : (c ^ ((r >> 1) & 7));  // cpr == 8 -> two rows per bank row
+  return (cpr >= 16) ? (c ^ (r & 15))
+       : (cpr >= 8)  ? (c ^ ((r >> 1) & 7))    // cpr == 8 -> two rows per bank row
+                     : (c ^ ((r >> 2) & 3));   // cpr == 4 -> four rows per bank row
 }
 
 // ---- LDS addresses and transposing reads ------------------------------------------------------------

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void head_enc_kernel(const HeArgs A) {
   if (grp >= A.groups) return;
   HE_STAMP(0);
 
-  // ---- rows: the wave's TT tiles of 16 consecutive tokens.  Hp Wp and a_n0 are multiples of 16 (checked by the launcher), so a tile never
+  // ---- rows: the wave's TT tiles of 16 consecutive tokens.  Hp Wp and a_n0 are multiples of 16 (tante_head_enc_fused returns -2 otherwise), so a tile never
   // straddles an image or an addressing block: one base offset + j a_s0, and a tile is live or dead as a whole (wave-uniform) ---------
   const int HW = A.Hp * A.Wp;
   const unsigned n_rows = (unsigned)A.n_img * (unsigned)HW;
@@ -628,6 +628,10 @@ extern "C" int tante_head_enc_fused(int n_ord, const float* const* rows, const v
   if (n_ord < 1 || n_ord > 4) TANTE_FAIL(-2, "tante_head_enc_fused: 1 .. 4 orders");
   if (!tante_head_enc_supported(C, D)) TANTE_FAIL(-2, "tante_head_enc_fused: unsupported C=%d D=%d", C, D);
   if (a_n0 <= 0 || n_img <= 0 || Hp <= 0 || Wp <= 0) TANTE_FAIL(-1, "tante_head_enc_fused: bad shape");
+  // the kernel's 16-token tiles never straddle an image or an addressing block: refused here, before anything is launched
+  if (((long)Hp * Wp) % 16 || a_n0 % 16)
+    TANTE_FAIL(-2, "tante_head_enc_fused: whole 16-token tiles expected: Hp * Wp = %ld and a_n0 = %d must be multiples of 16", (long)Hp * Wp,
+               (int)a_n0);
   if (a_s1 % 4 || a_s0 % 4 || a_off % 4 || out_bstride % 4 || last_bstride % 4 || ((uintptr_t)out % 16) || ((uintptr_t)last % 16))
     TANTE_FAIL(-1, "tante_head_enc_fused: alignment");
   for (int k = 0; k < n_ord; ++k)
