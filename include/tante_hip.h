@@ -1001,6 +1001,41 @@ int tante_field_stats(const float* x, int64_t B, int T, int C, int64_t HW, float
 int tante_field_affine_supported(int64_t B, int Tk, int C, int64_t HW);
 int tante_field_affine(const float* y, const float* stats, int64_t B, int Tk, int C, int64_t HW, float* out, void* stream);
 
+/* ---- UNetConvNext: the ConvNeXt block, its first half, the channels-first norm's row part, a direct 3 x 3 convolution (convnext.hip;
+ * added without an ABI bump: nothing that existed changed) ----
+ * tante_convnext_block: Block.forward (unet_convnext.py:134-148) as ONE launch on x (n_img, H, W, C) fp32 channels-last:
+ *   y = x + W2' gelu_erf(W1' LN(dwconv7x7(x) + b_dw) + b1') + b2'
+ * with the depthwise 7 x 7, padding 3 (unet_convnext.py:118-120; zeros where the image ends, never the neighbouring image), the
+ * LayerNorm over the true C with biased variance and eps (unet_convnext.py:65, 121; mean first, then centred squares) and the skip in
+ * fp32 in both compute modes; W1' / b1' carry the norm's affine and W2' / b2' carry gamma (unet_convnext.py:143-144), folded by the
+ * caller.  The two products are v_mfma_f32_16x16x4_f32 (TANTE_F32) or v_mfma_f32_16x16x32_bf16 with fp32 accumulation (TANTE_BF16);
+ * the 4 C hidden values never leave the registers.  y must not alias x.  No atomics: a token's result does not depend on its tile or
+ * its image's place in the batch.  Served: 1 <= C <= 256, any H, W >= 1; otherwise -2 with the reason.
+ * tante_pack_convnext: dw_w (C, 49) [= (C, 1, 7, 7)], dw_b (C), w1 (4 C, C), b1 (4 C), w2 (C, 4 C), b2 (C), all fp32 on the device ->
+ * one stream of tante_convnext_stream_bytes(C) bytes (16-byte aligned) in the fragment order of `compute`; C and 4 C are zero-padded to
+ * 16 2^k and four times that. */
+int tante_convnext_block_supported(int64_t n_img, int H, int W, int C);
+int64_t tante_convnext_stream_bytes(int C);
+int tante_pack_convnext(const float* dw_w, const float* dw_b, const float* w1, const float* b1, const float* w2, const float* b2, int C, int compute,
+                        void* out, void* stream);
+int tante_convnext_block(const float* x, float* y, const void* block_stream, int64_t n_img, int H, int W, int C, int compute, float eps, void* stream);
+/* tante_dwconv_ln: the first half of the block alone (unet_convnext.py:136-139): y (n_img H W, C) fp32 or bf16 =
+ * LN(dwconv7x7(x) + dw_b) [* ln_w + ln_b], ln_w / ln_b may be NULL; same arithmetic and order as the fused kernel.  The modular route
+ * of a block: tante_gemm with the GELU epilogue and tante_gemm with the skip as residual follow.  Served: 1 <= C <= 1024. */
+int tante_dwconv_ln_supported(int64_t n_img, int H, int W, int C);
+int tante_dwconv_ln(const float* x, int64_t n_img, int H, int W, int C, const float* dw_w, const float* dw_b, float eps, const float* ln_w, const float* ln_b,
+                    void* y, int y_dtype, void* stream);
+/* tante_l2norm_rows: y[m] = x[m] / max(||x[m]||_2, eps) on rows (M, C) fp32 -> fp32 or bf16: F.normalize(x, p=2, dim=1, eps)
+ * (unet_convnext.py:69), the token-local part of the channels_first "LayerNorm"; its weight is folded into the resample convolution
+ * and its bias is never applied, as in the reference.  A row of zeros gives zeros. */
+int tante_l2norm_rows_supported(int64_t M, int C);
+int tante_l2norm_rows(const float* x, int64_t M, int C, float eps, void* y, int y_dtype, void* stream);
+/* tante_conv3x3: Conv2d(Cin, Cout, kernel 3, padding 1) (unet_convnext.py:227-232), w (Cout, Cin, 3, 3), bias (Cout) or NULL, fp32
+ * throughout; in_nchw / out_nchw choose (n, C, H, W) or (n, H, W, C) on either side.  Served: Cin <= 128, Cout <= 64. */
+int tante_conv3x3_supported(int64_t n_img, int Cin, int Cout, int H, int W);
+int tante_conv3x3(const float* x, int64_t n_img, int Cin, int H, int W, int in_nchw, const float* w, const float* bias, int Cout, float* y, int out_nchw,
+                  void* stream);
+
 const char* tante_last_error(void);
 int tante_abi_version(void);
 

@@ -289,6 +289,16 @@ SIGNATURES = {
     "tante_field_stats": ([c_vp, c_i64, c_i32, c_i32, c_i64, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp], c_i32),
     "tante_field_affine_supported": ([c_i64, c_i32, c_i32, c_i64], c_i32),
     "tante_field_affine": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp], c_i32),
+    "tante_convnext_block_supported": ([c_i64, c_i32, c_i32, c_i32], c_i32),
+    "tante_convnext_stream_bytes": ([c_i32], c_i64),
+    "tante_pack_convnext": ([c_vp] * 6 + [c_i32, c_i32, c_vp, c_vp], c_i32),
+    "tante_convnext_block": ([c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp], c_i32),
+    "tante_dwconv_ln_supported": ([c_i64, c_i32, c_i32, c_i32], c_i32),
+    "tante_dwconv_ln": ([c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_vp], c_i32),
+    "tante_l2norm_rows_supported": ([c_i64, c_i32], c_i32),
+    "tante_l2norm_rows": ([c_vp, c_i64, c_i32, c_f32, c_vp, c_i32, c_vp], c_i32),
+    "tante_conv3x3_supported": ([c_i64, c_i32, c_i32, c_i32, c_i32], c_i32),
+    "tante_conv3x3": ([c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp], c_i32),
 }
 
 # every option name the library looks up (tante_opt in csrc/): tests/test_host_cpu.py checks this list against the sources
@@ -302,7 +312,7 @@ LIB_OPTIONS = ("TANTE_ATTN_BWD_HG", "TANTE_ATTN_BWD_NO_SPLIT", "TANTE_ATTN_BWD_V
 
 
 _lib = None
-ABI_VERSION = 14     # include/tante_hip.h: bumped whenever an entry point is added or changes (round 4: 6 tante_head_enc_*, 7 tante_pos_embed_tmajor + tante_spectral_*bf16out*; round 5: 8 tante_block_bwd_fused, 9 TanteGemm.a_pad; round 6: 10 tante_tail_*, 11 tante_attention_masked_bwd, 12 tante_spectral_layer_x, tante_axis_mlp_film; round 7: 13 tante_block_fused_last; 14 tante_attention_flash*; still 14: tante_attention_flash_masked + tante_attention_flash_masked_bwd were ADDED without a bump -- nothing that existed changed its signature or meaning, so a caller built against 14 runs unchanged, and the suite pins 14 (test_abi_version_is_14); a caller that needs the two looks the symbols up; the same holds for the six tante_adaptive_* / tante_head_adaptive entries of the adaptive-step tail, for tante_cross_attention_route, for the four tante_afno_* entries of the AFNO filter, for the three tante_groupnorm* and four tante_dpot_* entries of DPOT, for the twelve tante_instnorm* / tante_axial_attention* / tante_time_attention* / tante_field_* entries of AViT, and for tante_encode_window_raw with its three tante_*enc1_raw* helpers)
+ABI_VERSION = 14     # include/tante_hip.h: bumped whenever an entry point is added or changes (round 4: 6 tante_head_enc_*, 7 tante_pos_embed_tmajor + tante_spectral_*bf16out*; round 5: 8 tante_block_bwd_fused, 9 TanteGemm.a_pad; round 6: 10 tante_tail_*, 11 tante_attention_masked_bwd, 12 tante_spectral_layer_x, tante_axis_mlp_film; round 7: 13 tante_block_fused_last; 14 tante_attention_flash*; still 14: tante_attention_flash_masked + tante_attention_flash_masked_bwd were ADDED without a bump -- nothing that existed changed its signature or meaning, so a caller built against 14 runs unchanged, and the suite pins 14 (test_abi_version_is_14); a caller that needs the two looks the symbols up; the same holds for the six tante_adaptive_* / tante_head_adaptive entries of the adaptive-step tail, for tante_cross_attention_route, for the four tante_afno_* entries of the AFNO filter, for the three tante_groupnorm* and four tante_dpot_* entries of DPOT, for the twelve tante_instnorm* / tante_axial_attention* / tante_time_attention* / tante_field_* entries of AViT, for tante_encode_window_raw with its three tante_*enc1_raw* helpers, and for the ten tante_convnext_* / tante_pack_convnext / tante_dwconv_ln* / tante_l2norm_rows* / tante_conv3x3* entries of UNetConvNext)
 
 
 def lib():

@@ -1,0 +1,510 @@
+"""UNetConvNext baseline on the HIP kernels  (reference models/unet_convnext.py, configs/unet_convnext.yaml: the Well benchmark's CNN).
+
+Same constructor arguments, attributes, module tree, `state_dict` keys / shapes and forward contract (`b t c h w -> b 1 c h w`) as the
+reference's models.UNetConvNext.  The model is channels-last inside, (n, H, W, C) fp32, the residual stream fp32, and every arithmetic
+step is a C-ABI call of libtante_hip:
+  in_proj / out_proj  tante_conv3x3, fp32 in both modes: the batch is read as it arrives (b t c h w contiguous IS b (t c) h w) and
+                      written channels-last; out_proj reads channels-last and writes b 1 c h w.  Past Cin 128 / Cout 64: tante_im2col +
+                      tante_gemm.
+  Block               ONE launch, tante_convnext_block: depthwise 7 x 7 + bias, LayerNorm over channels, pwconv1 + erf GELU, pwconv2,
+                      layer scale, skip; out of place (the stage ping-pongs two buffers).  The norm's affine is folded into pwconv1 and
+                      gamma into pwconv2 in float64 at pack time.  The kernel serves C <= 256 and is the default up to C = 32, where it
+                      was measured faster; wider blocks, and every block with TANTE_CONVNEXT_FUSED = 0, take the modular route:
+                      tante_dwconv_ln -> tante_gemm (GELU epilogue) -> tante_gemm (skip as the residual operand).
+  Downsample          tante_l2norm_rows -> tante_im2col (2 x 2 / 2) -> tante_gemm, the norm's weight folded into the columns
+  Upsample            tante_l2norm_rows -> the 2 x 2 / 2 transposed convolution as a scatter GEMM (tap GEMM + tante_col2im_nhwc past 512
+                      input channels), the norm's weight folded into the rows
+  skip_proj           two GEMMs that accumulate through the residual operand, W[:, :C] x then + W[:, C:] skip: the concatenated tensor
+                      is never written
+torch allocates and reshapes.
+
+Restated as the reference has them: the channels_first "LayerNorm" of the resamples is F.normalize(x, p=2, dim=1, eps) * weight
+(unet_convnext.py:69) and its `bias` is held for the state dict and NEVER applied; skips[0] (the full-resolution in_proj output) is
+stored and never read (unet_convnext.py:274, 279: skips[-j] for j >= 1); `n_spatial_dims` comes from the metadata, not from the argument
+(unet_convnext.py:219); `gradient_checkpointing` is an attribute without effect here.
+
+In bf16 mode bf16 is the GEMM operand type of the groups in BF16_SITES; the depthwise sum, every norm, the skip and the two edge
+convolutions stay fp32.
+
+Inference only (eval mode under no_grad).  Training, 3-D metadata, a wrong t * c and H or W not divisible by 2 ** stages raise; there is
+no CPU fallback."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+import torch.nn as nn
+
+from . import _lib as L
+from . import kernels as K
+from . import options as _O
+from . import stages as S
+from .attn_backbone import _PackCache, resolve_compute
+from .avit import _conv_rows, _gemm
+
+FUSED_MAX_C = 256      # channels tante_convnext_block serves
+FUSED_DEFAULT_MAX_C = 32   # ... and the widest block it is the DEFAULT for: on the config's pyramid (token count x C^2 constant) the one launch
+#                            is 1.4 - 2.4 x faster than the modular route at C = 15 and 30 and slower from C = 60 on, where a level has too
+#                            few 128-token tiles to fill the chip (DESIGN 4.8 has the table); Block.run(fused=True) forces it at any C <= 256
+DWLN_MAX_C = 1024      # channels tante_dwconv_ln serves
+CONV3_MAX_CIN, CONV3_MAX_COUT = 128, 64
+BF16_SITES = ("block", "resample", "skip")   # the GEMM groups that take bf16 operands in bf16 mode (DESIGN 4.8 has the per-group figures)
+
+# True: blocks up to FUSED_DEFAULT_MAX_C channels run as one launch; False: every block runs the modular route (tante_dwconv_ln + two
+# tante_gemm), the A/B and parity partner of the fused launch
+FUSED = _O.register("TANTE_CONVNEXT_FUSED", True, __name__, "FUSED")
+
+
+def _site(compute: int, site: str) -> int:
+    """The compute mode of one GEMM group: the caller's for the groups in BF16_SITES, fp32 for the rest."""
+    return compute if site in BF16_SITES else L.F32
+
+
+# ---- host side of the kernels: the predicates' mirrors, the wrappers, the folds -----------------------------------------------------------
+def _tiles_ok(n_img: int, H: int, W: int, th: int, tw: int) -> bool:
+    tiles = ((W + tw - 1) // tw) * ((H + th - 1) // th)
+    return tiles <= 2 ** 31 - 1 and n_img * tiles <= 2 ** 31 - 1
+
+
+def convnext_block_supported_py(n_img: int, H: int, W: int, C_: int) -> bool:
+    """Python mirror of tante_convnext_block_supported."""
+    return 1 <= C_ <= FUSED_MAX_C and H >= 1 and W >= 1 and n_img >= 0 and _tiles_ok(n_img, H, W, 8, 16)
+
+
+def dwconv_ln_supported_py(n_img: int, H: int, W: int, C_: int) -> bool:
+    """Python mirror of tante_dwconv_ln_supported."""
+    return 1 <= C_ <= DWLN_MAX_C and H >= 1 and W >= 1 and n_img >= 0 and _tiles_ok(n_img, H, W, 8 if C_ <= 512 else 4, 8)
+
+
+def l2norm_rows_supported_py(M: int, C_: int) -> bool:
+    """Python mirror of tante_l2norm_rows_supported."""
+    return 1 <= C_ <= (1 << 24) and 0 <= M and (M + 3) // 4 <= 2 ** 31 - 1
+
+
+def conv3x3_supported_py(n_img: int, Cin: int, Cout: int, H: int, W: int) -> bool:
+    """Python mirror of tante_conv3x3_supported."""
+    return (1 <= Cin <= CONV3_MAX_CIN and 1 <= Cout <= CONV3_MAX_COUT and H >= 1 and W >= 1 and 0 <= n_img <= 65535
+            and (H * W + 255) // 256 <= 2 ** 31 - 1)
+
+
+def fold_block(norm_w, norm_b, w1, b1, w2, b2, gamma):
+    """pwconv1(LN_affine(z)) = (W1 diag(w)) z + (W1 b_ln + b1) and gamma * pwconv2(h) = (diag(gamma) W2) h + gamma b2
+    (unet_convnext.py:139-144), in float64, rounded to fp32 once -> (W1', b1', W2', b2')."""
+    w1d, w2d = w1.detach().double(), w2.detach().double()
+    nw, nb = norm_w.detach().double(), norm_b.detach().double()
+    w1f = w1d * nw[None, :]
+    b1f = w1d @ nb + b1.detach().double()
+    b2f = b2.detach().double()
+    if gamma is not None:
+        g = gamma.detach().double()
+        w2d, b2f = w2d * g[:, None], b2f * g
+    return w1f.float().contiguous(), b1f.float().contiguous(), w2d.float().contiguous(), b2f.float().contiguous()
+
+
+def fold_cf_norm(weight: torch.Tensor, norm_w: torch.Tensor) -> torch.Tensor:
+    """conv(normalize(x) * w) = conv'(normalize(x)) with the input channel's w folded into the convolution's weight (axis 1 of a Conv2d
+    weight, axis 0 of a ConvTranspose2d weight is its input channel: pass the weight with the input channel on axis 1), float64."""
+    w = norm_w.detach().double().reshape(-1)
+    shape = [1, -1] + [1] * (weight.dim() - 2)
+    return (weight.detach().double() * w.reshape(shape)).float().contiguous()
+
+
+def pack_convnext(dw_w, dw_b, w1, b1, w2, b2, C_: int, compute: int) -> torch.Tensor:
+    """tante_pack_convnext: the block's stream (depthwise taps, folded biases, both matrices in fragment order)."""
+    ts = [t.detach().to(torch.float32).contiguous() for t in (dw_w.reshape(C_, 49), dw_b, w1, b1, w2, b2)]
+    K._dev(*ts)
+    lib = L.lib()
+    nbytes = int(lib.tante_convnext_stream_bytes(C_))
+    out = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=ts[0].device)
+    L.check(lib.tante_pack_convnext(*[K._p(t) for t in ts], C_, compute, K._p(out), K._stream()), "tante_pack_convnext")
+    return out
+
+
+def convnext_block(x: torch.Tensor, stream: torch.Tensor, compute: int, eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tante_convnext_block on x (n, H, W, C) fp32 channels-last -> a NEW tensor (or `out`, which must not be x)."""
+    K._dev(x, stream, out)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError("the ConvNeXt block takes fp32 channels-last images (n, H, W, C)")
+    n, H, W, C_ = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    L.check(L.lib().tante_convnext_block(K._p(x), K._p(out), K._p(stream), n, H, W, C_, compute, float(eps), K._stream()), "tante_convnext_block")
+    return out
+
+
+def dwconv_ln(x: torch.Tensor, dw_w: torch.Tensor, dw_b: torch.Tensor, eps: float, ln_w: Optional[torch.Tensor] = None,
+              ln_b: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """tante_dwconv_ln on x (n, H, W, C) fp32 -> rows (n H W, C) fp32 or bf16."""
+    K._dev(x, dw_w, dw_b, ln_w, ln_b)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError("the depthwise convolution takes fp32 channels-last images (n, H, W, C)")
+    n, H, W, C_ = x.shape
+    out = torch.empty(n * H * W, C_, dtype=out_dtype, device=x.device)
+    L.check(L.lib().tante_dwconv_ln(K._p(x), n, H, W, C_, K._p(dw_w), K._p(dw_b), float(eps), K._p(ln_w), K._p(ln_b), K._p(out), K._DT[out_dtype],
+                                    K._stream()), "tante_dwconv_ln")
+    return out
+
+
+def l2norm_rows(x: torch.Tensor, eps: float, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """tante_l2norm_rows on rows (M, C) fp32 -> x / max(||x||_2, eps), fp32 or bf16."""
+    K._dev(x)
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise RuntimeError("the row norm takes fp32 rows (M, C)")
+    M, C_ = x.shape
+    out = torch.empty(M, C_, dtype=out_dtype, device=x.device)
+    L.check(L.lib().tante_l2norm_rows(K._p(x), M, C_, float(eps), K._p(out), K._DT[out_dtype], K._stream()), "tante_l2norm_rows")
+    return out
+
+
+def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], in_nchw: bool, out_nchw: bool) -> torch.Tensor:
+    """tante_conv3x3: x (n, Cin, H, W) or (n, H, W, Cin) fp32 -> (n, Cout, H, W) or (n, H, W, Cout) fp32."""
+    weight = weight.detach()
+    bias = None if bias is None else bias.detach()
+    K._dev(x, weight, bias)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError("the 3 x 3 convolution takes fp32 images of four dimensions")
+    n = x.shape[0]
+    Cin, H, W = (x.shape[1], x.shape[2], x.shape[3]) if in_nchw else (x.shape[3], x.shape[1], x.shape[2])
+    Cout = weight.shape[0]
+    if tuple(weight.shape) != (Cout, Cin, 3, 3):
+        raise RuntimeError(f"the weight must be ({Cout}, {Cin}, 3, 3), got {tuple(weight.shape)}")
+    out = torch.empty((n, Cout, H, W) if out_nchw else (n, H, W, Cout), dtype=torch.float32, device=x.device)
+    L.check(L.lib().tante_conv3x3(K._p(x), n, Cin, H, W, int(in_nchw), K._p(weight), K._p(bias), Cout, K._p(out), int(out_nchw), K._stream()),
+            "tante_conv3x3")
+    return out
+
+
+def _conv3x3_any(x: torch.Tensor, conv: nn.Conv2d, cache: _PackCache, in_nchw: bool, out_nchw: bool) -> torch.Tensor:
+    """The edge convolutions: tante_conv3x3 where it serves, tante_im2col + tante_gemm (fp32) beyond."""
+    n = x.shape[0]
+    Cin, H, W = (x.shape[1], x.shape[2], x.shape[3]) if in_nchw else (x.shape[3], x.shape[1], x.shape[2])
+    Cout = conv.weight.shape[0]
+    if conv3x3_supported_py(n, Cin, Cout, H, W):
+        return conv3x3(x, conv.weight, conv.bias, in_nchw, out_nchw)
+    korder = 0 if in_nchw else 1
+    chunks = cache.get(("im2col", korder), [conv.weight, conv.bias],
+                       lambda: S.pack_linear_chunks(S.conv_weight_2d(conv.weight, korder).contiguous(), conv.bias.detach(), L.F32))
+    cols = K.im2col(x, in_nchw, n, Cin, H, W, 3, 3, 1, 1, 1, 1, korder, torch.float32)
+    y = S.linear_chunks(cols, chunks, torch.float32)
+    return S._rows_to_nchw(y, n, H, W) if out_nchw else y.view(n, H, W, Cout)
+
+
+# ---- the reference's modules -------------------------------------------------------------------------------------------------------
+def _gpu(x: torch.Tensor):
+    if not x.is_cuda:
+        raise RuntimeError("tante_amd.UNetConvNext runs on the GPU only (no CPU fallback); move the model and its input to cuda")
+
+
+def _inference_only(module: nn.Module):
+    if module.training or (torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters())):
+        raise NotImplementedError("tante_amd.UNetConvNext is inference only: training is out of scope (the backward of the fused block is a "
+                                  "kernel of its own that is not built); call .eval() under torch.no_grad()")
+
+
+def _two_d(n_spatial_dims: int):
+    if n_spatial_dims != 2:
+        raise NotImplementedError(f"n_spatial_dims = {n_spatial_dims} is out of scope: the HIP path serves 2-D fields")
+
+
+def _to_nhwc(x: torch.Tensor) -> torch.Tensor:
+    return x.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
+
+
+def _to_nchw(y: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    return y.permute(0, 3, 1, 2).contiguous().to(like.dtype)
+
+
+class LayerNorm(nn.Module):
+    """unet_convnext.py:39-70.  channels_last: a LayerNorm over the last axis.  channels_first: NOT a LayerNorm but
+    F.normalize(x, p=2, dim=1, eps) * weight; `bias` is held and never applied.  A parameter holder: its owner folds the affine into the
+    GEMM behind it; forward evaluates it alone."""
+
+    def __init__(self, normalized_shape, n_spatial_dims, eps=1e-6, data_format="channels_last"):
+        super().__init__()
+        if data_format == "channels_last":
+            padded_shape = (normalized_shape,)
+        else:
+            padded_shape = (normalized_shape,) + (1,) * n_spatial_dims
+        self.weight = nn.Parameter(torch.ones(padded_shape))
+        self.bias = nn.Parameter(torch.zeros(padded_shape))
+        self.n_spatial_dims = n_spatial_dims
+        self.eps = eps
+        self.data_format = data_format
+        if self.data_format not in ["channels_last", "channels_first"]:
+            raise NotImplementedError
+        self.normalized_shape = (normalized_shape,)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """Inference only.  channels_last (..., C) -> (..., C); channels_first is evaluated by Downsample / Upsample."""
+        _inference_only(self)
+        if self.data_format != "channels_last":
+            raise NotImplementedError("the channels_first norm is evaluated by its Downsample / Upsample (tante_l2norm_rows, weight folded "
+                                      "into the convolution)")
+        _gpu(x)
+        return K.layernorm_affine(x.detach().to(torch.float32), self.weight.detach(), self.bias.detach(), self.eps).to(x.dtype)
+
+
+class _Resample(nn.Module):
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """(n, C, H, W) -> (n, C', H', W').  Inference only."""
+        _inference_only(self)
+        _gpu(x)
+        return _to_nchw(self.run(_to_nhwc(x), resolve_compute(None)), x)
+
+
+class Upsample(_Resample):
+    """channels-first norm -> ConvTranspose2d 2 x 2 / 2  (unet_convnext.py:73-86)."""
+
+    def __init__(self, dim_in, dim_out, n_spatial_dims=2):
+        super().__init__()
+        _two_d(n_spatial_dims)
+        self.block = nn.Sequential(LayerNorm(dim_in, n_spatial_dims, eps=1e-6, data_format="channels_first"),
+                                   nn.ConvTranspose2d(dim_in, dim_out, kernel_size=2, stride=2))
+        self._cache = _PackCache()
+
+    def _packed(self, compute: int):
+        norm, dec = self.block[0], self.block[1]
+        cin, cout = dec.weight.shape[0], dec.weight.shape[1]
+
+        def build():
+            w = fold_cf_norm(dec.weight.transpose(0, 1), norm.weight).transpose(0, 1).contiguous()      # (Cin, Cout, 2, 2)
+            if cin <= S.KMAX:
+                return K.pack_weight(w, dec.bias.detach(), compute, L.W_DECONV_NHWC, N=cout * 4, K=cin, P=2, C_other=cout)
+            return S.pack_linear_chunks(w.permute(2, 3, 1, 0).reshape(-1, cin).contiguous(), None, compute)
+        return self._cache.get(compute, [norm.weight, dec.weight, dec.bias], build)
+
+    def run(self, x: torch.Tensor, compute: int) -> torch.Tensor:
+        """x (n, H, W, C) fp32 -> (n, 2 H, 2 W, C') fp32."""
+        compute = _site(compute, "resample")
+        n, H, W, C_ = x.shape
+        dec = self.block[1]
+        cout = dec.weight.shape[1]
+        pw = self._packed(compute)
+        rows = l2norm_rows(x.view(n * H * W, C_), self.block[0].eps, K.act_torch_dtype(compute))
+        if isinstance(pw, K.PackedWeight):
+            img = torch.empty(n, 2 * H, 2 * W, cout, dtype=torch.float32, device=x.device)
+            return K.deconv(rows, pw, img, n_img=n, Hi=H, Wi=W, P=2, Cout=cout, nchw_out=False, act=L.ACT_NONE)
+        taps = S.linear_chunks(rows, pw, torch.float32)
+        return K.col2im_nhwc(taps, n, H, W, 2, 2, 0, cout, dec.bias.detach(), torch.float32)
+
+
+class Downsample(_Resample):
+    """channels-first norm -> Conv2d 2 x 2 / 2  (unet_convnext.py:89-100)."""
+
+    def __init__(self, dim_in, dim_out, n_spatial_dims=2):
+        super().__init__()
+        _two_d(n_spatial_dims)
+        self.block = nn.Sequential(LayerNorm(dim_in, n_spatial_dims, eps=1e-6, data_format="channels_first"),
+                                   nn.Conv2d(dim_in, dim_out, kernel_size=2, stride=2))
+        self._cache = _PackCache()
+
+    def _packed(self, compute: int):
+        norm, conv = self.block[0], self.block[1]
+        return self._cache.get(compute, [norm.weight, conv.weight, conv.bias], lambda: S.pack_linear_chunks(
+            _conv_rows(fold_cf_norm(conv.weight, norm.weight)), conv.bias.detach(), compute))
+
+    def run(self, x: torch.Tensor, compute: int) -> torch.Tensor:
+        """x (n, H, W, C) fp32 -> (n, H / 2, W / 2, C') fp32."""
+        compute = _site(compute, "resample")
+        n, H, W, C_ = x.shape
+        if H % 2 or W % 2:
+            raise ValueError(f"the 2 x 2 / 2 convolution takes even H and W, got {H} x {W}")
+        adt = K.act_torch_dtype(compute)
+        rows = l2norm_rows(x.view(n * H * W, C_), self.block[0].eps, adt)
+        cols = K.im2col(rows, False, n, C_, H, W, 2, 2, 2, 2, 0, 0, 1, adt)
+        y = S.linear_chunks(cols, self._packed(compute), torch.float32)
+        return y.view(n, H // 2, W // 2, -1)
+
+
+class Block(nn.Module):
+    """dwconv 7 x 7 -> LayerNorm -> Linear C -> 4 C -> GELU -> Linear 4 C -> C -> gamma -> + input  (unet_convnext.py:103-148)."""
+
+    def __init__(self, dim, n_spatial_dims, drop_path=0.0, layer_scale_init_value=1e-6):
+        super().__init__()
+        _two_d(n_spatial_dims)
+        if drop_path > 0.0:
+            raise NotImplementedError("drop_path > 0 is out of scope: the reference's UNetConvNext builds every block with 0")
+        self.n_spatial_dims = n_spatial_dims
+        self.dwconv = nn.Conv2d(dim, dim, kernel_size=7, padding=3, groups=dim)
+        self.norm = LayerNorm(dim, n_spatial_dims, eps=1e-6)
+        self.pwconv1 = nn.Linear(dim, 4 * dim)
+        self.act = nn.GELU()
+        self.pwconv2 = nn.Linear(4 * dim, dim)
+        self.gamma = nn.Parameter(layer_scale_init_value * torch.ones((dim)), requires_grad=True) if layer_scale_init_value > 0 else None
+        self.drop_path = nn.Identity()
+        self._cache = _PackCache()
+
+    def _params(self):
+        return [self.dwconv.weight, self.dwconv.bias, self.norm.weight, self.norm.bias, self.pwconv1.weight, self.pwconv1.bias, self.pwconv2.weight,
+                self.pwconv2.bias] + ([self.gamma] if self.gamma is not None else [])
+
+    def _folded(self):
+        return fold_block(self.norm.weight, self.norm.bias, self.pwconv1.weight, self.pwconv1.bias, self.pwconv2.weight, self.pwconv2.bias, self.gamma)
+
+    def _packed_fused(self, compute: int):
+        C_ = self.dwconv.weight.shape[0]
+        return self._cache.get(("fused", compute), self._params(),
+                               lambda: pack_convnext(self.dwconv.weight, self.dwconv.bias, *self._folded(), C_, compute))
+
+    def _packed_modular(self, compute: int):
+        C_ = self.dwconv.weight.shape[0]
+
+        def build():
+            w1, b1, w2, b2 = self._folded()
+            return (self.dwconv.weight.detach().reshape(C_, 49).contiguous(), self.dwconv.bias.detach().contiguous(),
+                    S.pack_linear_chunks(w1, b1, compute), S.pack_linear_chunks(w2, b2, compute))
+        return self._cache.get(("modular", compute), self._params(), build)
+
+    def run(self, x: torch.Tensor, compute: int, out: Optional[torch.Tensor] = None, fused: Optional[bool] = None) -> torch.Tensor:
+        """x (n, H, W, C) fp32 -> `out` (a new tensor by default; never x)."""
+        compute = _site(compute, "block")
+        n, H, W, C_ = x.shape
+        fused = (FUSED and C_ <= FUSED_DEFAULT_MAX_C) if fused is None else fused
+        if out is None:
+            out = torch.empty_like(x)
+        if fused and convnext_block_supported_py(n, H, W, C_):
+            return convnext_block(x, self._packed_fused(compute), compute, self.norm.eps, out)
+        if not dwconv_ln_supported_py(n, H, W, C_):
+            raise NotImplementedError(f"a block of {C_} channels is out of scope: tante_dwconv_ln serves 1..{DWLN_MAX_C}")
+        dw_w, dw_b, fc1, fc2 = self._packed_modular(compute)
+        adt = K.act_torch_dtype(compute)
+        a = dwconv_ln(x, dw_w, dw_b, self.norm.eps, None, None, adt)
+        h = _gemm(a, fc1, adt, L.ACT_GELU_ERF)
+        _gemm(h, fc2, residual=x.view(n * H * W, C_), out=out.view(n * H * W, C_))          # gamma folded; the skip rides the residual operand
+        return out
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """(n, C, H, W) -> (n, C, H, W)  (unet_convnext.py:134-148).  Inference only."""
+        _inference_only(self)
+        _gpu(x)
+        return _to_nchw(self.run(_to_nhwc(x), resolve_compute(None)), x)
+
+
+class Stage(nn.Module):
+    """skip_proj -> blocks -> resample  (unet_convnext.py:151-199)."""
+
+    def __init__(self, dim_in, dim_out, n_spatial_dims, depth=1, drop_path=0.0, layer_scale_init_value=1e-6, mode="down", skip_project=False):
+        super().__init__()
+        _two_d(n_spatial_dims)
+        if skip_project:
+            self.skip_proj = nn.Conv2d(2 * dim_in, dim_in, 1)
+        else:
+            self.skip_proj = nn.Identity()
+        if mode == "down":
+            self.resample = Downsample(dim_in, dim_out, n_spatial_dims)
+        elif mode == "up":
+            self.resample = Upsample(dim_in, dim_out, n_spatial_dims)
+        else:
+            self.resample = nn.Identity()
+        self.blocks = nn.ModuleList([Block(dim_in, n_spatial_dims, drop_path, layer_scale_init_value) for _ in range(depth)])
+        self._cache = _PackCache()
+
+    def _packed_skip(self, compute: int):
+        sp = self.skip_proj
+        C_ = sp.weight.shape[0]
+
+        def build():
+            w = sp.weight.detach().reshape(C_, 2 * C_)
+            return (S.pack_linear_chunks(w[:, :C_].contiguous(), sp.bias.detach(), compute), S.pack_linear_chunks(w[:, C_:].contiguous(), None, compute))
+        return self._cache.get(compute, [sp.weight, sp.bias], build)
+
+    def project(self, x: torch.Tensor, skip: torch.Tensor, compute: int) -> torch.Tensor:
+        """skip_proj(cat([x, skip], channels)) without the concatenation: W[:, :C] x + b, then + W[:, C:] skip through the residual operand."""
+        compute = _site(compute, "skip")
+        n, H, W, C_ = x.shape
+        if tuple(skip.shape) != tuple(x.shape):
+            raise ValueError(f"the skip must have the stream's shape {tuple(x.shape)}, got {tuple(skip.shape)}")
+        wx, ws = self._packed_skip(compute)
+        out = _gemm(x.view(n * H * W, C_), wx)
+        _gemm(skip.view(n * H * W, C_), ws, residual=out, out=out)
+        return out.view(n, H, W, C_)
+
+    def run(self, x: torch.Tensor, compute: int, skip: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x (n, H, W, C) fp32 channels-last (and the skip of the same shape for a stage with skip_proj) -> the stage's output.  x and skip
+        are left unchanged: the blocks ping-pong two buffers of the stage's own."""
+        if isinstance(self.skip_proj, nn.Identity):
+            if skip is not None:
+                raise ValueError("this stage has no skip projection")
+        else:
+            if skip is None:
+                raise ValueError("a stage with skip_proj takes the skip")
+            x = self.project(x, skip, compute)
+        bufs = [torch.empty_like(x) for _ in range(min(len(self.blocks), 2))]
+        for i, blk in enumerate(self.blocks):
+            x = blk.run(x, compute, bufs[i % 2])
+        if not isinstance(self.resample, nn.Identity):
+            x = self.resample.run(x, compute)
+        return x
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """(n, C, H, W), or (n, 2 C, H, W) = cat([x, skip]) for a stage with skip_proj -> the stage's output, channels first.  Inference only."""
+        _inference_only(self)
+        _gpu(x)
+        compute = resolve_compute(None)
+        if isinstance(self.skip_proj, nn.Identity):
+            return _to_nchw(self.run(_to_nhwc(x), compute), x)
+        C_ = self.skip_proj.weight.shape[0]
+        return _to_nchw(self.run(_to_nhwc(x[:, :C_]), compute, _to_nhwc(x[:, C_:])), x)
+
+
+class UNetConvNext(nn.Module):
+    """models/unet_convnext.py:202-283 -- same constructor, attributes, parameters and forward contract."""
+
+    def __init__(self, in_T, dset_metadata, stages: int = 4, blocks_per_stage: int = 1, blocks_at_neck: int = 1, n_spatial_dims: int = 2,
+                 init_features: int = 32, gradient_checkpointing: bool = False):
+        super().__init__()
+        n_channel = dset_metadata.n_fields
+        dim_in = n_channel * in_T
+        dim_out = n_channel
+        self.dset_metadata = dset_metadata
+        n_spatial_dims = dset_metadata.n_spatial_dims                       # the argument is ignored (unet_convnext.py:219)
+        _two_d(n_spatial_dims)
+        self.n_spatial_dims = n_spatial_dims
+        features = init_features
+        self.gradient_checkpointing = gradient_checkpointing
+        encoder_dims = [features * 2 ** i for i in range(stages + 1)]
+        decoder_dims = [features * 2 ** i for i in range(stages, -1, -1)]
+        encoder = []
+        decoder = []
+        self.in_proj = nn.Conv2d(dim_in, features, kernel_size=3, padding=1)
+        self.out_proj = nn.Conv2d(features, dim_out, kernel_size=3, padding=1)
+        for i in range(stages):
+            encoder.append(Stage(encoder_dims[i], encoder_dims[i + 1], n_spatial_dims, blocks_per_stage, mode="down"))
+            decoder.append(Stage(decoder_dims[i], decoder_dims[i + 1], n_spatial_dims, blocks_per_stage, mode="up", skip_project=i != 0))
+        self.encoder = nn.ModuleList(encoder)
+        self.neck = Stage(encoder_dims[-1], encoder_dims[-1], n_spatial_dims, blocks_at_neck, mode="neck")
+        self.decoder = nn.ModuleList(decoder)
+        self.dim_in, self.dim_out, self.stages = dim_in, dim_out, stages
+        self.compute: Optional[str] = None
+        self._cache = _PackCache()
+
+    def set_compute(self, mode: Optional[str]):
+        if mode is not None and mode not in K.COMPUTE:
+            raise ValueError("compute must be None, 'fp32' or 'bf16'")
+        self.compute = mode
+        return self
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x (b, t, c, h, w) -> (b, 1, c, h, w)   (unet_convnext.py:269-283)."""
+        _inference_only(self)
+        if x.dim() != 5:
+            raise ValueError(f"expected (B, T, C, H, W), got {tuple(x.shape)}")
+        b, t, c, h, w = x.shape
+        if t * c != self.dim_in:
+            raise ValueError(f"the input has t * c = {t} * {c} = {t * c} channels, in_proj takes dim_in = n_fields * in_T = {self.dim_in}")
+        div = 2 ** self.stages
+        if h % div or w % div:
+            raise ValueError(f"H and W must be multiples of 2 ** stages = {div} (the decoder's skips would not match), got {h} x {w}")
+        _gpu(x)
+        compute = resolve_compute(self.compute)
+        x4 = x.detach().to(torch.float32).contiguous().view(b, t * c, h, w)       # b t c h w contiguous IS b (t c) h w
+        cur = _conv3x3_any(x4, self.in_proj, self._cache, True, False)
+        skips = []
+        for enc in self.encoder:
+            skips.append(cur)                                                   # skips[0] is stored and never read, as in the reference
+            cur = enc.run(cur, compute)
+        cur = self.neck.run(cur, compute)
+        for j, dec in enumerate(self.decoder):
+            cur = dec.run(cur, compute, skips[-j] if j > 0 else None)
+        y = _conv3x3_any(cur, self.out_proj, self._cache, False, True)
+        return y.view(b, 1, self.dim_out, h, w)
