@@ -1036,6 +1036,43 @@ int tante_conv3x3_supported(int64_t n_img, int Cin, int Cout, int H, int W);
 int tante_conv3x3(const float* x, int64_t n_img, int Cin, int H, int W, int in_nchw, const float* w, const float* bias, int Cout, float* y, int out_nchw,
                   void* stream);
 
+/* ---- AttentionUNet: a dense 3 x 3 convolution as an implicit GEMM on the matrix pipe, and the attention gate (unet_att.hip; added
+ * without an ABI bump: nothing that existed changed) ----
+ * tante_conv3x3_mfma: y (n_img, H, W, Cout) = act(conv3x3(src) + shift), padding 1, stride 1, channels-last, replacing
+ * Conv2d(3, padding 1) -> BatchNorm2d (eval) -> ReLU (unet_att.py:11-16, 31-33).  The caller folds the norm: scale =
+ * bn.weight / sqrt(running_var + eps) into the weights before packing, shift = bn.bias + (conv.bias - running_mean) * scale (Cout
+ * floats, or NULL).  act is TANTE_ACT_NONE or TANTE_ACT_RELU; y_dtype TANTE_F32 or TANTE_BF16.  The source form (`form`) lets the
+ * staging loop read what the model would otherwise write:
+ *   0 plain      a (n_img, H, W, Ca); with Cb > 0 a second source b (n_img, H, W, Cb) supplies channels Ca .. Ca + Cb - 1
+ *                (torch.cat((s, d), dim=1), unet_att.py:149-169); Hs = H, Ws = W
+ *   1 pooled     a (n_img, Hs, Ws, Ca), H = Hs / 2, W = Ws / 2 (floor): each value is the max of its 2 x 2 window
+ *                (MaxPool2d(2, 2), unet_att.py:94, 132-145)
+ *   2 upsampled  a (n_img, Hs, Ws, Ca), H = 2 Hs, W = 2 Ws, read at (y >> 1, x >> 1) (nn.Upsample(scale_factor=2), unet_att.py:30)
+ * A workgroup owns a pixel tile of ONE image with its 1-pixel halo, staged in LDS in chunks of 64 or 128 channels with zeros outside the
+ * image (the neighbouring image is never read), and a group of output channels; K runs over (channel chunk, k-step, tap) in a fixed
+ * order; TANTE_F32 uses v_mfma_f32_16x16x4_f32, TANTE_BF16 rounds both operands to bf16 and uses v_mfma_f32_16x16x32_bf16 with fp32
+ * accumulation.  No atomics, no split-K through memory: a pixel's result does not depend on the tile form, its tile or its image's
+ * place in the batch.  Served: 1 <= Ca + Cb <= 2048, 1 <= Cout <= 1024, any H, W >= 1 (even for form 2), Cb > 0 only with form 0;
+ * otherwise -2 with the reason.  y must not alias a source.
+ * tante_pack_conv3x3: w (Cout, Cin, 3, 3) fp32 on the device (scale folded) -> tante_conv3x3_pack_bytes(Cin, Cout, compute) bytes
+ * (16-byte aligned) in the fragment order of `compute`, padded channels written as zeros. */
+int tante_conv3x3_mfma_supported(int64_t n_img, int Ca, int Cb, int Cout, int H, int W, int form);
+int64_t tante_conv3x3_pack_bytes(int Cin, int Cout, int compute);
+int tante_pack_conv3x3(const float* w, int Cin, int Cout, int compute, void* out, void* stream);
+int tante_conv3x3_mfma(const float* a, int Ca, const float* b, int Cb, int64_t n_img, int H, int W, int form, int Hs, int Ws, const void* packed,
+                       const float* shift, int Cout, int act, int compute, void* y, int y_dtype, void* stream);
+/* tante_attn_gate: AttentionBlock.forward (unet_att.py:70-76) on channels-last rows g (M, Cg), x (M, Cx) fp32, one launch:
+ *   psi = sigmoid(w_psi . relu(W [g | x] + b) + b_psi),  out (M, Cx) fp32 = x * psi
+ * The caller folds the three BatchNorms (unet_att.py:52-66): W (N, Cg + Cx) = [W_gate' | W_x'], b = b_gate' + b_x', w_psi (N), b_psi.
+ * The product is one MFMA GEMM with K = Cg + Cx (TANTE_F32 / TANTE_BF16 as above); the N hidden values stay in registers and the dot
+ * product with w_psi is reduced in a fixed order.  Served: Cg, Cx >= 1 with Cg + Cx <= 1024 and 1 <= N <= 256 (the reference's gates
+ * are Cg = Cx = C, N = C / 2 for C = 64 .. 512); otherwise -2.  out may alias x.
+ * tante_pack_attn_gate: W, b, w_psi fp32 on the device and b_psi -> one stream of tante_attn_gate_stream_bytes bytes (16-byte aligned). */
+int tante_attn_gate_supported(int64_t M, int Cg, int Cx, int N);
+int64_t tante_attn_gate_stream_bytes(int Cg, int Cx, int N, int compute);
+int tante_pack_attn_gate(const float* w, const float* bias, const float* wpsi, float bpsi, int Cg, int Cx, int N, int compute, void* out, void* stream);
+int tante_attn_gate(const float* g, const float* x, int64_t M, int Cg, int Cx, int N, const void* gate_stream, int compute, float* out, void* stream);
+
 const char* tante_last_error(void);
 int tante_abi_version(void);
 

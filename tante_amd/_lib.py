@@ -299,12 +299,21 @@ SIGNATURES = {
     "tante_l2norm_rows": ([c_vp, c_i64, c_i32, c_f32, c_vp, c_i32, c_vp], c_i32),
     "tante_conv3x3_supported": ([c_i64, c_i32, c_i32, c_i32, c_i32], c_i32),
     "tante_conv3x3": ([c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp], c_i32),
+    "tante_conv3x3_mfma_supported": ([c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32], c_i32),
+    "tante_conv3x3_pack_bytes": ([c_i32, c_i32, c_i32], c_i64),
+    "tante_pack_conv3x3": ([c_vp, c_i32, c_i32, c_i32, c_vp, c_vp], c_i32),
+    "tante_conv3x3_mfma": ([c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp],
+                           c_i32),
+    "tante_attn_gate_supported": ([c_i64, c_i32, c_i32, c_i32], c_i32),
+    "tante_attn_gate_stream_bytes": ([c_i32, c_i32, c_i32, c_i32], c_i64),
+    "tante_pack_attn_gate": ([c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp], c_i32),
+    "tante_attn_gate": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp], c_i32),
 }
 
 # every option name the library looks up (tante_opt in csrc/): tests/test_host_cpu.py checks this list against the sources
 LIB_OPTIONS = ("TANTE_ATTN_BWD_HG", "TANTE_ATTN_BWD_NO_SPLIT", "TANTE_ATTN_BWD_VALU", "TANTE_ATTN_FWD_VALU", "TANTE_AXIS_BWD_SMALL_WGS",
                "TANTE_AXIS_BLOCKS", "TANTE_AXIS_BWD_WGS", "TANTE_AXIS_CT", "TANTE_AXIS_FILM", "TANTE_AXIS_GENERIC", "TANTE_AXIS_MFMA", "TANTE_AXIS_NT", "TANTE_AXIS_WGRAD_WGS",
-               "TANTE_BLOCK_KERNEL", "TANTE_COLSUM_ROWS", "TANTE_CVIT_CHAIN_TOKENS", "TANTE_ENC23_SPLIT", "TANTE_FILM_BWD_ROWS",
+               "TANTE_BLOCK_KERNEL", "TANTE_COLSUM_ROWS", "TANTE_CONV3_FORM","TANTE_CVIT_CHAIN_TOKENS", "TANTE_ENC23_SPLIT", "TANTE_FILM_BWD_ROWS",
                "TANTE_FS_GROUPS", "TANTE_FS_HALF", "TANTE_FS_SKEW", "TANTE_FS_WAVES", "TANTE_GEMM_NO_LITE", "TANTE_GEMM_SMALLM", "TANTE_GEMM_WGS", "TANTE_HEAD_WAVES",
                "TANTE_IM2COL_TILED", "TANTE_RAW_ENCODE_ONE_LAUNCH", "TANTE_RESIZE_TILED", "TANTE_SPECTRAL_BF16OUT", "TANTE_SPECTRAL_DFT", "TANTE_SPECTRAL_X3", "TANTE_WGRAD_DEEP",
                "TANTE_WGRAD_JOBS", "TANTE_WGRAD_JOBS_WGS", "TANTE_WGRAD_NO_SLAB", "TANTE_WGRAD_NO_TR", "TANTE_WGRAD_REDUCE_NY",
@@ -312,7 +321,7 @@ LIB_OPTIONS = ("TANTE_ATTN_BWD_HG", "TANTE_ATTN_BWD_NO_SPLIT", "TANTE_ATTN_BWD_V
 
 
 _lib = None
-ABI_VERSION = 14     # include/tante_hip.h: bumped whenever an entry point is added or changes (round 4: 6 tante_head_enc_*, 7 tante_pos_embed_tmajor + tante_spectral_*bf16out*; round 5: 8 tante_block_bwd_fused, 9 TanteGemm.a_pad; round 6: 10 tante_tail_*, 11 tante_attention_masked_bwd, 12 tante_spectral_layer_x, tante_axis_mlp_film; round 7: 13 tante_block_fused_last; 14 tante_attention_flash*; still 14: tante_attention_flash_masked + tante_attention_flash_masked_bwd were ADDED without a bump -- nothing that existed changed its signature or meaning, so a caller built against 14 runs unchanged, and the suite pins 14 (test_abi_version_is_14); a caller that needs the two looks the symbols up; the same holds for the six tante_adaptive_* / tante_head_adaptive entries of the adaptive-step tail, for tante_cross_attention_route, for the four tante_afno_* entries of the AFNO filter, for the three tante_groupnorm* and four tante_dpot_* entries of DPOT, for the twelve tante_instnorm* / tante_axial_attention* / tante_time_attention* / tante_field_* entries of AViT, for tante_encode_window_raw with its three tante_*enc1_raw* helpers, and for the ten tante_convnext_* / tante_pack_convnext / tante_dwconv_ln* / tante_l2norm_rows* / tante_conv3x3* entries of UNetConvNext)
+ABI_VERSION = 14     # include/tante_hip.h: bumped whenever an entry point is added or changes (round 4: 6 tante_head_enc_*, 7 tante_pos_embed_tmajor + tante_spectral_*bf16out*; round 5: 8 tante_block_bwd_fused, 9 TanteGemm.a_pad; round 6: 10 tante_tail_*, 11 tante_attention_masked_bwd, 12 tante_spectral_layer_x, tante_axis_mlp_film; round 7: 13 tante_block_fused_last; 14 tante_attention_flash*; still 14: tante_attention_flash_masked + tante_attention_flash_masked_bwd were ADDED without a bump -- nothing that existed changed its signature or meaning, so a caller built against 14 runs unchanged, and the suite pins 14 (test_abi_version_is_14); a caller that needs the two looks the symbols up; the same holds for the six tante_adaptive_* / tante_head_adaptive entries of the adaptive-step tail, for tante_cross_attention_route, for the four tante_afno_* entries of the AFNO filter, for the three tante_groupnorm* and four tante_dpot_* entries of DPOT, for the twelve tante_instnorm* / tante_axial_attention* / tante_time_attention* / tante_field_* entries of AViT, for tante_encode_window_raw with its three tante_*enc1_raw* helpers, and for the ten tante_convnext_* / tante_pack_convnext / tante_dwconv_ln* / tante_l2norm_rows* / tante_conv3x3* entries of UNetConvNext, and for the eight tante_conv3x3_mfma* / tante_pack_conv3x3 / tante_conv3x3_pack_bytes / tante_attn_gate* / tante_pack_attn_gate entries of AttentionUNet)
 
 
 def lib():
