@@ -236,8 +236,12 @@ int tante_rt_reduce(const float* t, int B, int L, float out_T, float ep, float* 
  * outputs and the MLP hidden layer never leave the CU.  It consumes the "weight stream" built by
  * tante_pack_block from the block's 12 fp32 parameters (LayerNorm affine folded, 1/sqrt(d) folded into q,
  * bf16, k-permuted LDS tile images in consumption order).
- * Supported: head dim 32, C in {64,128,256}, hidden in {C, 2C} (C = 256: hidden = 256), sequence length L
- * dividing 32 (tante_block_fused_supported); anything else goes through tante_gemm + tante_attention. */
+ * Supported (tante_block_fused_supported): head dim 32 and either
+ *   C = 256, 8 heads, hidden 256: any sequence length 1 <= L <= 128, fewer than 2^23 sequences (the feature-sliced kernel), or
+ *   C in {64, 128}, hidden in {C, 2C}: L dividing 32 (the token-stationary kernels; at C = 256 / hidden 256 only on request,
+ *   tante_set_option("TANTE_BLOCK_KERNEL", 16 or 32), any other value leaves the choice to the library).
+ * Anything else (L > 128, hidden 512 at C = 256, ...) is refused with -2 and goes through tante_gemm + tante_attention; a null or
+ * misaligned (16 bytes) x / block_stream is a bad argument, -1. */
 int tante_block_fused_supported(int C, int n_head, int hidden, int L);
 int64_t tante_block_stream_bytes(int C, int hidden);
 int tante_pack_block(const float* ln1_w, const float* ln1_b, const float* in_w, const float* in_b, const float* out_w,
@@ -246,8 +250,10 @@ int tante_pack_block(const float* ln1_w, const float* ln1_b, const float* in_w, 
 int tante_block_fused(float* x, const void* block_stream, int C, int n_head, int hidden, const TanteSeq* seq, int causal,
                       float eps, void* stream);
 /* The same at L = 4 (the T letter) WITH the temporal propagator of attn_backbone.py:144-145 applied to the rows first, inside the launch:
- * tprop = w1 (4 x 4, row-major), b1 (4), w2 (4 x 4), b2 (4) -- 40 floats in device memory.  Equals tante_axis_mlp_c (bf16 compute) along the
- * T axis followed by tante_block_fused, bit for bit, in one pass over x. */
+ * tprop = w1 (4 x 4, row-major), b1 (4), w2 (4 x 4), b2 (4) -- 40 floats in device memory.  The same function as tante_axis_mlp_c (bf16
+ * compute) along the T axis followed by tante_block_fused, in one pass over x -- NOT bit for bit: the propagated rows agree to fp32
+ * rounding (the contractions run as v_mfma_f32_4x4x1 here, as v_pk_fma_f32 chains there), and behind the block a last-bit difference of a
+ * row moves a bf16 rounding here and there (tests/test_hip_block_forms.py holds both to float64 and the pair to 2e-4 / 2e-3). */
 int tante_block_fused_tprop(float* x, const void* block_stream, int C, int n_head, int hidden, const TanteSeq* seq, int causal, float eps,
                             const float* tprop, void* stream);
 /* The last-slot form of the T letter (L = 4), tprop = the propagator's 40 floats (as tante_block_fused_tprop) or NULL (as

@@ -716,8 +716,10 @@ void launch_block16(float* x, const char* stream, const TanteSeq& sq, int causal
 
 template <int CB, int HB>
 void launch_block(float* x, const char* stream, const TanteSeq& sq, int causal, float eps, hipStream_t s) {
-  const int which = tante_opt("TANTE_BLOCK_KERNEL", 16);
-  if (which == 16 && (sq.L == 32 || 16 % sq.L == 0)) return launch_block16<CB, HB>(x, stream, sq, causal, eps, s);
+  // only 32 selects the 256-thread form: an option that was set and put back to 0 ("no choice", what use_fs reads it as -- the table has
+  // no unset) must leave the shipping 16 form in place at C = 64 / 128, not fall through to the A/B kernel
+  const int which = tante_opt("TANTE_BLOCK_KERNEL", 0);
+  if (which != 32 && (sq.L == 32 || 16 % sq.L == 0)) return launch_block16<CB, HB>(x, stream, sq, causal, eps, s);
   constexpr int TH = 96 * CB * 4 * 16 + BIAS_BYTES, T2 = 64 * HB * 4 * 16 + BIAS_BYTES;
   constexpr int SLOT = TH > T2 ? TH : T2;
   const int spw = 32 / sq.L;

@@ -100,7 +100,8 @@ struct FsSeqMap {
 // xs[t] = 4 channels of time step t of ONE sequence, all four in the same lane.  v_mfma_f32_4x4x1_16B_f32: 16 blocks of (4 x 1)(1 x 4)
 // outer products, lane 4 b + j = column j of block b -- every lane is its own column, its four accumulator registers are the four
 // hidden units (first product) / time steps (second), and lane 4 b + i supplies row i of the 4 x 4 weight, the same for every block.
-// fp32 in, fp32 accumulate (a k-ordered fma chain from the bias), no cross-lane traffic.  tp = w1 (4 x 4) | b1 | w2 (4 x 4) | b2.
+// fp32 in, fp32 accumulate (k-ordered from the bias; NOT bit for bit the v_pk_fma_f32 chain of axis_mlp_vec_kernel in the same order: the rows
+// agree to fp32 rounding, tests/test_hip_block_forms.py), no cross-lane traffic.  tp = w1 (4 x 4) | b1 | w2 (4 x 4) | b2.
 struct TpropW {
   float w1c[4], w2c[4];
   f32x4 b1v, b2v;
@@ -319,7 +320,7 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
       // sequence), and the two 4 x 4 contractions run as v_mfma_f32_4x4x1_16B_f32: 16 blocks of (4 x 1)(1 x 4) outer products per
       // instruction, lane 4 b + j = column j of block b, i.e. EVERY LANE IS ITS OWN COLUMN (its channel), the four accumulator registers
       // are the four hidden units / time steps, and lane 4 b + i supplies row i of the 4 x 4 weight (the same for every block).  fp32 in,
-      // fp32 accumulate (an exact k-ordered fma chain), no cross-lane traffic at all; the matrix pipe is idle in this phase anyway.
+      // fp32 accumulate (k-ordered), no cross-lane traffic at all; the matrix pipe is idle in this phase anyway.
       constexpr int GPW = 4 * NTT / NW;      // sequences (groups of 4 token rows) per wave
       f32x4 xv[GPW][4];
 #pragma unroll
