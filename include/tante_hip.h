@@ -1079,6 +1079,44 @@ int64_t tante_attn_gate_stream_bytes(int Cg, int Cx, int N, int compute);
 int tante_pack_attn_gate(const float* w, const float* bias, const float* wpsi, float bpsi, int Cg, int Cx, int N, int compute, void* out, void* stream);
 int tante_attn_gate(const float* g, const float* x, int64_t M, int Cg, int Cx, int N, const void* gate_stream, int compute, float* out, void* stream);
 
+/* ---- UNO: the resampling spectral operator block (uno_ops.hip; added without an ABI bump: nothing that existed changed) ----
+ * tante_uno_block: OperatorBlock_2D.forward (uno.py:44-56) on channels-first fp32 planes, x (B, Ci, Hi, Wi) -> out (B, Co, Ho, Wo):
+ *   spectral  = irfft2(out_ft, s=(Ho, Wo), 'forward'), out_ft[:m1, :m2] = rfft2(x, 'forward')[:m1, :m2] (x) weights1 and
+ *               out_ft[-m1:, :m2] = rfft2(x)[-m1:, :m2] (x) weights2, the second written last (uno.py:112-138)
+ *   pointwise = interpolate(conv1x1(x), (Ho, Wo), bicubic, align_corners, antialias)                          (uno.py:154-173)
+ *   out       = act(spectral + pointwise)
+ * pw_w NULL: the spectral convolution alone (SpectralConv2d_Uno.forward), pw_b ignored.  act: TANTE_ACT_NONE or TANTE_ACT_GELU_ERF.
+ * x_stride / out_stride: the distance between two images in elements (>= C H W), so either tensor may be a channel slice of a wider
+ * channels-first buffer.  Image b's result does not depend on B or on b.  Seven launches (eight per further 8 images): six products of
+ * v_mfma_f32_16x16x4_f32 against the tables (fp32 in both compute modes) and the mode mix, which reads w1 / w2 in place once per 8
+ * images; only the kept 2 m1 x m2 modes are ever computed; sums in a fixed order, no atomics.
+ *   w1, w2: weights1 / weights2 (Ci, Co, m1, m2) complex64 as torch.view_as_real gives them, 8-byte aligned.
+ *   pw_w (Co, Ci), pw_b (Co) or NULL: the 1 x 1 convolution as the state dict holds it.
+ *   tables: tante_uno_table_floats(...) floats, five dense row-major tables at the offsets tante_uno_table_layout writes into
+ *     layout[16] = {offset, rows, cols} x 5, then 1 if the 1 x 1 runs on the output grid (Ho Wo <= Hi Wi) and 0 if on the input grid.
+ *     With J = 2 m1, kin = [0..m1-1, Hi-m1..Hi-1], kout = [0..m1-1, Ho-m1..Ho-1], live[j] = 0 where kout[j] repeats at a later j,
+ *     A_w (Wo, Wi) and A_h (Ho, Hi) the resize as matrices:
+ *       T1 rows 2l, 2l+1 = cos, -sin(2 pi l w / Wi) / (Hi Wi), l < m2; then A_w's rows if layout[15] = 1 and pointwise
+ *       T2 (2J, 2Hi): row j = [cos | sin](2 pi kin[j] h / Hi), row J + j = [-sin | cos]
+ *       T3 = A_h (pointwise only, else empty)
+ *       T4 (2Ho, 2J): row y = live [cos | -sin](2 pi kout[j] y / Ho), row Ho + y = live [sin | cos]
+ *       T5 (Wo, 2 m2 [+ Wi]): [c_l cos | -c_l sin](2 pi l x / Wo), then A_w if layout[15] = 0 and pointwise; c_0 = 1, c_{Wo/2} = 1
+ *       (Wo even), 2 otherwise.
+ *   work: _workspace_bytes(...) bytes, 16-byte aligned.
+ * Served: 1 <= Ci, Co <= 512; 1 <= Hi, Wi, Ho, Wo <= 512; 1 <= m1 <= min(Hi, Ho); 1 <= m2 <= min(Wi, Wo) / 2 + 1;
+ * B max(Ci, Co) <= 65535; strides of at least an image; tensors 4-byte and w1 / w2 8-byte aligned; out not overlapping x.  Anything
+ * else returns -2 with the reason and launches nothing (_supported answers for the sizes and strides).
+ * tante_uno_mode_mix: the mix alone, X (B, Ci, 2, 2 m1, m2) -> Y (B, Co, 2, 2 m1, m2), [0] real and [1] imaginary planes. */
+int tante_uno_block_supported(int64_t B, int Ci, int Co, int Hi, int Wi, int Ho, int Wo, int m1, int m2, int64_t x_stride, int64_t out_stride);
+int64_t tante_uno_table_floats(int Hi, int Wi, int Ho, int Wo, int m1, int m2, int pointwise);
+int tante_uno_table_layout(int Hi, int Wi, int Ho, int Wo, int m1, int m2, int pointwise, int64_t* layout);
+int64_t tante_uno_block_workspace_bytes(int64_t B, int Ci, int Co, int Hi, int Wi, int Ho, int Wo, int m1, int m2, int pointwise);
+int tante_uno_block(const float* x, int64_t x_stride, int64_t B, int Ci, int Co, int Hi, int Wi, int Ho, int Wo, int m1, int m2,
+                    const float* tables, const float* w1, const float* w2, const float* pw_w, const float* pw_b, int act, float* out,
+                    int64_t out_stride, void* work, int64_t work_bytes, void* stream);
+int tante_uno_mode_mix_supported(int64_t B, int Ci, int Co, int m1, int m2);
+int tante_uno_mode_mix(const float* X, const float* w1, const float* w2, float* Y, int64_t B, int Ci, int Co, int m1, int m2, void* stream);
+
 const char* tante_last_error(void);
 int tante_abi_version(void);
 

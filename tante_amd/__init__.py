@@ -14,6 +14,7 @@ from .dpot import DPOT  # noqa: F401
 from .avit import AViT  # noqa: F401
 from .convnext import UNetConvNext  # noqa: F401
 from .unet_att import AttentionUNet  # noqa: F401
+from .uno import UNO  # noqa: F401
 from .rollout import (DefaultChannelsFirstFormatter, DefaultChannelsLastFormatter, rollout_model,  # noqa: F401
                       rollout_adaptive, GraphedRollout)
 from .config import instantiate, load_config, build_model  # noqa: F401
@@ -27,4 +28,4 @@ from .harness import LinearWarmupCosineAnnealingLR, SyntheticDataModule, save_ch
 
 __all__ = ["TANTE", "TanteMetadata", "enc_CNN", "dec_CNN", "film", "interprator", "t_series", "Attn_Backbone",
            "TransformerBlock", "DefaultChannelsFirstFormatter", "DefaultChannelsLastFormatter", "rollout_model",
-           "rollout_adaptive", "GraphedRollout", "instantiate", "load_config", "build_model", "CViT", "FNO", "AFNO", "DPOT", "AViT", "UNetConvNext", "AttentionUNet", "SpectralLayer", "enc_FNO", "dec_FNO", "set_option", "get_option"]
+           "rollout_adaptive", "GraphedRollout", "instantiate", "load_config", "build_model", "CViT", "FNO", "AFNO", "DPOT", "AViT", "UNetConvNext", "AttentionUNet", "UNO", "SpectralLayer", "enc_FNO", "dec_FNO", "set_option", "get_option"]

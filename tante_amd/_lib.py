@@ -308,6 +308,14 @@ SIGNATURES = {
     "tante_attn_gate_stream_bytes": ([c_i32, c_i32, c_i32, c_i32], c_i64),
     "tante_pack_attn_gate": ([c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp], c_i32),
     "tante_attn_gate": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp], c_i32),
+    "tante_uno_block_supported": ([c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64], c_i32),
+    "tante_uno_table_floats": ([c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32], c_i64),
+    "tante_uno_table_layout": ([c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp], c_i32),
+    "tante_uno_block_workspace_bytes": ([c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32], c_i64),
+    "tante_uno_block": ([c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64,
+                         c_vp, c_i64, c_vp], c_i32),
+    "tante_uno_mode_mix_supported": ([c_i64, c_i32, c_i32, c_i32, c_i32], c_i32),
+    "tante_uno_mode_mix": ([c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp], c_i32),
 }
 
 # every option name the library looks up (tante_opt in csrc/): tests/test_host_cpu.py checks this list against the sources

@@ -25,6 +25,8 @@ _TARGET_ALIASES = {
     "models.unet_convnext.UNetConvNext": "tante_amd.convnext.UNetConvNext",
     "models.AttentionUNet": "tante_amd.unet_att.AttentionUNet",
     "models.unet_att.AttentionUNet": "tante_amd.unet_att.AttentionUNet",
+    "models.UNO": "tante_amd.uno.UNO",
+    "models.uno.UNO": "tante_amd.uno.UNO",
     "models.enc_dec_fno.SpectralLayer": "tante_amd.spectral.SpectralLayer",
     "models.attn_backbone.Attn_Backbone": "tante_amd.attn_backbone.Attn_Backbone",
     "models.attn_backbone.TransformerBlock": "tante_amd.attn_backbone.TransformerBlock",
