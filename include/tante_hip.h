@@ -604,6 +604,28 @@ int64_t tante_afno_twiddle_floats(int H, int W);
 int64_t tante_afno_filter_workspace_bytes(int64_t B, int H, int W, int C);
 int tante_afno_filter(const float* x, const float* residual, int64_t B, int H, int W, int C, int bs, const float* twiddles, const float* w1,
                       const float* w2, float lambda, float* out, void* work, int64_t work_bytes, void* stream);
+/* The filter's backward (afno_filter_bwd.hip; added without an ABI bump: nothing that existed changed): what torch.autograd derives for
+ * afno.py:103-117 and the swap / skip of afno.py:154-159, for training a model that opted in (AFNO.set_trainable).  The forward is a
+ * chain of real-linear maps and two pointwise functions, P = T1 x, X = T2 P, U = X M1, V = gelu(U), Yp = V M2, Y = softshrink(Yp),
+ * G = T3 Y, out = Re(T4 G) + residual; the backward runs it in reverse against the conjugate-transposed tables, in three launches plus
+ * one reduce:
+ *   dG = T4^H dout;  dY = T3^H dG,  dYp = dY [|Yp| > lambda] (real and imaginary part separately),  dV = dYp M2^T,
+ *   dU = dV gelu'(U),  dX = dU M1^T,  dP = T2^H dX;  dx = Re(T1^H dP);  dM2 = V^T dYp,  dM1 = X^T dU, folded to the parameter's layout.
+ * X, U, V and Yp are recomputed from P (the first part of the forward's workspace, (B, Lc, H, 2, C) floats, which the caller keeps) with
+ * the forward's own instruction sequence, so the threshold decisions are the forward's bit for bit.  The gradient with respect to the
+ * residual is dout itself and is left to the caller.  Same served shapes and refusals as the forward; fp32 MFMA products throughout.
+ *   twiddles: the forward's buffer.  twiddles_bwd: T1^H (W, Lc), T2^H (H, Kc), T3^H (Kc, W), T4^H (Lc, H), packed like the forward's:
+ *     _twiddle_bwd_floats(H, W) floats in all (-1: unsupported grid).
+ *   dx (B, H, W, C).  dw1, dw2 (C / bs, bs, bs, 2): the gradients of ComplexBlockLinear.weight, summed over samples and modes in a fixed
+ *     order (per-workgroup partials in the workspace, then one reduce launch: no atomics, two runs give the same bits); accumulate != 0
+ *     adds them onto what dw1 / dw2 hold.
+ *   keep: NULL, or (B, Lc, Kc, 2, C) bytes that receive the threshold decisions [|Yp| > lambda] (1 = kept).
+ *   work: _bwd_workspace_bytes(B, H, W, C, bs) bytes, 16-byte aligned. */
+int64_t tante_afno_twiddle_bwd_floats(int H, int W);
+int64_t tante_afno_filter_bwd_workspace_bytes(int64_t B, int H, int W, int C, int bs);
+int tante_afno_filter_bwd(const float* dout, const float* P, int64_t B, int H, int W, int C, int bs, const float* twiddles,
+                          const float* twiddles_bwd, const float* w1, const float* w2, float lambda, float* dx, float* dw1, float* dw2,
+                          int accumulate, uint8_t* keep, void* work, int64_t work_bytes, void* stream);
 
 /* ---- DPOT: GroupNorm and the truncated-mode mixer (dpot_mixer.hip; added without an ABI bump: nothing that existed changed) ----
  * tante_groupnorm: torch.nn.GroupNorm(G, C) as Block.norm1 / norm2 use it (dpot.py:138, 147, 160, 167) on channels-last fp32 rows

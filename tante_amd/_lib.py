@@ -269,6 +269,10 @@ SIGNATURES = {
     "tante_afno_twiddle_floats": ([c_i32, c_i32], c_i64),
     "tante_afno_filter_workspace_bytes": ([c_i64, c_i32, c_i32, c_i32], c_i64),
     "tante_afno_filter": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_i64, c_vp], c_i32),
+    "tante_afno_twiddle_bwd_floats": ([c_i32, c_i32], c_i64),
+    "tante_afno_filter_bwd_workspace_bytes": ([c_i64, c_i32, c_i32, c_i32, c_i32], c_i64),
+    "tante_afno_filter_bwd": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp,
+                               c_i64, c_vp], c_i32),
     "tante_groupnorm_supported": ([c_i64, c_i32, c_i32, c_i32], c_i32),
     "tante_groupnorm_workspace_bytes": ([c_i64, c_i32, c_i32, c_i32], c_i64),
     "tante_groupnorm": ([c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp], c_i32),

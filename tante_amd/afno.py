@@ -14,16 +14,23 @@ Reference quirks kept on purpose (pinned by the g18 fixtures):
   * ComplexBlockLinear takes `bias=True` and creates no bias  (afno.py:22-44); the filter runs in fp32 also under autocast (l.105);
   * a freshly initialised filter is identically zero on unit-variance input: weights of scale 0.02 against a soft threshold of 0.01.
 
-Inference only (eval mode under no_grad).  Training, dropout / drop-path in train() and n_spatial_dims = 3 raise NotImplementedError;
-there is no CPU fallback."""
+Inference is the default: under grad a model whose parameters require one refuses (NotImplementedError), as it always did.  Training is
+opt-in through `model.set_trainable()`.  An opted-in model called under grad takes afno_train_forward: the same arithmetic as a graph
+of the training nodes of tante_amd/autograd.py (Im2colFn + LinearFn for the patch embedding, LayerNormAffineFn, LinearFn, ActFn,
+DeconvFn) with AfnoFilterFn for the filter, whose forward is the unchanged tante_afno_filter (bit-identical to inference) and whose
+backward is tante_afno_filter_bwd (csrc/afno_filter_bwd.hip).  The input receives a gradient too, so `rollout_model` back-propagates
+through its re-fed frames and `train.train_step` works with FlatAdamW as for the other trained models.  Dropout / drop-path in train()
+and n_spatial_dims = 3 raise NotImplementedError with or without the opt-in; there is no CPU fallback."""
 from __future__ import annotations
 
+import contextlib
 from functools import partial
 from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd import Function
 
 from . import _lib as L
 from . import kernels as K
@@ -82,6 +89,19 @@ def pack_twiddles(H: int, W: int) -> np.ndarray:
     return np.concatenate(planes)
 
 
+def pack_twiddles_bwd(H: int, W: int) -> np.ndarray:
+    """-> the float32 buffer of adjoint tables tante_afno_filter_bwd reads: the conjugate transposes T1^H (W, Lc), T2^H (H, Kc),
+    T3^H (Kc, W), T4^H (Lc, H) of the same float64 tables, rounded once and padded like pack_twiddles."""
+    planes = []
+    for t in twiddle_tables(H, W):
+        a = t.conj().T
+        p = np.zeros((2, _r(a.shape[0], 16), _r(a.shape[1], 4)), dtype=np.float32)
+        p[0, :a.shape[0], :a.shape[1]] = a.real
+        p[1, :a.shape[0], :a.shape[1]] = a.imag
+        planes.append(p.reshape(-1))
+    return np.concatenate(planes)
+
+
 def pack_block_weight(weight: torch.Tensor) -> torch.Tensor:
     """ComplexBlockLinear.weight (n_blocks, bs, bs, 2) -> the real-ified (n_blocks, 2 bsP, 2 bsP) fp32 matrices [[Wr, Wi], [-Wi, Wr]]
     ([Re | Im] . M = [Re Wr - Im Wi | Re Wi + Im Wr]), bsP = bs rounded up to 16, zero padded."""
@@ -113,11 +133,32 @@ def _twiddles(H: int, W: int, device) -> torch.Tensor:
     return t
 
 
+_TWIDDLES_BWD = {}
+
+
+def _twiddles_bwd(H: int, W: int, device) -> torch.Tensor:
+    key = (H, W, str(device))
+    t = _TWIDDLES_BWD.get(key)
+    if t is None:
+        host = pack_twiddles_bwd(H, W)
+        n = int(L.lib().tante_afno_twiddle_bwd_floats(H, W))
+        if n != host.size:
+            raise RuntimeError(f"adjoint twiddle tables for a {H} x {W} grid: {host.size} floats packed, the library expects {n}")
+        t = torch.from_numpy(host).to(device)
+        _TWIDDLES_BWD[key] = t
+    return t
+
+
 def afno_filter(x: torch.Tensor, residual: Optional[torch.Tensor], w1: torch.Tensor, w2: torch.Tensor, bs: int, lam: float,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """tante_afno_filter on x (B, H, W, C) fp32 channels-last: residual + swap_hw(filter(x)); w1 / w2 from pack_block_weight."""
+    return _filter_launch(x, residual, w1, w2, bs, lam, out)[0]
+
+
+def _filter_launch(x, residual, w1, w2, bs, lam, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (out, the call's workspace: P (B, Lc, H, 2, C) then G (B, W, Lc, 2, C), as bytes)."""
     K._dev(x, residual, w1, w2, out)
-    if x.dtype != torch.float32 or x.dim() != 4:
+    if x.dtype != torch.float32 or x.dim() != 4 or (residual is not None and residual.dtype != torch.float32):
         raise RuntimeError("the AFNO filter takes fp32 channels-last rows (B, H, W, C)")
     B, H, W, C_ = x.shape
     lib = L.lib()
@@ -130,7 +171,150 @@ def afno_filter(x: torch.Tensor, residual: Optional[torch.Tensor], w1: torch.Ten
     work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
     L.check(lib.tante_afno_filter(K._p(x), K._p(residual), B, H, W, C_, bs, K._p(_twiddles(H, W, x.device)), K._p(w1), K._p(w2), float(lam),
                                   K._p(out), K._p(work), nbytes, K._stream()), "tante_afno_filter")
-    return out
+    return out, work
+
+
+# ---- training: the filter as an autograd node -------------------------------------------------------------------------------------------
+_KEEP_SINK = [None]
+
+
+@contextlib.contextmanager
+def record_keep_masks(sink: list):
+    """Inside this scope every AfnoFilterFn.backward also asks the kernel for its threshold decisions [|Yp| > lambda] and appends them to
+    `sink` as a (B, Lc, Kc, 2, C) uint8 tensor, in the order the backward calls run (the reverse of the forward calls).  For tests that
+    restate the decisions; outside the scope nothing is allocated."""
+    prev, _KEEP_SINK[0] = _KEEP_SINK[0], sink
+    try:
+        yield sink
+    finally:
+        _KEEP_SINK[0] = prev
+
+
+_BLOCK_PACKS = {}     # (data_ptr, version, shape) -> (real-ified matrices, the weight), all of weight epoch _BLOCK_PACKS_EPOCH[0]
+_BLOCK_PACKS_EPOCH = [-1]
+
+
+def _packed_block_weight(w: torch.Tensor) -> torch.Tensor:
+    """pack_block_weight(w), shared by the BPTT calls of one step.  FlatAdamW updates the parameters through raw pointers, which moves
+    neither their address nor their version: it bumps attn_backbone's weight epoch instead, and a new epoch empties this cache, as it
+    invalidates every _PackCache."""
+    from .attn_backbone import _WEIGHT_EPOCH
+    if _BLOCK_PACKS_EPOCH[0] != _WEIGHT_EPOCH[0] or len(_BLOCK_PACKS) >= 256:
+        _BLOCK_PACKS.clear()
+        _BLOCK_PACKS_EPOCH[0] = _WEIGHT_EPOCH[0]
+    key = (w.data_ptr(), w._version, tuple(w.shape))
+    hit = _BLOCK_PACKS.get(key)
+    if hit is None:
+        hit = _BLOCK_PACKS[key] = (pack_block_weight(w), w)      # the weight is held so that its address stays its own
+    return hit[0]
+
+
+class AfnoFilterFn(Function):
+    """residual + swap_hw(filter(x)) on x (B, H, W, C) fp32 with ComplexBlockLinear weights weight1 / weight2 (n_blocks, bs, bs, 2).
+    Forward: the unchanged tante_afno_filter on a workspace the node owns; the P part of it (the transform along w) is what the backward
+    recomputes the spectrum from, so x itself is not saved.  (The entry point takes one workspace, P then G, so the G half -- as large
+    as P for a square grid -- stays allocated with it until the backward ran; a copy of P would free it at the price of a launch per
+    block.)  Backward: tante_afno_filter_bwd; the weight gradients go straight into the parameters' gradient slots where those exist
+    (FlatAdamW), the residual's gradient is dout itself."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight1, weight2, bs, lam):
+        x = x.contiguous()
+        residual = None if residual is None else residual.contiguous()
+        K._dev(weight1, weight2)
+        w1, w2 = _packed_block_weight(weight1), _packed_block_weight(weight2)
+        out, work = _filter_launch(x, residual, w1, w2, bs, lam)
+        ctx.save_for_backward(work, w1, w2)      # P is the head of the workspace
+        ctx.geo = (*x.shape, int(bs), float(lam))
+        ctx.has_res = residual is not None
+        ctx.params = (weight1, weight2)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from .autograd import _grad_slot
+        work, w1, w2 = ctx.saved_tensors
+        B, H, W, C_, bs, lam = ctx.geo
+        dout = dout.contiguous()
+        dev = dout.device
+        lib = L.lib()
+        dx = torch.empty_like(dout)
+        slots = [_grad_slot(p) if ctx.needs_input_grad[2 + i] else None for i, p in enumerate(ctx.params)]
+        into = slots[0] is not None and slots[1] is not None
+        dws = slots if into else [torch.empty(p.shape, dtype=torch.float32, device=dev) for p in ctx.params]
+        keep = None
+        if _KEEP_SINK[0] is not None:
+            Lc, Kc = kept_modes(H, W)
+            keep = torch.empty(B, Lc, Kc, 2, C_, dtype=torch.uint8, device=dev)
+            _KEEP_SINK[0].append(keep)
+        nbytes = int(lib.tante_afno_filter_bwd_workspace_bytes(B, H, W, C_, bs))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        L.check(lib.tante_afno_filter_bwd(K._p(dout), K._p(work), B, H, W, C_, bs, K._p(_twiddles(H, W, dev)), K._p(_twiddles_bwd(H, W, dev)),
+                                          K._p(w1), K._p(w2), lam, K._p(dx), K._p(dws[0]), K._p(dws[1]), int(into), K._p(keep), K._p(ws), nbytes,
+                                          K._stream()), "tante_afno_filter_bwd")
+        g1, g2 = (None, None) if into else (dws[0] if ctx.needs_input_grad[2] else None, dws[1] if ctx.needs_input_grad[3] else None)
+        return dx, (dout if ctx.has_res else None), g1, g2, None, None
+
+
+class PosRowsFn(Function):
+    """pos_embed (1, H', W', C) -> its rows repeated per sample (b H' W', C), the residual operand of the patch-embedding GEMM.  Backward:
+    the sum over the samples through tante_colsum, not a torch reduction (up to 64 samples one workgroup per 64 columns adds them in a
+    fixed order)."""
+
+    @staticmethod
+    def forward(ctx, pos, b):
+        ctx.param, ctx.b = pos, b
+        return pos.detach().expand(b, -1, -1, -1).reshape(-1, pos.shape[-1]).contiguous()
+
+    @staticmethod
+    def backward(ctx, d):
+        from .autograd import _grad_slot, colsum
+        d = d.contiguous()
+        pos, b = ctx.param, ctx.b
+        slot = _grad_slot(pos)
+        g = colsum(d, b, pos.numel(), 1, into=None if slot is None else slot.view(-1))
+        return (None if slot is not None else g.view(pos.shape)), None
+
+
+def _no_dropout(training: bool, *rates):
+    if training and any(r > 0.0 for r in rates):
+        raise NotImplementedError("drop_rate / drop_path_rate > 0 in train() is out of scope: dropout and stochastic depth are not part of "
+                                  "the training path (set_trainable); call .eval(), or build the model with both rates at 0")
+
+
+def block_train(blk: "Block", x: torch.Tensor, compute: int) -> torch.Tensor:
+    """Block.run as a graph of training nodes: x (B, H, W, C) fp32 -> block(x)."""
+    from .autograd import ActFn, LayerNormAffineFn, LinearFn
+    _no_dropout(blk.training, blk.drop_path_rate, blk.mlp.drop.p)
+    B, H, W, C_ = x.shape
+    M = B * H * W
+    adt = K.act_torch_dtype(compute)
+    f, m = blk.filter, blk.mlp
+    n1 = LayerNormAffineFn.apply(x, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps)
+    x1 = AfnoFilterFn.apply(n1, x if blk.double_skip else None, f.cmlp[0].weight, f.cmlp[2].weight, f.hidden_size // f.cmlp_diagonal_blocks,
+                            f.sparsity_threshold)
+    skip = x1 if blk.double_skip else x
+    n2 = LayerNormAffineFn.apply(x1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
+    h = ActFn.apply(LinearFn.apply(n2.view(M, C_), m.fc1.weight, m.fc1.bias, None, compute, adt), L.ACT_GELU_ERF, adt)
+    return LinearFn.apply(h, m.fc2.weight, m.fc2.bias, skip.reshape(M, C_), compute, torch.float32).view(B, H, W, C_)
+
+
+def afno_train_forward(model: "AFNO", x: torch.Tensor, compute: int) -> torch.Tensor:
+    """AFNO.forward with an autograd graph: x (b, t, c, h, w) -> (b, 1, c, h, w) fp32.  torch only re-lays out (the channels-last copy of
+    the input, parameter-sized weight views); every activation-sized operation is a HIP node."""
+    from .autograd import DeconvFn, Im2colFn, LinearFn
+    b, t, c, h, w = x.shape
+    p, C_ = model.patch_size, model.hidden_dim
+    Hp, Wp = h // p, w // p
+    pe, pd = model.patch_embed, model.patch_debed
+    img = x.to(torch.float32).reshape(b, t * c, h, w).permute(0, 2, 3, 1).contiguous()       # 'b t c h w -> b h w (t c)'
+    cols = Im2colFn.apply(img, b, t * c, h, w, p, p, 0, K.act_torch_dtype(compute))           # columns (kh, kw, channel)
+    w2d = pe.weight.permute(0, 2, 3, 1).reshape(C_, -1).contiguous()                          # the same order, a parameter-sized re-layout
+    y = LinearFn.apply(cols, w2d, pe.bias, PosRowsFn.apply(model.pos_embed, b), compute, torch.float32).view(b, Hp, Wp, C_)
+    for blk in model.blocks:
+        y = block_train(blk, y, compute)
+    out = DeconvFn.apply(y.view(b * Hp * Wp, C_), pd.weight, pd.bias, b, Hp, Wp, p, True, compute, torch.float32)
+    return out.unsqueeze(1)                                                                   # 'b c h w -> b 1 c h w'
 
 
 # ---- the reference's modules -------------------------------------------------------------------------------------------------------
@@ -179,6 +363,12 @@ class AFNO_ND(nn.Module):
         self.cmlp = nn.Sequential(ComplexBlockLinear(hidden_size, cmlp_diagonal_blocks=cmlp_diagonal_blocks), RealImagGELU(),
                                   ComplexBlockLinear(hidden_size, cmlp_diagonal_blocks=cmlp_diagonal_blocks))
         self._cache = _PackCache()
+        self._trainable = False
+
+    def set_trainable(self, flag: bool = True):
+        """Opt in to (or out of) training: under grad, forward then builds an autograd graph through AfnoFilterFn instead of refusing."""
+        self._trainable = bool(flag)
+        return self
 
     def _packed(self):
         ws = [self.cmlp[0].weight, self.cmlp[2].weight]
@@ -190,11 +380,15 @@ class AFNO_ND(nn.Module):
         return afno_filter(x, residual, w1, w2, self.hidden_size // self.cmlp_diagonal_blocks, self.sparsity_threshold)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """(b, H, W, C) -> (b, W, H, C), as the reference returns it (afno.py:103-117).  Inference only."""
-        _inference_only(self)
+        """(b, H, W, C) -> (b, W, H, C), as the reference returns it (afno.py:103-117).  Under grad only after set_trainable()."""
+        train = _wants_graph(self, x)
         if x.dim() != 4:
             raise NotImplementedError("the AFNO filter is two-dimensional here: n_spatial_dims = 3 is out of scope")
         _gpu(x)
+        if train:
+            y = AfnoFilterFn.apply(x.to(torch.float32), None, self.cmlp[0].weight, self.cmlp[2].weight,
+                                   self.hidden_size // self.cmlp_diagonal_blocks, self.sparsity_threshold)
+            return y.transpose(1, 2).to(x.dtype)
         return self.run(x.detach().to(torch.float32).contiguous(), None).transpose(1, 2).to(x.dtype)
 
 
@@ -214,6 +408,12 @@ class Block(nn.Module):
         self.double_skip = double_skip
         self.hidden_dim = hidden_dim
         self._cache = _PackCache()
+        self._trainable = False
+
+    def set_trainable(self, flag: bool = True):
+        self._trainable = bool(flag)
+        self.filter.set_trainable(flag)
+        return self
 
     def _packed(self, compute: int):
         n2, m = self.norm2, self.mlp
@@ -244,10 +444,14 @@ class Block(nn.Module):
         return y.view(B, H, W, C_)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        _inference_only(self)
+        train = _wants_graph(self, x)
+        if train:
+            _no_dropout(self.training, self.drop_path_rate, self.mlp.drop.p)
         if x.dim() != 4:
             raise NotImplementedError("the AFNO block is two-dimensional here: n_spatial_dims = 3 is out of scope")
         _gpu(x)
+        if train:
+            return block_train(self, x.to(torch.float32), resolve_compute(None))
         return self.run(x.detach().to(torch.float32).contiguous(), resolve_compute(None))
 
 
@@ -256,10 +460,18 @@ def _gpu(x: torch.Tensor):
         raise RuntimeError("tante_amd.AFNO runs on the GPU only (no CPU fallback); move the model and its input to cuda")
 
 
-def _inference_only(module: nn.Module):
-    if torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()):
-        raise NotImplementedError("tante_amd.AFNO is inference only: training is out of scope (the filter's backward is a kernel of its own "
-                                  "that is not built); call it in eval mode under torch.no_grad()")
+def _wants_graph(module: nn.Module, x: torch.Tensor) -> bool:
+    """True: build the autograd graph (opted in, grad enabled, something to differentiate).  A module that has not opted in refuses
+    under grad as it always did."""
+    if not torch.is_grad_enabled():
+        return False
+    params = any(p.requires_grad for p in module.parameters())
+    if module._trainable:
+        return params or x.requires_grad
+    if params:
+        raise NotImplementedError("tante_amd.AFNO is inference only unless set_trainable() was called: training is out of scope for this "
+                                  "model as it stands; opt in, or call it in eval mode under torch.no_grad()")
+    return False
 
 
 class AFNO(nn.Module):
@@ -300,6 +512,15 @@ class AFNO(nn.Module):
         self.compute: Optional[str] = None
         self._cache = _PackCache()
         self._pos = _PackCache()
+        self._trainable = False
+
+    def set_trainable(self, flag: bool = True):
+        """Opt in to (or out of) training: under grad, forward then takes afno_train_forward instead of refusing.  Not a constructor
+        argument and not part of the state_dict; returns self, like set_compute."""
+        self._trainable = bool(flag)
+        for blk in self.blocks:
+            blk.set_trainable(flag)
+        return self
 
     def _init_weights(self, m):
         if isinstance(m, nn.Linear):
@@ -350,12 +571,8 @@ class AFNO(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x (b, t, c, h, w) -> (b, 1, c, h, w)   (afno.py:270-278)."""
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("tante_amd.AFNO is inference only: training is out of scope (the filter's backward is a kernel of its "
-                                      "own that is not built); call it in eval mode under torch.no_grad()")
-        if self.training and (self.drop_rate > 0.0 or self.drop_path_rate > 0.0):
-            raise NotImplementedError("drop_rate / drop_path_rate > 0 in train() is out of scope: dropout and stochastic depth belong to the "
-                                      "training path, which is not built; call .eval()")
+        train = _wants_graph(self, x)
+        _no_dropout(self.training, self.drop_rate, self.drop_path_rate)
         if x.dim() != 5 or x.shape[1] * x.shape[2] != self.dim_in:
             raise ValueError(f"expected (B, {self.in_T}, {self.dim_out}, H, W), got {tuple(x.shape)}")
         _gpu(x)
@@ -364,6 +581,8 @@ class AFNO(nn.Module):
         if [h // p, w // p] != list(self.inner_size) or h % p or w % p:
             raise ValueError(f"input {h} x {w} does not give the {tuple(self.inner_size)} token grid of pos_embed at patch size {p}")
         compute = resolve_compute(self.compute)
+        if train:
+            return afno_train_forward(self, x, compute)
         x = x.detach().to(torch.float32).contiguous().view(b, t * c, h, w)       # 'b t c h w -> b (t c) h w' (the conv's channel order)
         y = self.forward_features(x, compute)
         _, pd = self._packed(compute)

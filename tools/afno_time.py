@@ -6,7 +6,12 @@ synchronised on both sides.  The two outputs must agree under the bf16 bar (1e-2
 
     python tools/afno_time.py [--steps 20] [--out profiles/afno_time.json]
 
-Writes both times, the spread of the regions, the launches per forward and the per-kernel split (torch.profiler, one forward)."""
+Writes both times, the spread of the regions, the launches per forward and the per-kernel split (torch.profiler, one forward).
+
+    python tools/afno_time.py --train [--train-rollout 1] [--out profiles/afno_train_time.json]
+
+times one train step instead (model.set_trainable(), train_step with FlatAdamW, bf16, the config's batch of 4): the same ramp and median
+of 7 regions, and the per-kernel device times of a warm step from one `rocprofv3 --kernel-trace --stats` run of a child process of its own."""
 import argparse
 import json
 import os
@@ -83,12 +88,110 @@ def kernel_split(step):
         return None, f"profiler unavailable: {type(e).__name__}: {e}"
 
 
+def train_setup(dev, rollout):
+    """The config's model, opted in to training, bf16 compute, with FlatAdamW and one fixed random batch of the config's shape."""
+    cfg = tante_amd.load_config(os.path.join(ROOT, "configs", "afno_am.yaml"))
+    wl = cfg["workload"]
+    torch.manual_seed(cfg["seed"])
+    md = tante_amd.TanteMetadata(n_fields=wl["n_fields"], spatial_resolution=tuple(wl["spatial_resolution"]))
+    m = tante_amd.build_model(cfg, md).to(dev).train().set_compute("bf16").set_trainable()
+    with torch.no_grad():       # a default-init filter is identically zero (see main)
+        for k, p in m.named_parameters():
+            if ".cmlp." in k:
+                p.mul_(2.0)
+    B, T, res, nf = wl["batch_size"], cfg["model"]["in_T"], wl["spatial_resolution"], wl["n_fields"]
+    batch = {"input": torch.randn(B, T, *res, nf, device=dev), "output": torch.randn(B, rollout, *res, nf, device=dev)}
+    fmt = tante_amd.DefaultChannelsFirstFormatter(md)
+    opt = tante_amd.FlatAdamW(m.parameters(), lr=1e-4)
+    return (lambda: tante_amd.train_step(m, opt, batch, fmt, rollout)), {"config": "configs/afno_am.yaml", "compute": "bf16", "batch": B, "in_T": T,
+                                                                          "resolution": res, "n_fields": nf, "n_steps_output": rollout}
+
+
+WARM_STEPS, PROFILED_STEPS = 5, 5
+
+
+def kernel_stats_under_rocprof(rollout):
+    """Per-kernel device time of one WARM train step: `rocprofv3 --kernel-trace --stats` around a fresh child process that runs
+    WARM_STEPS + PROFILED_STEPS train steps and nothing else.  The trace is cut into steps at the optimiser's kernel (the last launch of a
+    step) and only the last PROFILED_STEPS of them are counted, so first-step work (weight packing, table uploads, allocator growth) is
+    left out; -> ([{name, calls_per_step, us_per_step}], device us per step) or a string saying why there is none."""
+    import csv
+    import glob
+    import subprocess
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--", sys.executable, os.path.abspath(__file__), "--train",
+               "--profiled-child", "--train-rollout", str(rollout)]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+        except (OSError, subprocess.TimeoutExpired) as e:
+            return f"rocprofv3 run failed: {type(e).__name__}: {e}"
+        files = glob.glob(os.path.join(tmp, "**", "*kernel_trace.csv"), recursive=True)
+        if r.returncode != 0 or not files:
+            return f"rocprofv3 run left no kernel trace (exit {r.returncode}): {r.stderr[-300:]}"
+        rows = sorted(csv.DictReader(open(files[0])), key=lambda q: int(q["Start_Timestamp"]))
+    steps, cur = [], []
+    for q in rows:
+        cur.append((q["Kernel_Name"], int(q["End_Timestamp"]) - int(q["Start_Timestamp"])))
+        if "adamw_kernel" in q["Kernel_Name"]:
+            steps.append(cur)
+            cur = []
+    if len(steps) != WARM_STEPS + PROFILED_STEPS:
+        return f"the trace holds {len(steps)} optimiser launches, {WARM_STEPS + PROFILED_STEPS} steps were run"
+    agg = {}
+    for st in steps[-PROFILED_STEPS:]:
+        for name, ns in st:
+            e = agg.setdefault(name, [0, 0])
+            e[0] += 1
+            e[1] += ns
+    kernels = sorted(agg.items(), key=lambda kv: -kv[1][1])
+    total = round(sum(v[1] for v in agg.values()) / PROFILED_STEPS / 1e3, 1)
+    return [{"name": k[:110], "calls_per_step": round(v[0] / PROFILED_STEPS, 2), "us_per_step": round(v[1] / PROFILED_STEPS / 1e3, 1)}
+            for k, v in kernels[:24]], total
+
+
+def train_main(args):
+    dev = torch.device("cuda:0")
+    if args.profiled_child:
+        step, _ = train_setup(dev, args.train_rollout)
+        for _ in range(WARM_STEPS + PROFILED_STEPS):
+            step()
+        torch.cuda.synchronize()
+        return
+    kernels = kernel_stats_under_rocprof(args.train_rollout)      # before this process opens the GPU
+    step, workload = train_setup(dev, args.train_rollout)
+    losses = [float(step()) for _ in range(3)]
+    if not all(v == v and abs(v) != float("inf") for v in losses):
+        raise SystemExit(f"the train step's loss is not finite ({losses}): nothing timed")
+    t = timed(step, args.steps)
+    kernels, total = kernels if isinstance(kernels, tuple) else (kernels, None)
+    result = {"workload": workload, "device": torch.cuda.get_device_name(0), "train_step": t, "first_losses": losses,
+              "kernels_rocprofv3": kernels, "kernel_us_per_step_all": total,
+              "note": "a first measurement of this path, not a target.  kernels_rocprofv3: the largest kernels of the last "
+                      f"{PROFILED_STEPS} of {WARM_STEPS + PROFILED_STEPS} steps of a profiled child process (warm steps only); "
+                      "kernel_us_per_step_all: the device time of ALL kernels of such a step, measured under the profiler, next to the "
+                      "unprofiled wall-clock median in train_step"}
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "afno_train_time.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(result, f, indent=1)
+    print(json.dumps({"train_step_ms": t["ms_median"], "kernel_us_per_step_all": total}))
+
+
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "afno_time.json")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 4])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "afno_time.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--train", action="store_true", help="time one train step (set_trainable, FlatAdamW, bf16) -> profiles/afno_train_time.json")
+    ap.add_argument("--train-rollout", type=int, default=1, help="--train: frames predicted (and back-propagated through) per step")
+    ap.add_argument("--profiled-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.train:
+        return train_main(args)
     dev = torch.device("cuda:0")
     cfg = tante_amd.load_config(os.path.join(ROOT, "configs", "afno_am.yaml"))
     wl = cfg["workload"]
