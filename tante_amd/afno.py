@@ -36,13 +36,10 @@ from . import _lib as L
 from . import kernels as K
 from . import stages as S
 from .attn_backbone import _PackCache, resolve_compute
+from .dft_tables import cis, device_tables, pack_tables
 
 MAX_GRID = 64     # token-grid points per axis the filter kernels serve
 MAX_BLOCK = 64    # channels per diagonal block
-
-
-def _r(n: int, m: int) -> int:
-    return (n + m - 1) // m * m
 
 
 # ---- host side of tante_afno_filter: the predicate's mirror, the twiddle tables, the real-ified weights ---------------------------------
@@ -60,46 +57,24 @@ def kept_modes(H: int, W: int) -> Tuple[int, int]:
     return min(H, W), min(H // 2 + 1, W // 2 + 1)
 
 
-def _cis(num: np.ndarray, n: int, sign: int) -> np.ndarray:
-    """e^{sign 2 pi i num / n} in float64 with the angle reduced in integers (so the entries that are real / imaginary are exactly so)."""
-    m = np.mod(num, n).astype(np.float64)
-    z = np.cos(2.0 * np.pi * m / n) + sign * 1j * np.sin(2.0 * np.pi * m / n)
-    z.real[np.abs(z.real) < 1e-15] = 0.0
-    z.imag[np.abs(z.imag) < 1e-15] = 0.0
-    return z
-
-
 def twiddle_tables(H: int, W: int) -> List[np.ndarray]:
     """The four complex128 tables of tante_afno_filter (include/tante_hip.h), unpadded: T1 (Lc, W), T2 (Kc, H), T3 (W, Kc), T4 (H, Lc)."""
     Lc, Kc = kept_modes(H, W)
     l, k, w, h = np.arange(Lc), np.arange(Kc), np.arange(W), np.arange(H)
     ck = np.where((k == 0) | ((W % 2 == 0) & (k == W // 2)), 1.0, 2.0)
-    return [_cis(np.outer(l, w), W, -1) / np.sqrt(W), _cis(np.outer(k, h), H, -1) / np.sqrt(H),
-            _cis(np.outer(w, k), W, +1) * ck[None, :] / np.sqrt(W), _cis(np.outer(h, l), H, +1) / np.sqrt(H)]
+    return [cis(np.outer(l, w), W, -1) / np.sqrt(W), cis(np.outer(k, h), H, -1) / np.sqrt(H),
+            cis(np.outer(w, k), W, +1) * ck[None, :] / np.sqrt(W), cis(np.outer(h, l), H, +1) / np.sqrt(H)]
 
 
 def pack_twiddles(H: int, W: int) -> np.ndarray:
     """-> the float32 buffer tante_afno_filter reads: per table a real then an imaginary plane, rows padded to 16, columns to 4."""
-    planes = []
-    for t in twiddle_tables(H, W):
-        p = np.zeros((2, _r(t.shape[0], 16), _r(t.shape[1], 4)), dtype=np.float32)
-        p[0, :t.shape[0], :t.shape[1]] = t.real
-        p[1, :t.shape[0], :t.shape[1]] = t.imag
-        planes.append(p.reshape(-1))
-    return np.concatenate(planes)
+    return pack_tables(twiddle_tables(H, W))
 
 
 def pack_twiddles_bwd(H: int, W: int) -> np.ndarray:
     """-> the float32 buffer of adjoint tables tante_afno_filter_bwd reads: the conjugate transposes T1^H (W, Lc), T2^H (H, Kc),
     T3^H (Kc, W), T4^H (Lc, H) of the same float64 tables, rounded once and padded like pack_twiddles."""
-    planes = []
-    for t in twiddle_tables(H, W):
-        a = t.conj().T
-        p = np.zeros((2, _r(a.shape[0], 16), _r(a.shape[1], 4)), dtype=np.float32)
-        p[0, :a.shape[0], :a.shape[1]] = a.real
-        p[1, :a.shape[0], :a.shape[1]] = a.imag
-        planes.append(p.reshape(-1))
-    return np.concatenate(planes)
+    return pack_tables([t.conj().T for t in twiddle_tables(H, W)])
 
 
 def pack_block_weight(weight: torch.Tensor) -> torch.Tensor:
@@ -107,7 +82,7 @@ def pack_block_weight(weight: torch.Tensor) -> torch.Tensor:
     ([Re | Im] . M = [Re Wr - Im Wi | Re Wi + Im Wr]), bsP = bs rounded up to 16, zero padded."""
     w = weight.detach().to(torch.float32)
     nb, bs = w.shape[0], w.shape[1]
-    bp = _r(bs, 16)
+    bp = (bs + 15) // 16 * 16
     m = torch.zeros(nb, 2 * bp, 2 * bp, dtype=torch.float32, device=w.device)
     wr, wi = w[..., 0], w[..., 1]
     m[:, :bs, :bs] = wr
@@ -117,36 +92,14 @@ def pack_block_weight(weight: torch.Tensor) -> torch.Tensor:
     return m.contiguous()
 
 
-_TWIDDLES = {}     # (H, W, device) -> packed tables on the device: weight independent, built once per shape
-
-
 def _twiddles(H: int, W: int, device) -> torch.Tensor:
-    key = (H, W, str(device))
-    t = _TWIDDLES.get(key)
-    if t is None:
-        host = pack_twiddles(H, W)
-        n = int(L.lib().tante_afno_twiddle_floats(H, W))
-        if n != host.size:
-            raise RuntimeError(f"twiddle tables for a {H} x {W} grid: {host.size} floats packed, the library expects {n}")
-        t = torch.from_numpy(host).to(device)
-        _TWIDDLES[key] = t
-    return t
-
-
-_TWIDDLES_BWD = {}
+    return device_tables(("afno", H, W), lambda: pack_twiddles(H, W), L.lib().tante_afno_twiddle_floats(H, W),
+                         f"twiddle tables for a {H} x {W} grid", device)
 
 
 def _twiddles_bwd(H: int, W: int, device) -> torch.Tensor:
-    key = (H, W, str(device))
-    t = _TWIDDLES_BWD.get(key)
-    if t is None:
-        host = pack_twiddles_bwd(H, W)
-        n = int(L.lib().tante_afno_twiddle_bwd_floats(H, W))
-        if n != host.size:
-            raise RuntimeError(f"adjoint twiddle tables for a {H} x {W} grid: {host.size} floats packed, the library expects {n}")
-        t = torch.from_numpy(host).to(device)
-        _TWIDDLES_BWD[key] = t
-    return t
+    return device_tables(("afno_bwd", H, W), lambda: pack_twiddles_bwd(H, W), L.lib().tante_afno_twiddle_bwd_floats(H, W),
+                         f"adjoint twiddle tables for a {H} x {W} grid", device)
 
 
 def afno_filter(x: torch.Tensor, residual: Optional[torch.Tensor], w1: torch.Tensor, w2: torch.Tensor, bs: int, lam: float,
@@ -436,12 +389,7 @@ class Block(nn.Module):
             skip = x
         h = torch.empty(M, pk["fc1_ln2"].N, dtype=K.act_torch_dtype(compute), device=x.device)
         K.linear(x1.view(M, C_), pk["fc1_ln2"], h, M=M, act=L.ACT_GELU_ERF, ln=True, ln_eps=self.norm2.eps)
-        y = torch.empty(M, C_, dtype=torch.float32, device=x.device)
-        k0, Kt = 0, h.shape[1]
-        for i, pw in enumerate(pk["fc2"]):           # K-chunks accumulate through the residual operand; the first one carries the skip
-            K.linear(h, pw, y, M=M, a_n0=M, a_s0=Kt, a_off=k0, residual=skip.view(M, C_) if i == 0 else y)
-            k0 += pw.K
-        return y.view(B, H, W, C_)
+        return S.linear_chunks(h, pk["fc2"], residual=skip.view(M, C_)).view(B, H, W, C_)       # the skip rides the residual operand
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         train = _wants_graph(self, x)
@@ -559,12 +507,7 @@ class AFNO(nn.Module):
         cols = K.im2col(x, True, b, cin, h, w, p, p, p, p, 0, 0, 0, K.act_torch_dtype(compute))
         # x + pos_embed: the embedding's rows, repeated per sample, are the residual the first K-chunk accumulates onto
         pos = self._pos.get(b, [self.pos_embed], lambda: self.pos_embed.detach().expand(b, -1, -1, -1).reshape(M, C_).contiguous())
-        y = torch.empty(M, C_, dtype=torch.float32, device=x.device)
-        k0, Kt = 0, cols.shape[1]
-        for i, pw in enumerate(chunks):
-            K.linear(cols, pw, y, M=M, a_n0=M, a_s0=Kt, a_off=k0, residual=pos if i == 0 else y)
-            k0 += pw.K
-        y = y.view(b, Hp, Wp, C_)
+        y = S.linear_chunks(cols, chunks, residual=pos).view(b, Hp, Wp, C_)
         for blk in self.blocks:
             y = blk.run(y, compute)
         return y

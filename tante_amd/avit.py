@@ -211,27 +211,6 @@ def fold_stem(bag_weight: torch.Tensor, bag_bias: torch.Tensor, conv_weight: tor
     return w.reshape(w.shape[0], -1).float().contiguous(), b.float().contiguous()
 
 
-def _conv_rows(w: torch.Tensor) -> torch.Tensor:
-    """Conv2d weight (Cout, Cin, kh, kw) -> (Cout, kh kw Cin): the channels-last im2col column order."""
-    return w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
-
-
-def _gemm(a: torch.Tensor, chunks, out_dtype: torch.dtype = torch.float32, act: int = L.ACT_NONE, residual: Optional[torch.Tensor] = None,
-          out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """act(a @ W^T + b), or a @ W^T + b + residual into fp32 `out` (which may be `residual`): K-chunks accumulate through the residual
-    operand, the first one carries the skip."""
-    if residual is None:
-        return S.linear_chunks(a, chunks, out_dtype, act)
-    M, Kt = a.shape
-    if out is None:
-        out = torch.empty(M, chunks[0].N, dtype=torch.float32, device=a.device)
-    k0 = 0
-    for i, pw in enumerate(chunks):
-        K.linear(a, pw, out, M=M, a_n0=M, a_s0=Kt, a_off=k0, residual=residual if i == 0 else out)
-        k0 += pw.K
-    return out
-
-
 def _deconv2(rows: torch.Tensor, dec, n: int, Hi: int, Wi: int, Cout: int) -> torch.Tensor:
     """A 2 x 2 / 2 transposed convolution without bias on channels-last rows -> (n, 2 Hi, 2 Wi, Cout) fp32."""
     if isinstance(dec, K.PackedWeight):
@@ -389,7 +368,7 @@ class hMLP_stem(nn.Module):
     def _packed(self, compute: int):
         c0, c3, c6 = self.in_proj[0], self.in_proj[3], self.in_proj[6]
         return self._cache.get(compute, [c0.weight, c3.weight, c6.weight], lambda: tuple(
-            S.pack_linear_chunks(_conv_rows(c.weight), None, compute) for c in (c0, c3, c6)))
+            S.pack_linear_chunks(S.conv_rows(c.weight), None, compute) for c in (c0, c3, c6)))
 
     def run(self, x: torch.Tensor, compute: int, first=None) -> torch.Tensor:
         """x (n, H, W, Cin) fp32 channels-last -> rows (n H/16 W/16, embed_dim) fp32; `first`: packed chunks that replace in_proj[0]."""
@@ -528,12 +507,12 @@ class AxialAttentionBlock(nn.Module):
         inp, outp, fc1, fc2 = self._packed(compute)
         x3 = x.view(n, Hp * Wp, C_)
         n1 = self.norm1.run(x3, adt)
-        qkv = _gemm(n1.view(M, C_), inp)
+        qkv = S.linear_chunks(n1.view(M, C_), inp)
         att = axial_attention(qkv, n, self.num_heads, Hp, Wp, self.qnorm, self.knorm)
         n2 = self.norm2.run(att.view(n, Hp * Wp, C_), adt)
-        _gemm(n2.view(M, C_), outp, residual=x, out=x)                         # gamma_att folded; the skip rides the residual operand
-        h = _gemm(x, fc1, mdt, L.ACT_GELU_ERF)
-        y = _gemm(h, fc2)
+        S.linear_chunks(n2.view(M, C_), outp, residual=x, out=x)               # gamma_att folded; the skip rides the residual operand
+        h = S.linear_chunks(x, fc1, mdt, L.ACT_GELU_ERF)
+        y = S.linear_chunks(h, fc2)
         if self.gamma_mlp is None:
             instnorm(y.view(n, Hp * Wp, C_), L.INSTNORM_RMS, self.mlp_norm.weight.detach(), None, self.mlp_norm.eps, residual=x3,
                      gamma=torch.ones(C_, dtype=torch.float32, device=x.device), out=x3)
@@ -599,10 +578,10 @@ class AttentionBlock(nn.Module):
         adt = K.act_torch_dtype(_site(compute, "attn"))
         inp, outp = self._packed(compute)
         n1 = instnorm(x.view(T * B, HW, C_), L.INSTNORM_INSTANCE, self.norm1.weight.detach(), self.norm1.bias.detach(), self.norm1.eps, adt)
-        qkv = _gemm(n1.view(M, C_), inp)
+        qkv = S.linear_chunks(n1.view(M, C_), inp)
         att = time_attention(qkv, B * HW, T, self.num_heads, self.qnorm, self.knorm, self._bias(T, x.device))
         n2 = instnorm(att.view(T * B, HW, C_), L.INSTNORM_INSTANCE, self.norm2.weight.detach(), self.norm2.bias.detach(), self.norm2.eps, adt)
-        return _gemm(n2.view(M, C_), outp, residual=x, out=x)                  # gamma folded; the skip rides the residual operand
+        return S.linear_chunks(n2.view(M, C_), outp, residual=x, out=x)        # gamma folded; the skip rides the residual operand
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(T, B, C, H, W) -> (T, B, C, H, W)  (avit.py:308-331).  Inference only."""

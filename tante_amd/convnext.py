@@ -40,7 +40,6 @@ from . import kernels as K
 from . import options as _O
 from . import stages as S
 from .attn_backbone import _PackCache, resolve_compute
-from .avit import _conv_rows, _gemm
 
 FUSED_MAX_C = 256      # channels tante_convnext_block serves
 FUSED_DEFAULT_MAX_C = 32   # ... and the widest block it is the DEFAULT for: on the config's pyramid (token count x C^2 constant) the one launch
@@ -301,7 +300,7 @@ class Downsample(_Resample):
     def _packed(self, compute: int):
         norm, conv = self.block[0], self.block[1]
         return self._cache.get(compute, [norm.weight, conv.weight, conv.bias], lambda: S.pack_linear_chunks(
-            _conv_rows(fold_cf_norm(conv.weight, norm.weight)), conv.bias.detach(), compute))
+            S.conv_rows(fold_cf_norm(conv.weight, norm.weight)), conv.bias.detach(), compute))
 
     def run(self, x: torch.Tensor, compute: int) -> torch.Tensor:
         """x (n, H, W, C) fp32 -> (n, H / 2, W / 2, C') fp32."""
@@ -369,8 +368,8 @@ class Block(nn.Module):
         dw_w, dw_b, fc1, fc2 = self._packed_modular(compute)
         adt = K.act_torch_dtype(compute)
         a = dwconv_ln(x, dw_w, dw_b, self.norm.eps, None, None, adt)
-        h = _gemm(a, fc1, adt, L.ACT_GELU_ERF)
-        _gemm(h, fc2, residual=x.view(n * H * W, C_), out=out.view(n * H * W, C_))          # gamma folded; the skip rides the residual operand
+        h = S.linear_chunks(a, fc1, adt, L.ACT_GELU_ERF)
+        S.linear_chunks(h, fc2, residual=x.view(n * H * W, C_), out=out.view(n * H * W, C_))  # gamma folded; the skip rides the residual operand
         return out
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -415,8 +414,8 @@ class Stage(nn.Module):
         if tuple(skip.shape) != tuple(x.shape):
             raise ValueError(f"the skip must have the stream's shape {tuple(x.shape)}, got {tuple(skip.shape)}")
         wx, ws = self._packed_skip(compute)
-        out = _gemm(x.view(n * H * W, C_), wx)
-        _gemm(skip.view(n * H * W, C_), ws, residual=out, out=out)
+        out = S.linear_chunks(x.view(n * H * W, C_), wx)
+        S.linear_chunks(skip.view(n * H * W, C_), ws, residual=out, out=out)
         return out.view(n, H, W, C_)
 
     def run(self, x: torch.Tensor, compute: int, skip: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -15,9 +15,11 @@
 //                                  G[w, l] = sum_k  T3[w, k] Y[k]                          T3 = c_k e^{+2 pi i k w / W} / sqrt(W)
 //   launch 3 (b, w, 64 channels)  out[h, w] = Re sum_l T4[h, l] G[w, l] + residual[h, w]   T4 = e^{+2 pi i l h / H} / sqrt(H)
 //
+// Launch 1 is dft_r2c_rows_kernel and launch 3 dft_c2r_rows_kernel<AfnoInvEpilogue> of dft_rows.hip.h, which also holds the table layout and
+// the table product; launch 2, afno_mix_kernel, is this file's.
+//
 // c_k = 1 for k = 0 and for k = W/2 (W even), 2 otherwise: the complex-to-real weights.  The imaginary parts of those two entries drop
-// out by themselves, their table entries being real.  The tables come from the host (float64, rounded once, zero padded to whole
-// 16-row / 4-column fragments), so no kernel checks a table bound; data tiles are zero filled to the same padding in LDS.
+// out by themselves, their table entries being real.
 //
 // Every product is v_mfma_f32_16x16x4_f32: exact fp32 products and fp32 accumulation in BOTH compute modes, as the reference keeps the
 // filter in fp32 under autocast.  A operand lane (i = l & 15, k = l >> 4), B operand lane (k = l >> 4, j = l & 15), result register r =
@@ -27,40 +29,6 @@
 namespace {
 
 __device__ __forceinline__ float softshrink(float v, float lam) { return v > lam ? v - lam : (v < -lam ? v + lam : 0.0f); }
-
-// ---- launch 1: the forward transform along w -----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(AF_THREADS) void afno_fwd_w_kernel(const float* __restrict__ x, const float* __restrict__ Tr,
-                                                                const float* __restrict__ Ti, int ldt, float* __restrict__ P, int H, int W, int C,
-                                                                int Lc) {
-  __shared__ float xs[AF_MAX * AF_LD1];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, kk = lane >> 4;
-  const long b = blockIdx.x / H;
-  const int h = blockIdx.x % H;
-  const int c0 = blockIdx.y * AF_CH;
-  const int nc = (C - c0) < AF_CH ? (C - c0) : AF_CH;
-  const int Wp = (W + 3) & ~3;
-  const float* xrow = x + ((b * H + h) * W) * (long)C + c0;
-  for (int idx = tid; idx < Wp * AF_CH; idx += AF_THREADS) {
-    const int w = idx / AF_CH, c = idx % AF_CH;
-    xs[w * AF_LD1 + c] = (w < W && c < nc) ? xrow[(long)w * C + c] : 0.0f;
-  }
-  __syncthreads();
-  const int MT = (Lc + 15) >> 4, NT = (nc + 15) >> 4;
-  for (int t = wave; t < MT * NT; t += AF_THREADS / 64) {
-    const int mt = t / NT, nt = t % NT;
-    f32x4 dr = {0.f, 0.f, 0.f, 0.f}, di = {0.f, 0.f, 0.f, 0.f};
-    table_tile<false, true>(Tr, Ti, ldt, mt * 16, xs, AF_LD1, nt * 16, 0, Wp, dr, di);
-    const int c = nt * 16 + i;
-    for (int r = 0; r < 4; ++r) {
-      const int l = mt * 16 + 4 * kk + r;
-      if (l < Lc && c < nc) {
-        float* p = P + (((b * Lc + l) * H + h) * 2) * (long)C + c0 + c;
-        p[0] = dr[r];
-        p[C] = di[r];
-      }
-    }
-  }
-}
 
 // ---- launch 2: transform along h, block MLP, soft threshold, inverse along k ---------------------------------------------------------
 __global__ __launch_bounds__(AF_THREADS) void afno_mix_kernel(const float* __restrict__ P, const float* __restrict__ T2r, const float* __restrict__ T2i,
@@ -135,38 +103,11 @@ __global__ __launch_bounds__(AF_THREADS) void afno_mix_kernel(const float* __res
   }
 }
 
-// ---- launch 3: the inverse along l, the axis swap and the skip -------------------------------------------------------------------------
-__global__ __launch_bounds__(AF_THREADS) void afno_inv_h_kernel(const float* __restrict__ G, const float* __restrict__ Tr, const float* __restrict__ Ti,
-                                                                int ldt, const float* __restrict__ resid, float* __restrict__ out, int H, int W, int C,
-                                                                int Lc) {
-  __shared__ float gs[AF_MAX * AF_LD];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, kk = lane >> 4;
-  const long b = blockIdx.x / W;
-  const int w = blockIdx.x % W;
-  const int c0 = blockIdx.y * AF_CH;
-  const int nc = (C - c0) < AF_CH ? (C - c0) : AF_CH;
-  const int Lp = (Lc + 3) & ~3;
-  const float* Gw = G + ((b * W + w) * Lc) * 2 * (long)C + c0;
-  for (int idx = tid; idx < Lp * 2 * AF_CH; idx += AF_THREADS) {
-    const int l = idx / (2 * AF_CH), j = idx % (2 * AF_CH), ri = j / AF_CH, c = j % AF_CH;
-    gs[l * AF_LD + j] = (l < Lc && c < nc) ? Gw[((long)l * 2 + ri) * C + c] : 0.0f;
-  }
-  __syncthreads();
-  const int MT = (H + 15) >> 4, NT = (nc + 15) >> 4;
-  for (int t = wave; t < MT * NT; t += AF_THREADS / 64) {
-    const int mt = t / NT, nt = t % NT;
-    f32x4 dr = {0.f, 0.f, 0.f, 0.f}, di = {0.f, 0.f, 0.f, 0.f};
-    table_tile<true, false>(Tr, Ti, ldt, mt * 16, gs, AF_LD, nt * 16, AF_CH, Lp, dr, di);
-    const int c = nt * 16 + i;
-    for (int r = 0; r < 4; ++r) {
-      const int h = mt * 16 + 4 * kk + r;
-      if (h < H && c < nc) {
-        const long o = ((b * H + h) * W + w) * (long)C + c0 + c;
-        out[o] = dr[r] + (resid ? resid[o] : 0.0f);
-      }
-    }
-  }
-}
+// ---- launch 3's store: + residual, and + 0.0f without one (which is not the bare value where that is -0) --------------------------------
+struct AfnoInvEpilogue {
+  const float* resid;
+  __device__ float operator()(float v, long o) const { return v + (resid ? resid[o] : 0.0f); }
+};
 
 }  // namespace
 
@@ -195,15 +136,18 @@ extern "C" int tante_afno_filter(const float* x, const float* residual, int64_t 
   float* P = (float*)work;
   float* G = P + 2 * B * t.Lc * (int64_t)H * C;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned cch = (unsigned)((C + AF_CH - 1) / AF_CH);
-  hipLaunchKernelGGL(afno_fwd_w_kernel, dim3((unsigned)(B * H), cch), dim3(AF_THREADS), 0, s, x, twiddles + t.re[0], twiddles + t.im[0], t.Kp[0], P, H, W, C,
-                     t.Lc);
+  const unsigned cch = (unsigned)((C + DFT_CH - 1) / DFT_CH);
+  const long C1 = C, C2 = 2l * C;
+  const DftRows fwd_w = {H * W * C1, W * C1, C1, t.Lc * H * C2, C2, H * C2, H};       // x rows (b, h) -> P[b][l][h]
+  const DftRows inv_h = {W * t.Lc * C2, t.Lc * C2, C2, H * W * C1, C1, W * C1, W};    // G[b][w] -> the columns (b, w) of out
+  hipLaunchKernelGGL(dft_r2c_rows_kernel, dim3((unsigned)(B * H), cch), dim3(DFT_THREADS), 0, s, x, twiddles + t.re[0], twiddles + t.im[0], t.Kp[0], P,
+                     fwd_w, W, t.Lc, C);
   TANTE_CHECK_LAUNCH();
   hipLaunchKernelGGL(afno_mix_kernel, dim3((unsigned)t.Lc, (unsigned)(C / bs), (unsigned)B), dim3(AF_THREADS), 0, s, (const float*)P, twiddles + t.re[1],
                      twiddles + t.im[1], t.Kp[1], twiddles + t.re[2], twiddles + t.im[2], t.Kp[2], w1, w2, lambda, G, H, W, C, bs, t.Lc, t.Kc);
   TANTE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(afno_inv_h_kernel, dim3((unsigned)(B * W), cch), dim3(AF_THREADS), 0, s, (const float*)G, twiddles + t.re[3], twiddles + t.im[3], t.Kp[3],
-                     residual, out, H, W, C, t.Lc);
+  hipLaunchKernelGGL(dft_c2r_rows_kernel<AfnoInvEpilogue>, dim3((unsigned)(B * W), cch), dim3(DFT_THREADS), 0, s, (const float*)G, twiddles + t.re[3],
+                     twiddles + t.im[3], t.Kp[3], out, inv_h, t.Lc, H, C, AfnoInvEpilogue{residual});
   TANTE_CHECK_LAUNCH();
   return 0;
 }

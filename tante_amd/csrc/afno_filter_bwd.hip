@@ -17,6 +17,9 @@
 //   launch B3 (b, h, 64 channels)   dx[h, w] = Re sum_l conj(T1[l, w]) dP[l, h]                      complex in, real out
 //   reduce                          dw[e]    = sum over (b, l) of the partials, in a fixed order (eight interleaved running sums)
 //
+// B1 is dft_r2c_rows_kernel reading the strided columns of dout, B3 dft_c2r_rows_kernel<AfnoBwdEpilogue> (dft_rows.hip.h); B2,
+// afno_bwd_mix_kernel, and the reduce are this file's.
+//
 // The weight gradients are summed over the B Lc workgroups of a channel block without atomics: every workgroup of B2 stores its folded
 // partial to its own slot of the workspace and the reduce adds the slots in a fixed order, so two runs give the same bits.
 //
@@ -39,40 +42,6 @@ constexpr int AFB_LDS_MAX = 4 * AF_ROWS_B * AF_LD * (int)sizeof(float);     // 1
 inline int afb_rows_r(int H, int W, int Kc) {
   const int a = 2 * r16(Kc), b = r4(H > W ? H : W);
   return a > b ? a : b;
-}
-
-// ---- launch B1: the adjoint of the inverse along l -----------------------------------------------------------------------------------
-__global__ __launch_bounds__(AF_THREADS) void afno_bwd_h_kernel(const float* __restrict__ dout, const float* __restrict__ Tr,
-                                                                const float* __restrict__ Ti, int ldt, float* __restrict__ dG, int H, int W, int C,
-                                                                int Lc) {
-  __shared__ float ds[AF_MAX * AF_LD1];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, kk = lane >> 4;
-  const long b = blockIdx.x / W;
-  const int w = blockIdx.x % W;
-  const int c0 = blockIdx.y * AF_CH;
-  const int nc = (C - c0) < AF_CH ? (C - c0) : AF_CH;
-  const int Hp = (H + 3) & ~3;
-  const float* col = dout + ((b * H) * W + w) * (long)C + c0;       // the strided column w of dout: row h at + h W C
-  for (int idx = tid; idx < Hp * AF_CH; idx += AF_THREADS) {
-    const int h = idx / AF_CH, c = idx % AF_CH;
-    ds[h * AF_LD1 + c] = (h < H && c < nc) ? col[(long)h * W * C + c] : 0.0f;
-  }
-  __syncthreads();
-  const int MT = (Lc + 15) >> 4, NT = (nc + 15) >> 4;
-  for (int t = wave; t < MT * NT; t += AF_THREADS / 64) {
-    const int mt = t / NT, nt = t % NT;
-    f32x4 dr = {0.f, 0.f, 0.f, 0.f}, di = {0.f, 0.f, 0.f, 0.f};
-    table_tile<false, true>(Tr, Ti, ldt, mt * 16, ds, AF_LD1, nt * 16, 0, Hp, dr, di);
-    const int c = nt * 16 + i;
-    for (int r = 0; r < 4; ++r) {
-      const int l = mt * 16 + 4 * kk + r;
-      if (l < Lc && c < nc) {
-        float* p = dG + (((b * W + w) * Lc + l) * 2) * (long)C + c0 + c;
-        p[0] = dr[r];
-        p[C] = di[r];
-      }
-    }
-  }
 }
 
 // (dWr + i dWi)[i][j] of one channel block from the real-ified product A^T B over `rows` rows, A = [Ar | Ai], B = [Br | Bi] in LDS:
@@ -246,33 +215,10 @@ __global__ __launch_bounds__(AF_THREADS) void afno_bwd_mix_kernel(
   }
 }
 
-// ---- launch B3: the adjoint of the forward transform along w -------------------------------------------------------------------------
-__global__ __launch_bounds__(AF_THREADS) void afno_bwd_w_kernel(const float* __restrict__ dP, const float* __restrict__ Tr, const float* __restrict__ Ti,
-                                                                int ldt, float* __restrict__ dx, int H, int W, int C, int Lc) {
-  __shared__ float gs[AF_MAX * AF_LD];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, kk = lane >> 4;
-  const long b = blockIdx.x / H;
-  const int h = blockIdx.x % H;
-  const int c0 = blockIdx.y * AF_CH;
-  const int nc = (C - c0) < AF_CH ? (C - c0) : AF_CH;
-  const int Lp = (Lc + 3) & ~3;
-  for (int idx = tid; idx < Lp * 2 * AF_CH; idx += AF_THREADS) {
-    const int l = idx / (2 * AF_CH), j = idx % (2 * AF_CH), ri = j / AF_CH, c = j % AF_CH;
-    gs[l * AF_LD + j] = (l < Lc && c < nc) ? dP[(((b * Lc + l) * H + h) * 2 + ri) * (long)C + c0 + c] : 0.0f;
-  }
-  __syncthreads();
-  const int MT = (W + 15) >> 4, NT = (nc + 15) >> 4;
-  for (int t = wave; t < MT * NT; t += AF_THREADS / 64) {
-    const int mt = t / NT, nt = t % NT;
-    f32x4 dr = {0.f, 0.f, 0.f, 0.f}, di = {0.f, 0.f, 0.f, 0.f};
-    table_tile<true, false>(Tr, Ti, ldt, mt * 16, gs, AF_LD, nt * 16, AF_CH, Lp, dr, di);
-    const int c = nt * 16 + i;
-    for (int r = 0; r < 4; ++r) {
-      const int w = mt * 16 + 4 * kk + r;
-      if (w < W && c < nc) dx[((b * H + h) * W + w) * (long)C + c0 + c] = dr[r];
-    }
-  }
-}
+// ---- launch B3's store: dx is the transform's value itself ------------------------------------------------------------------------------
+struct AfnoBwdEpilogue {
+  __device__ float operator()(float v, long) const { return v; }
+};
 
 // ---- the weight gradients: the workgroups' partials, added in slot order ------------------------------------------------------------------
 __global__ __launch_bounds__(256) void afno_wgrad_reduce_kernel(const float* __restrict__ part1, const float* __restrict__ part2, long n_part,
@@ -325,9 +271,12 @@ extern "C" int tante_afno_filter_bwd(const float* dout, const float* P, int64_t 
   float* part2 = part1 + 2 * B * t.Lc * (int64_t)bs * C;
   hipStream_t s = (hipStream_t)stream;
   if (B > 0) {
-    const unsigned cch = (unsigned)((C + AF_CH - 1) / AF_CH);
-    hipLaunchKernelGGL(afno_bwd_h_kernel, dim3((unsigned)(B * W), cch), dim3(AF_THREADS), 0, s, dout, twiddles_bwd + a.re[3], twiddles_bwd + a.im[3],
-                       a.Kp[3], dG, H, W, C, t.Lc);
+    const unsigned cch = (unsigned)((C + DFT_CH - 1) / DFT_CH);
+    const long C1 = C, C2 = 2l * C;
+    const DftRows bwd_h = {H * W * C1, C1, W * C1, W * t.Lc * C2, t.Lc * C2, C2, W};      // the columns (b, w) of dout -> dG[b][w]
+    const DftRows bwd_w = {t.Lc * H * C2, C2, H * C2, H * W * C1, W * C1, C1, H};         // dP[b][l][h] -> dx rows (b, h)
+    hipLaunchKernelGGL(dft_r2c_rows_kernel, dim3((unsigned)(B * W), cch), dim3(DFT_THREADS), 0, s, dout, twiddles_bwd + a.re[3],
+                       twiddles_bwd + a.im[3], a.Kp[3], dG, bwd_h, H, t.Lc, C);
     TANTE_CHECK_LAUNCH();
     const int bsP = r16(bs);
     const size_t lds = sizeof(float) * (size_t)(2 * r16(t.Kc) + afb_rows_r(H, W, t.Kc)) * (2 * bsP + 4);
@@ -337,8 +286,8 @@ extern "C" int tante_afno_filter_bwd(const float* dout, const float* P, int64_t 
                        twiddles + t.re[1], twiddles + t.im[1], t.Kp[1], twiddles_bwd + a.re[2], twiddles_bwd + a.im[2], a.Kp[2],
                        twiddles_bwd + a.re[1], twiddles_bwd + a.im[1], a.Kp[1], w1, w2, lambda, dP, part1, part2, keep, H, W, C, bs, t.Lc, t.Kc);
     TANTE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(afno_bwd_w_kernel, dim3((unsigned)(B * H), cch), dim3(AF_THREADS), 0, s, (const float*)dP, twiddles_bwd + a.re[0],
-                       twiddles_bwd + a.im[0], a.Kp[0], dx, H, W, C, t.Lc);
+    hipLaunchKernelGGL(dft_c2r_rows_kernel<AfnoBwdEpilogue>, dim3((unsigned)(B * H), cch), dim3(DFT_THREADS), 0, s, (const float*)dP,
+                       twiddles_bwd + a.re[0], twiddles_bwd + a.im[0], a.Kp[0], dx, bwd_w, t.Lc, W, C, AfnoBwdEpilogue{});
     TANTE_CHECK_LAUNCH();
   }
   const long n_el = 2l * C * bs;

@@ -42,8 +42,6 @@ constexpr int TM_TOK = 64;                 // tokens a workgroup of the time ker
 constexpr int FS_SLAB = 4096;              // elements a slab of the field statistics aims for
 constexpr int FS_SLABS = 64;
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 // ================================================================ instance norms ========================================================
 struct InPlan {
   int R, S, strips;      // rows per slab, slabs, 64-channel strips

@@ -129,6 +129,9 @@ __device__ __forceinline__ void st_wt8(void* p, const u32x2& v) {
   asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
 }
 
+// one v_mfma_f32_16x16x4_f32 step: exact fp32 products, fp32 accumulation
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
 // ---- activations (always evaluated in fp32) ---------------------------------------------------
 __device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 // erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7): one v_exp, one v_rcp, 6 fma -- a third of ocml erff.

@@ -34,7 +34,6 @@ constexpr int DL_CH = 32;
 constexpr int C3_CO = 16;                  // output channels per workgroup of the 3 x 3 convolution
 constexpr int C3_MAXCIN = 128, C3_MAXCOUT = 64;
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4 mfma32(const u32x4& a, const u32x4& b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }

@@ -20,8 +20,8 @@
 //                                                                                             T4 = c_l e^{+2 pi i l w / W} / sqrt(W)
 //
 // c_l = 1 for l = 0 and l = W/2 (W even), 2 otherwise: the complex-to-real weights; the table entries of those two columns are real, so
-// their imaginary input drops out by itself.  The tables come from the host (float64, rounded once, zero padded to whole 16-row /
-// 4-column fragments).
+// their imaginary input drops out by itself.  Launch 1 is dft_r2c_rows_kernel and launch 6 dft_c2r_rows_kernel<DpotInvEpilogue> of
+// dft_rows.hip.h, which also holds the table layout and the table product; launches 2 .. 5 are this file's.
 //
 // The block MLP reads w1 / w2 (2, nb, bs, bs) and b1 / b2 (2, nb, bs) as the state dict holds them and evaluates the four real products
 // Re = Xr Wr - Xi Wi, Im = Xi Wr + Xr Wi.  Its rows are few (B k1 k2: 40 per sample at the reference's config) against 2 x nb x bs^2
@@ -33,23 +33,17 @@
 // Every product is v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 accumulation, in both compute modes.  A operand lane (i = l & 15,
 // k = l >> 4), B operand lane (k = l >> 4, j = l & 15), result register r = row 4 (l >> 4) + r, column l & 15.  LDS is plain C++ between
 // barriers: no hand-placed waits.
-#include "common.hip.h"
+#include "dft_rows.hip.h"
 
 namespace {
 
-constexpr int DP_MAX = 64;                 // grid points per axis
+constexpr int DP_MAX = DFT_MAX;            // grid points per axis
 constexpr int DP_MAX_BS = 512;             // channels per block
-constexpr int DP_THREADS = 256;            // four waves
-constexpr int DP_CH = 64;                  // channels per workgroup of the transform launches
-constexpr int DP_LD1 = DP_CH + 4;          // LDS row stride of launch 1 (real rows)
-constexpr int DP_LD = 2 * DP_CH + 4;       // LDS row stride of launches 2, 5, 6 ([re | im] rows)
+constexpr int DP_THREADS = DFT_THREADS;    // four waves
 constexpr int DP_MT = 12;                  // row tiles per workgroup of the MLP launches: 192 rows
 constexpr int GN_MAX_HW = 4096;
 constexpr int GN_SLABS = 64;               // slabs per group at most
 constexpr int GN_SLAB_ELEMS = 4096;        // elements a slab aims for
-
-inline int r4(int n) { return (n + 3) & ~3; }
-inline int r16(int n) { return (n + 15) & ~15; }
 
 // ================================================================ GroupNorm =============================================================
 struct GnPlan {
@@ -149,83 +143,15 @@ __global__ __launch_bounds__(DP_THREADS) void gn_apply_kernel(const float* __res
 }
 
 // ================================================================ the mixer ==============================================================
-struct DpTables {        // element offsets into the packed twiddle buffer: table t has its real plane at re[t], the imaginary one behind it
+struct DpTables : DftTables {
   int k1, k2;
-  int Kp[4];
-  long re[4], im[4], total;
 };
 
+// T1 (k2, W), T2 (k1, H), T3 (H, k1), T4 (W, k2)
 DpTables dp_tables(int H, int W, int modes) {
-  DpTables t;
-  t.k1 = modes < H ? modes : H;
-  t.k2 = modes < (W / 2 + 1) ? modes : (W / 2 + 1);
-  const int M[4] = {t.k2, t.k1, H, W}, K[4] = {W, H, t.k1, t.k2};
-  long off = 0;
-  for (int i = 0; i < 4; ++i) {
-    const long plane = (long)r16(M[i]) * r4(K[i]);
-    t.Kp[i] = r4(K[i]);
-    t.re[i] = off;
-    t.im[i] = off + plane;
-    off += 2 * plane;
-  }
-  t.total = off;
-  return t;
-}
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// (dr + i di) = sum_k (Tr + i Ti)[m0 + i][k] * (B[k][n0 + j] + i B[k][n0 + j + im_off]) over k < Kp (a multiple of 4), B in LDS
-template <bool B_COMPLEX, bool WANT_IM>
-__device__ __forceinline__ void table_tile(const float* __restrict__ Tr, const float* __restrict__ Ti, int ldt, int m0, const float* Bs, int ldb,
-                                           int n0, int im_off, int Kp, f32x4& dr, f32x4& di) {
-  const int lane = threadIdx.x & 63, i = lane & 15, kk = lane >> 4;
-  const float* tr = Tr + (long)(m0 + i) * ldt + kk;
-  const float* ti = Ti + (long)(m0 + i) * ldt + kk;
-  const float* b = Bs + kk * ldb + n0 + i;
-  for (int k = 0; k < Kp; k += 4) {
-    const float ar = tr[k], ai = ti[k];
-    const float br = b[k * ldb];
-    dr = mfma4(ar, br, dr);
-    if (WANT_IM) di = mfma4(ai, br, di);
-    if (B_COMPLEX) {
-      const float bi = b[k * ldb + im_off];
-      dr = mfma4(-ai, bi, dr);
-      if (WANT_IM) di = mfma4(ar, bi, di);
-    }
-  }
-}
-
-// ---- launch 1: the truncated forward transform along w ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(DP_THREADS) void dpot_fwd_w_kernel(const float* __restrict__ x, const float* __restrict__ Tr, const float* __restrict__ Ti,
-                                                                int ldt, float* __restrict__ P, int H, int W, int C, int k2) {
-  __shared__ float xs[DP_MAX * DP_LD1];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, kk = lane >> 4;
-  const long b = blockIdx.x / H;
-  const int h = blockIdx.x % H;
-  const int c0 = blockIdx.y * DP_CH;
-  const int nc = (C - c0) < DP_CH ? (C - c0) : DP_CH;
-  const int Wp = (W + 3) & ~3;
-  const float* xrow = x + ((b * H + h) * W) * (long)C + c0;
-  for (int idx = tid; idx < Wp * DP_CH; idx += DP_THREADS) {
-    const int w = idx / DP_CH, c = idx % DP_CH;
-    xs[w * DP_LD1 + c] = (w < W && c < nc) ? xrow[(long)w * C + c] : 0.0f;
-  }
-  __syncthreads();
-  const int MT = (k2 + 15) >> 4, NT = (nc + 15) >> 4;
-  for (int t = wave; t < MT * NT; t += DP_THREADS / 64) {
-    const int mt = t / NT, nt = t % NT;
-    f32x4 dr = {0.f, 0.f, 0.f, 0.f}, di = {0.f, 0.f, 0.f, 0.f};
-    table_tile<false, true>(Tr, Ti, ldt, mt * 16, xs, DP_LD1, nt * 16, 0, Wp, dr, di);
-    const int c = nt * 16 + i;
-    for (int r = 0; r < 4; ++r) {
-      const int l = mt * 16 + 4 * kk + r;
-      if (l < k2 && c < nc) {
-        float* p = P + (((b * k2 + l) * H + h) * 2) * (long)C + c0 + c;
-        p[0] = dr[r];
-        p[C] = di[r];
-      }
-    }
-  }
+  const int k1 = modes < H ? modes : H, k2 = modes < (W / 2 + 1) ? modes : (W / 2 + 1);
+  const int M[4] = {k2, k1, H, W}, K[4] = {W, H, k1, k2};
+  return DpTables{dft_tables(M, K), k1, k2};
 }
 
 // ---- launch 2: the truncated forward transform along h, into the MLP's (g, row, [re | im], bsP) layout ------------------------------------
@@ -233,25 +159,25 @@ __global__ __launch_bounds__(DP_THREADS) void dpot_fwd_w_kernel(const float* __r
 __global__ __launch_bounds__(DP_THREADS) void dpot_fwd_h_kernel(const float* __restrict__ P, const float* __restrict__ Tr, const float* __restrict__ Ti,
                                                                 int ldt, float* __restrict__ X, int H, int C, int bs, int bsP, int nb, int k1, int k2,
                                                                 long Mtot) {
-  __shared__ float ps[DP_MAX * DP_LD];
+  __shared__ float ps[DP_MAX * DFT_LD];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, kk = lane >> 4;
   const int l = blockIdx.x;
-  const int pc0 = blockIdx.y * DP_CH;
+  const int pc0 = blockIdx.y * DFT_CH;
   const long b = blockIdx.z;
-  const int npc = (nb * bsP - pc0) < DP_CH ? (nb * bsP - pc0) : DP_CH;       // a multiple of 16
+  const int npc = (nb * bsP - pc0) < DFT_CH ? (nb * bsP - pc0) : DFT_CH;       // a multiple of 16
   const int Hp = (H + 3) & ~3;
   const float* Pl = P + ((b * k2 + l) * H) * 2 * (long)C;
-  for (int idx = tid; idx < Hp * 2 * DP_CH; idx += DP_THREADS) {
-    const int h = idx / (2 * DP_CH), j = idx % (2 * DP_CH), ri = j / DP_CH, pc = pc0 + j % DP_CH;
+  for (int idx = tid; idx < Hp * 2 * DFT_CH; idx += DP_THREADS) {
+    const int h = idx / (2 * DFT_CH), j = idx % (2 * DFT_CH), ri = j / DFT_CH, pc = pc0 + j % DFT_CH;
     const int g = pc / bsP, q = pc % bsP;
-    ps[h * DP_LD + j] = (h < H && g < nb && q < bs) ? Pl[((long)h * 2 + ri) * C + g * bs + q] : 0.0f;
+    ps[h * DFT_LD + j] = (h < H && g < nb && q < bs) ? Pl[((long)h * 2 + ri) * C + g * bs + q] : 0.0f;
   }
   __syncthreads();
   const int MT = (k1 + 15) >> 4, NT = npc >> 4;
   for (int t = wave; t < MT * NT; t += DP_THREADS / 64) {
     const int mt = t / NT, nt = t % NT;
     f32x4 dr = {0.f, 0.f, 0.f, 0.f}, di = {0.f, 0.f, 0.f, 0.f};
-    table_tile<true, true>(Tr, Ti, ldt, mt * 16, ps, DP_LD, nt * 16, DP_CH, Hp, dr, di);
+    table_tile<true, true>(Tr, Ti, ldt, mt * 16, ps, DFT_LD, nt * 16, DFT_CH, Hp, dr, di);
     const int pc = pc0 + nt * 16 + i, g = pc / bsP, q = pc % bsP;
     for (int r = 0; r < 4; ++r) {
       const int k = mt * 16 + 4 * kk + r;
@@ -352,29 +278,29 @@ __global__ __launch_bounds__(DP_THREADS) void dpot_mlp_kernel(const float* __res
 __global__ __launch_bounds__(DP_THREADS) void dpot_inv_h_kernel(const float* __restrict__ Y, const float* __restrict__ Tr, const float* __restrict__ Ti,
                                                                 int ldt, float* __restrict__ Z, int H, int C, int bs, int bsP, int k1, int k2,
                                                                 long Mtot) {
-  __shared__ float ys[DP_MAX * DP_LD];
+  __shared__ float ys[DP_MAX * DFT_LD];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, kk = lane >> 4;
   const int l = blockIdx.x;
-  const int c0 = blockIdx.y * DP_CH;
+  const int c0 = blockIdx.y * DFT_CH;
   const long b = blockIdx.z;
-  const int nc = (C - c0) < DP_CH ? (C - c0) : DP_CH;
+  const int nc = (C - c0) < DFT_CH ? (C - c0) : DFT_CH;
   const int Kp = (k1 + 3) & ~3;
-  for (int idx = tid; idx < Kp * 2 * DP_CH; idx += DP_THREADS) {
-    const int k = idx / (2 * DP_CH), j = idx % (2 * DP_CH), ri = j / DP_CH, c = j % DP_CH;
+  for (int idx = tid; idx < Kp * 2 * DFT_CH; idx += DP_THREADS) {
+    const int k = idx / (2 * DFT_CH), j = idx % (2 * DFT_CH), ri = j / DFT_CH, c = j % DFT_CH;
     float v = 0.0f;
     if (k < k1 && c < nc) {
       const int g = (c0 + c) / bs, q = (c0 + c) % bs;
       const long m = (b * k1 + k) * k2 + l;
       v = Y[((g * Mtot + m) * 2 + ri) * (long)bsP + q];
     }
-    ys[k * DP_LD + j] = v;
+    ys[k * DFT_LD + j] = v;
   }
   __syncthreads();
   const int MT = (H + 15) >> 4, NT = (nc + 15) >> 4;
   for (int t = wave; t < MT * NT; t += DP_THREADS / 64) {
     const int mt = t / NT, nt = t % NT;
     f32x4 dr = {0.f, 0.f, 0.f, 0.f}, di = {0.f, 0.f, 0.f, 0.f};
-    table_tile<true, true>(Tr, Ti, ldt, mt * 16, ys, DP_LD, nt * 16, DP_CH, Kp, dr, di);
+    table_tile<true, true>(Tr, Ti, ldt, mt * 16, ys, DFT_LD, nt * 16, DFT_CH, Kp, dr, di);
     const int c = nt * 16 + i;
     for (int r = 0; r < 4; ++r) {
       const int h = mt * 16 + 4 * kk + r;
@@ -387,39 +313,15 @@ __global__ __launch_bounds__(DP_THREADS) void dpot_inv_h_kernel(const float* __r
   }
 }
 
-// ---- launch 6: the W-point complex-to-real inverse over the k2 kept columns, the inner skip and the optional residual ----------------------
-__global__ __launch_bounds__(DP_THREADS) void dpot_inv_w_kernel(const float* __restrict__ Z, const float* __restrict__ Tr, const float* __restrict__ Ti,
-                                                                int ldt, const float* __restrict__ x, const float* resid, float* out, int H, int W,
-                                                                int C, int k2) {
-  __shared__ float zs[DP_MAX * DP_LD];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, kk = lane >> 4;
-  const long b = blockIdx.x / H;
-  const int h = blockIdx.x % H;
-  const int c0 = blockIdx.y * DP_CH;
-  const int nc = (C - c0) < DP_CH ? (C - c0) : DP_CH;
-  const int Lp = (k2 + 3) & ~3;
-  const float* Zh = Z + ((b * H + h) * k2) * 2 * (long)C + c0;
-  for (int idx = tid; idx < Lp * 2 * DP_CH; idx += DP_THREADS) {
-    const int l = idx / (2 * DP_CH), j = idx % (2 * DP_CH), ri = j / DP_CH, c = j % DP_CH;
-    zs[l * DP_LD + j] = (l < k2 && c < nc) ? Zh[((long)l * 2 + ri) * C + c] : 0.0f;
+// ---- launch 6's store: the inner skip and the optional residual -------------------------------------------------------------------------
+struct DpotInvEpilogue {
+  const float* x;
+  const float* resid;
+  __device__ float operator()(float v, long o) const {
+    const float f = v + x[o];                // the filter's own skip: its value without a residual
+    return resid ? f + resid[o] : f;         // one more fp32 add of the finished value
   }
-  __syncthreads();
-  const int MT = (W + 15) >> 4, NT = (nc + 15) >> 4;
-  for (int t = wave; t < MT * NT; t += DP_THREADS / 64) {
-    const int mt = t / NT, nt = t % NT;
-    f32x4 dr = {0.f, 0.f, 0.f, 0.f}, di = {0.f, 0.f, 0.f, 0.f};
-    table_tile<true, false>(Tr, Ti, ldt, mt * 16, zs, DP_LD, nt * 16, DP_CH, Lp, dr, di);
-    const int c = nt * 16 + i;
-    for (int r = 0; r < 4; ++r) {
-      const int w = mt * 16 + 4 * kk + r;
-      if (w < W && c < nc) {
-        const long o = ((b * H + h) * W + w) * (long)C + c0 + c;
-        const float f = dr[r] + x[o];            // the filter's own skip: its value without a residual
-        out[o] = resid ? f + resid[o] : f;       // one more fp32 add of the finished value
-      }
-    }
-  }
-}
+};
 
 const char* dp_reason(int64_t B, int H, int W, int C, int bs, int modes, int hidden_factor) {
   if (H < 1 || W < 1 || H > DP_MAX || W > DP_MAX) return "token grid outside 1..64 points per axis";
@@ -509,10 +411,13 @@ extern "C" int tante_dpot_filter(const float* x, const float* residual, int64_t 
   float* X = P + k.spat;            // and Y
   float* V = X + k.blk;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned cch = (unsigned)((C + DP_CH - 1) / DP_CH), pch = (unsigned)((nb * bsP + DP_CH - 1) / DP_CH);
+  const unsigned cch = (unsigned)((C + DFT_CH - 1) / DFT_CH), pch = (unsigned)((nb * bsP + DFT_CH - 1) / DFT_CH);
   const dim3 mlp_grid((unsigned)((k.Mtot + 16 * DP_MT - 1) / (16 * DP_MT)), (unsigned)(bsP / 16), (unsigned)nb);
-  hipLaunchKernelGGL(dpot_fwd_w_kernel, dim3((unsigned)(B * H), cch), dim3(DP_THREADS), 0, s, x, twiddles + t.re[0], twiddles + t.im[0], t.Kp[0], P, H, W, C,
-                     t.k2);
+  const long C1 = C, C2 = 2l * C;
+  const DftRows fwd_w = {H * W * C1, W * C1, C1, t.k2 * H * C2, C2, H * C2, H};       // x rows (b, h) -> P[b][l][h]
+  const DftRows inv_w = {H * t.k2 * C2, t.k2 * C2, C2, H * W * C1, W * C1, C1, H};    // Z[b][h] -> out rows (b, h)
+  hipLaunchKernelGGL(dft_r2c_rows_kernel, dim3((unsigned)(B * H), cch), dim3(DFT_THREADS), 0, s, x, twiddles + t.re[0], twiddles + t.im[0], t.Kp[0], P,
+                     fwd_w, W, t.k2, C);
   TANTE_CHECK_LAUNCH();
   hipLaunchKernelGGL(dpot_fwd_h_kernel, dim3((unsigned)t.k2, pch, (unsigned)B), dim3(DP_THREADS), 0, s, (const float*)P, twiddles + t.re[1],
                      twiddles + t.im[1], t.Kp[1], X, H, C, bs, bsP, nb, t.k1, t.k2, k.Mtot);
@@ -524,8 +429,8 @@ extern "C" int tante_dpot_filter(const float* x, const float* residual, int64_t 
   hipLaunchKernelGGL(dpot_inv_h_kernel, dim3((unsigned)t.k2, cch, (unsigned)B), dim3(DP_THREADS), 0, s, (const float*)X, twiddles + t.re[2],
                      twiddles + t.im[2], t.Kp[2], P, H, C, bs, bsP, t.k1, t.k2, k.Mtot);
   TANTE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(dpot_inv_w_kernel, dim3((unsigned)(B * H), cch), dim3(DP_THREADS), 0, s, (const float*)P, twiddles + t.re[3], twiddles + t.im[3],
-                     t.Kp[3], x, residual, out, H, W, C, t.k2);
+  hipLaunchKernelGGL(dft_c2r_rows_kernel<DpotInvEpilogue>, dim3((unsigned)(B * H), cch), dim3(DFT_THREADS), 0, s, (const float*)P, twiddles + t.re[3],
+                     twiddles + t.im[3], t.Kp[3], out, inv_w, t.k2, W, C, DpotInvEpilogue{x, residual});
   TANTE_CHECK_LAUNCH();
   return 0;
 }

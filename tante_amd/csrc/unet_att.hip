@@ -38,7 +38,6 @@ constexpr int UA_MAXCIN = 2048, UA_MAXCOUT = 1024;
 constexpr int UA_PLAIN = 0, UA_POOLED = 1, UA_UPSAMPLED = 2;
 constexpr int AG_MAXK = 1024, AG_MAXN = 256;
 
-__device__ __forceinline__ f32x4 ua_mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4 ua_mfma32(const u32x4& a, const u32x4& b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
@@ -229,7 +228,7 @@ __global__ __launch_bounds__(UA_THREADS) void ua_conv_kernel(const UaArgs p) {
             for (int n = 0; n < NW; ++n) {
               const f32x4 wq = __builtin_bit_cast(f32x4, wv[n]);
 #pragma unroll
-              for (int s = 0; s < 4; ++s) acc[r][n] = ua_mfma4(wq[s], tf[s], acc[r][n]);
+              for (int s = 0; s < 4; ++s) acc[r][n] = mfma4(wq[s], tf[s], acc[r][n]);
             }
           }
         }
@@ -400,7 +399,7 @@ __global__ __launch_bounds__(UA_THREADS) void ag_kernel(const float* __restrict_
       for (int n = 0; n < NTW; ++n) {
         const f32x4 wq = __builtin_bit_cast(f32x4, wf[((long)n * G + gk) * 64]);
 #pragma unroll
-        for (int s = 0; s < 4; ++s) acc[n] = ua_mfma4(wq[s], t[s], acc[n]);
+        for (int s = 0; s < 4; ++s) acc[n] = mfma4(wq[s], t[s], acc[n]);
       }
     }
   }

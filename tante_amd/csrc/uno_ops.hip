@@ -47,8 +47,6 @@ constexpr int UNO_THREADS = 256;           // four waves
 constexpr int UNO_MT = 4;                  // 16-row tiles per wave of uno_gemm_kernel
 constexpr int UNO_PASS = 8;                // images per pass of the mode mix
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 // D[p][m, n] = act(sum_k T[m, k] B[p][k, n] + add[p][m, n] + bias[p % pdiv]), plane p = (p / pdiv, p % pdiv)
 struct UnoGemm {
   const float* T;        // (M, K) dense, row stride ldt

@@ -32,15 +32,12 @@ from . import _lib as L
 from . import kernels as K
 from . import stages as S
 from .attn_backbone import _PackCache, resolve_compute
+from .dft_tables import cis, device_tables, pack_tables
 
 MAX_GRID = 64       # token-grid points per axis the mixer serves
 MAX_BLOCK = 512     # channels per block
 MAX_TOKENS = 4096   # tokens per sample tante_groupnorm serves
 GROUPS = 8          # torch.nn.GroupNorm(8, width)  (dpot.py:138, 147)
-
-
-def _r(n: int, m: int) -> int:
-    return (n + m - 1) // m * m
 
 
 # ---- host side of tante_groupnorm / tante_dpot_filter: the predicates' mirrors, the twiddle tables -----------------------------------------
@@ -60,49 +57,23 @@ def kept_modes(H: int, W: int, modes: int) -> Tuple[int, int]:
     return min(modes, H), min(modes, W // 2 + 1)
 
 
-def _cis(num: np.ndarray, n: int, sign: int) -> np.ndarray:
-    """e^{sign 2 pi i num / n} in float64 with the angle reduced in integers (so the entries that are real / imaginary are exactly so)."""
-    m = np.mod(num, n).astype(np.float64)
-    z = np.cos(2.0 * np.pi * m / n) + sign * 1j * np.sin(2.0 * np.pi * m / n)
-    z.real[np.abs(z.real) < 1e-15] = 0.0
-    z.imag[np.abs(z.imag) < 1e-15] = 0.0
-    return z
-
-
 def twiddle_tables(H: int, W: int, modes: int) -> List[np.ndarray]:
     """The four complex128 tables of tante_dpot_filter (include/tante_hip.h), unpadded: T1 (k2, W), T2 (k1, H), T3 (H, k1), T4 (W, k2)."""
     k1, k2 = kept_modes(H, W, modes)
     k, l, h, w = np.arange(k1), np.arange(k2), np.arange(H), np.arange(W)
     cl = np.where((l == 0) | ((W % 2 == 0) & (l == W // 2)), 1.0, 2.0)
-    return [_cis(np.outer(l, w), W, -1) / np.sqrt(W), _cis(np.outer(k, h), H, -1) / np.sqrt(H),
-            _cis(np.outer(h, k), H, +1) / np.sqrt(H), _cis(np.outer(w, l), W, +1) * cl[None, :] / np.sqrt(W)]
+    return [cis(np.outer(l, w), W, -1) / np.sqrt(W), cis(np.outer(k, h), H, -1) / np.sqrt(H),
+            cis(np.outer(h, k), H, +1) / np.sqrt(H), cis(np.outer(w, l), W, +1) * cl[None, :] / np.sqrt(W)]
 
 
 def pack_twiddles(H: int, W: int, modes: int) -> np.ndarray:
     """-> the float32 buffer tante_dpot_filter reads: per table a real then an imaginary plane, rows padded to 16, columns to 4."""
-    planes = []
-    for t in twiddle_tables(H, W, modes):
-        p = np.zeros((2, _r(t.shape[0], 16), _r(t.shape[1], 4)), dtype=np.float32)
-        p[0, :t.shape[0], :t.shape[1]] = t.real
-        p[1, :t.shape[0], :t.shape[1]] = t.imag
-        planes.append(p.reshape(-1))
-    return np.concatenate(planes)
-
-
-_TWIDDLES = {}     # (H, W, k1, k2, device) -> packed tables on the device: weight independent, built once per shape
+    return pack_tables(twiddle_tables(H, W, modes))
 
 
 def _twiddles(H: int, W: int, modes: int, device) -> torch.Tensor:
-    key = (H, W) + kept_modes(H, W, modes) + (str(device),)
-    t = _TWIDDLES.get(key)
-    if t is None:
-        host = pack_twiddles(H, W, modes)
-        n = int(L.lib().tante_dpot_twiddle_floats(H, W, modes))
-        if n != host.size:
-            raise RuntimeError(f"twiddle tables for a {H} x {W} grid with {modes} modes: {host.size} floats packed, the library expects {n}")
-        t = torch.from_numpy(host).to(device)
-        _TWIDDLES[key] = t
-    return t
+    return device_tables(("dpot", H, W) + kept_modes(H, W, modes), lambda: pack_twiddles(H, W, modes),
+                         L.lib().tante_dpot_twiddle_floats(H, W, modes), f"twiddle tables for a {H} x {W} grid with {modes} modes", device)
 
 
 def fold_time_weight(w: torch.Tensor, gamma: Optional[torch.Tensor]) -> torch.Tensor:
@@ -275,12 +246,7 @@ class Block(nn.Module):
             skip = x
         n2 = groupnorm(f, GROUPS, self.norm2.weight.detach(), self.norm2.bias.detach(), self.norm2.eps, K.act_torch_dtype(compute))
         h = S.linear_chunks(n2.view(M, C_), fc1, K.act_torch_dtype(compute), L.ACT_GELU_ERF)
-        y = torch.empty(M, C_, dtype=torch.float32, device=x.device)
-        k0, Kt = 0, h.shape[1]
-        for i, pw in enumerate(fc2):                 # K-chunks accumulate through the residual operand; the first one carries the skip
-            K.linear(h, pw, y, M=M, a_n0=M, a_s0=Kt, a_off=k0, residual=skip.view(M, C_) if i == 0 else y)
-            k0 += pw.K
-        return y.view(B, H, W, C_)
+        return S.linear_chunks(h, fc2, residual=skip.view(M, C_)).view(B, H, W, C_)      # the skip rides the residual operand
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(B, C, H, W) -> (B, C, H, W), as the reference's Block takes its images (GroupNorm and the 1 x 1 convs act on dim 1)."""
@@ -326,13 +292,7 @@ class PatchEmbed(nn.Module):
         adt = K.act_torch_dtype(compute)
         cols = K.im2col(x, True, n, cin, h, w, p, p, p, p, 0, 0, 0, adt)
         h1 = S.linear_chunks(cols, c0, adt, L.ACT_GELU_ERF)
-        M = h1.shape[0]
-        y = torch.empty(M, self.out_dim, dtype=torch.float32, device=x.device)
-        k0, Kt = 0, h1.shape[1]
-        for i, pw in enumerate(c2):
-            K.linear(h1, pw, y, M=M, a_n0=M, a_s0=Kt, a_off=k0, residual=residual if i == 0 else y)
-            k0 += pw.K
-        return y
+        return S.linear_chunks(h1, c2, residual=residual)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(B, C, H, W) -> (B, out_dim, H', W')  (dpot.py:193-197).  Inference only."""

@@ -32,10 +32,20 @@ def pack_linear_chunks(weight2d: torch.Tensor, bias: Optional[torch.Tensor], com
     return out
 
 
-def linear_chunks(a: torch.Tensor, chunks: List[K.PackedWeight], out_dtype: torch.dtype, act: int = L.ACT_NONE) -> torch.Tensor:
+def linear_chunks(a: torch.Tensor, chunks: List[K.PackedWeight], out_dtype: torch.dtype = torch.float32, act: int = L.ACT_NONE,
+                  residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = act(a @ W^T + b) for a dense (M, K) activation matrix of any K: the K-chunks accumulate through the GEMM's fp32
-    residual operand (chunk i reads `out` as residual and writes it back in place)."""
+    residual operand (chunk i reads `out` as residual and writes it back in place).  With `residual`: a @ W^T + b + residual, fp32
+    and without activation, the first chunk carrying the residual, into `out` where one is given (it may be `residual` itself)."""
     M, Kt = a.shape
+    if residual is not None:
+        if out is None:
+            out = torch.empty(M, chunks[0].N, dtype=torch.float32, device=a.device)
+        k0 = 0
+        for i, pw in enumerate(chunks):
+            K.linear(a, pw, out, M=M, a_n0=M, a_s0=Kt, a_off=k0, residual=residual if i == 0 else out)
+            k0 += pw.K
+        return out
     if len(chunks) == 1:
         out = torch.empty(M, chunks[0].N, dtype=out_dtype, device=a.device)
         return K.linear(a, chunks[0], out, M=M, act=act)
@@ -61,6 +71,11 @@ def conv_weight_2d(w: torch.Tensor, korder: int) -> torch.Tensor:
     if korder == 0:
         return w.reshape(w.shape[0], -1)
     return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+
+
+def conv_rows(w: torch.Tensor) -> torch.Tensor:
+    """Conv2d weight (Cout, Cin, kh, kw) -> contiguous (Cout, kh kw Cin): the channels-last im2col column order."""
+    return conv_weight_2d(w, 1).contiguous()
 
 
 def conv_stage(x: torch.Tensor, nchw: bool, n_img: int, Cin: int, H: int, W: int, P: int, overlap: float, chunks: List[K.PackedWeight],

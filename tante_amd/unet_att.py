@@ -31,7 +31,6 @@ from . import kernels as K
 from . import options as _O
 from . import stages as S
 from .attn_backbone import _PackCache, resolve_compute
-from .avit import _conv_rows, _gemm
 
 CONV_MAX_CIN, CONV_MAX_COUT = 2048, 1024     # channels tante_conv3x3_mfma serves
 GATE_MAX_K, GATE_MAX_N = 1024, 256           # gate plus skip channels, coefficients tante_attn_gate serves
@@ -202,7 +201,7 @@ def _conv_bn_act(a: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, cache: _P
 
     def build():
         w, shift = fold_conv_bn(conv, bn)
-        return S.pack_linear_chunks(_conv_rows(w), shift, compute)
+        return S.pack_linear_chunks(S.conv_rows(w), shift, compute)
     chunks = cache.get((slot, "im2col", compute), params, build)
     src = _source(a, form, b).contiguous()
     n, H, W, Cin = src.shape
@@ -315,8 +314,8 @@ class AttentionBlock(nn.Module):
             return (S.pack_linear_chunks(w[:, :Cg].contiguous(), b, compute), S.pack_linear_chunks(w[:, Cg:].contiguous(), None, compute), wp, bp)
         wg, wx, wp, bp = self._cache.get(("modular", compute), self._params(), build)
         adt = K.act_torch_dtype(compute)
-        h = _gemm(g2.to(adt), wg)
-        _gemm(x2.to(adt), wx, residual=h, out=h)
+        h = S.linear_chunks(g2.to(adt), wg)
+        S.linear_chunks(x2.to(adt), wx, residual=h, out=h)
         psi = torch.sigmoid(torch.relu(h) @ wp + bp)
         return (x2 * psi[:, None]).view(n, H, W, Cx)
 
@@ -410,5 +409,5 @@ class AttentionUNet(nn.Module):
         pw = self._cache.get(("head", hc), [self.Conv.weight, self.Conv.bias], lambda: S.pack_linear_chunks(
             self.Conv.weight.detach().reshape(self.dim_out, 64).contiguous(), self.Conv.bias.detach(), hc))
         rows = d.view(b * h * w, 64)
-        y = _gemm(rows if hc == L.F32 else rows.to(torch.bfloat16), pw)
+        y = S.linear_chunks(rows if hc == L.F32 else rows.to(torch.bfloat16), pw)
         return y.view(b, h, w, self.dim_out // self.out_T, self.out_T).permute(0, 4, 3, 1, 2).contiguous()     # the channel index is (c t)

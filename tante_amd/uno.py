@@ -35,7 +35,6 @@ from . import _lib as L
 from . import kernels as K
 from . import stages as S
 from .attn_backbone import _PackCache, resolve_compute
-from .avit import _gemm
 
 MAX_DIM, MAX_CH, MAX_PLANES = 512, 512, 65535      # what tante_uno_block serves
 _TABLES = {}
@@ -388,6 +387,6 @@ class UNO(nn.Module):
         r6 = torch.empty(b, h, w, 2 * wd, dtype=adt, device=dev)
         r6.copy_(c6[:, :, p:p + h, p:p + w].permute(0, 2, 3, 1))                       # the crop, to rows
         x_fc1 = S.linear_chunks(r6.view(M, 2 * wd), fc1, adt, L.ACT_GELU_ERF)          # (M, 3 width)
-        y = _gemm(x_fc1, fc2a)
-        _gemm(x_fc, fc2b, residual=y, out=y)                                           # [fc1 | fc] as two K-chunks
+        y = S.linear_chunks(x_fc1, fc2a)
+        S.linear_chunks(x_fc, fc2b, residual=y, out=y)                                 # [fc1 | fc] as two K-chunks
         return y.view(b, h, w, self.dim_out).permute(0, 3, 1, 2).unsqueeze(1).contiguous().to(x.dtype if x.dtype.is_floating_point else torch.float32)

@@ -159,7 +159,8 @@ def leaves(sd: dict) -> dict:
 
 
 # ---- the cases of the filter tests: (B, H, W, C, bs), seeds and weight scale as tests/test_hip_afno.py draws them ------------------------
-FILTER_CASES = [(2, 7, 9, 40, 8), (1, 12, 5, 48, 24), (1, 5, 12, 48, 24), (1, 64, 33, 48, 24), (1, 33, 64, 128, 64), (3, 1, 1, 16, 16)]
+FILTER_CASES = [(2, 7, 9, 40, 8), (1, 12, 5, 48, 24), (1, 5, 12, 48, 24), (1, 64, 33, 48, 24), (1, 33, 64, 128, 64), (3, 1, 1, 16, 16),
+                (1, 5, 12, 80, 16), (1, 12, 5, 80, 16)]
 
 
 def filter_case(B, H, W, C, bs):

@@ -80,7 +80,8 @@ def test_filter_with_residual(dev, name):
     assert torch.equal(stream, y1)
 
 
-@pytest.mark.parametrize("B,H,W,C,bs", [(2, 7, 9, 40, 8), (1, 64, 33, 48, 24), (1, 33, 64, 128, 64), (3, 1, 1, 16, 16)])
+@pytest.mark.parametrize("B,H,W,C,bs", [(2, 7, 9, 40, 8), (1, 64, 33, 48, 24), (1, 33, 64, 128, 64), (3, 1, 1, 16, 16),
+                                            (1, 5, 12, 80, 16), (1, 12, 5, 80, 16)])
 def test_filter_shapes_without_a_fixture(dev, B, H, W, C, bs):
     """Odd axes, the 64-point limit, block sizes that are no multiple of 16, the largest block, channel counts that are no multiple of the
     64-channel workgroup slice, a one-point grid: against the float64 restatement, relative to the filter's own output."""

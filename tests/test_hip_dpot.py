@@ -102,7 +102,7 @@ def random_filter(B, H, W, C, nb, modes):
 
 
 @pytest.mark.parametrize("B,H,W,C,nb,modes", [(1, 8, 8, 768, 2, 16), (1, 64, 33, 48, 2, 20), (1, 33, 64, 128, 2, 64), (3, 1, 1, 16, 1, 5),
-                                               (2, 7, 9, 40, 5, 2)])
+                                               (2, 7, 9, 40, 5, 2), (1, 5, 12, 80, 5, 4), (1, 12, 5, 80, 5, 4)])
 def test_filter_shapes_without_a_fixture(dev, B, H, W, C, nb, modes):
     """The shipped block size of 384; the 64-point limit on either axis with odd partners and modes past / at the grid; a one-point grid;
     five blocks of 8 on odd axes: against the float64 restatement, relative to the contribution."""
