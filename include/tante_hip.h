@@ -658,6 +658,37 @@ int64_t tante_dpot_filter_workspace_bytes(int64_t B, int H, int W, int C, int bs
 int tante_dpot_filter(const float* x, const float* residual, int64_t B, int H, int W, int C, int bs, int modes, int hidden_factor,
                       const float* twiddles, const float* w1, const float* b1, const float* w2, const float* b2, float* out, void* work,
                       int64_t work_bytes, void* stream);
+/* The backward of both (dpot_mixer_bwd.hip; added without an ABI bump: nothing that existed changed), for training a model that opted in
+ * (DPOT.set_trainable).  No atomics: every sum has a fixed order and two runs give the same bits.
+ * tante_groupnorm_bwd: what torch.autograd derives for torch.nn.GroupNorm (dpot.py:138, 147, 160, 167) on x (B, HW, C) fp32 with dy
+ * (B, HW, C) fp32 or bf16 (dy_dtype).  With xh = (x - mean) rstd, per (sample, group)
+ *   dx = rstd (gamma dy - mean(gamma dy) - xh mean(gamma dy xh)),   dgamma_c = sum dy xh,   dbeta_c = sum dy   over samples and tokens.
+ * The statistics are recomputed as the forward computes them (mean first, centred squares per slab, pairwise combine); the two group
+ * sums and the per-channel sums are a slab stage and then a combine over slabs (and samples) in order.  gamma NULL: no affine.  dx fp32;
+ * dgamma / dbeta (C) or NULL; accumulate != 0 adds onto what they hold.  Same served shapes and refusals as the forward.
+ *   work: _bwd_workspace_bytes(B, HW, C, G) bytes. */
+int tante_groupnorm_bwd_supported(int64_t B, int HW, int C, int G);
+int64_t tante_groupnorm_bwd_workspace_bytes(int64_t B, int HW, int C, int G);
+int tante_groupnorm_bwd(const void* dy, int dy_dtype, const float* x, int64_t B, int HW, int C, int G, float eps, const float* gamma, float* dx,
+                        float* dgamma, float* dbeta, int accumulate, void* work, int64_t work_bytes, void* stream);
+/* tante_dpot_filter_bwd: what torch.autograd derives for AFNO2D.forward (dpot.py:47-102).  The forward is P = T1 x, X = T2 P,
+ * U = X W1 + b1, V = gelu(Re U) + i gelu(Im U), Y = V W2 + b2, Z = T3 Y, out = Re(T4 Z) + x (+ residual); the backward runs it in reverse
+ * against the conjugate-transposed tables:
+ *   dZ = T4^H dout;  dY = T3^H dZ;  dU = (dY conj(W2)^T) gelu'(U) (real and imaginary part separately);  dX = dU conj(W1)^T;
+ *   dP = T2^H dX;  dx = Re(T1^H dP) + dout (the inner skip);  dW2 = conj(V)^T dY, db2 = sum dY, dW1 = conj(X)^T dU, db1 = sum dU.
+ * X and U are recomputed from x with the forward's own launches 1 .. 3 (the forward keeps neither); V is gelu(U) on load.  The gradient
+ * with respect to the residual is dout itself and is left to the caller.  Same served shapes and refusals as the forward (square
+ * blocks); fp32 MFMA products throughout.
+ *   twiddles: the forward's buffer.  twiddles_bwd: T1^H (W, k2), T2^H (H, k1), T3^H (k1, H), T4^H (k2, W), packed like the forward's:
+ *     _twiddle_bwd_floats(H, W, modes) floats in all (-1: unsupported grid).
+ *   dx (B, H, W, C), neither dout nor x.  dw1, dw2 (2, nb, bs, bs) and db1, db2 (2, nb, bs) in the state dict's layout, summed over
+ *     samples and modes by one wave per 16 x 16 tile in row order; accumulate != 0 adds them onto what the buffers hold.
+ *   work: _bwd_workspace_bytes(...) bytes, 16-byte aligned. */
+int64_t tante_dpot_twiddle_bwd_floats(int H, int W, int modes);
+int64_t tante_dpot_filter_bwd_workspace_bytes(int64_t B, int H, int W, int C, int bs, int modes);
+int tante_dpot_filter_bwd(const float* dout, const float* x, int64_t B, int H, int W, int C, int bs, int modes, const float* twiddles,
+                          const float* twiddles_bwd, const float* w1, const float* b1, const float* w2, float* dx, float* dw1, float* db1,
+                          float* dw2, float* db2, int accumulate, void* work, int64_t work_bytes, void* stream);
 /* Backward of tante_cross_attention.  o is the forward output; dq gets the query gradient in the layout of q; the key / value gradients
  * are ADDED (fp32 atomics) to dk / dv, rows (b, j) at (b*Lk + j)*ldg + h*D -- zero them first.  stats: n_batch*n_head*Lq*3 floats of
  * scratch (softmax max, 1 / sum, dO . O per query). */

@@ -281,6 +281,13 @@ SIGNATURES = {
     "tante_dpot_filter_workspace_bytes": ([c_i64, c_i32, c_i32, c_i32, c_i32, c_i32], c_i64),
     "tante_dpot_filter": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
                           c_i32),
+    "tante_groupnorm_bwd_supported": ([c_i64, c_i32, c_i32, c_i32], c_i32),
+    "tante_groupnorm_bwd_workspace_bytes": ([c_i64, c_i32, c_i32, c_i32], c_i64),
+    "tante_groupnorm_bwd": ([c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp], c_i32),
+    "tante_dpot_twiddle_bwd_floats": ([c_i32, c_i32, c_i32], c_i64),
+    "tante_dpot_filter_bwd_workspace_bytes": ([c_i64, c_i32, c_i32, c_i32, c_i32, c_i32], c_i64),
+    "tante_dpot_filter_bwd": ([c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                               c_i32, c_vp, c_i64, c_vp], c_i32),
     "tante_instnorm_supported": ([c_i64, c_i32, c_i32], c_i32),
     "tante_instnorm_workspace_bytes": ([c_i64, c_i32, c_i32], c_i64),
     "tante_instnorm": ([c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp], c_i32),
@@ -333,7 +340,7 @@ LIB_OPTIONS = ("TANTE_ATTN_BWD_HG", "TANTE_ATTN_BWD_NO_SPLIT", "TANTE_ATTN_BWD_V
 
 
 _lib = None
-ABI_VERSION = 14     # include/tante_hip.h: bumped whenever an entry point is added or changes (round 4: 6 tante_head_enc_*, 7 tante_pos_embed_tmajor + tante_spectral_*bf16out*; round 5: 8 tante_block_bwd_fused, 9 TanteGemm.a_pad; round 6: 10 tante_tail_*, 11 tante_attention_masked_bwd, 12 tante_spectral_layer_x, tante_axis_mlp_film; round 7: 13 tante_block_fused_last; 14 tante_attention_flash*; still 14: tante_attention_flash_masked + tante_attention_flash_masked_bwd were ADDED without a bump -- nothing that existed changed its signature or meaning, so a caller built against 14 runs unchanged, and the suite pins 14 (test_abi_version_is_14); a caller that needs the two looks the symbols up; the same holds for the six tante_adaptive_* / tante_head_adaptive entries of the adaptive-step tail, for tante_cross_attention_route, for the four tante_afno_* entries of the AFNO filter, for the three tante_groupnorm* and four tante_dpot_* entries of DPOT, for the twelve tante_instnorm* / tante_axial_attention* / tante_time_attention* / tante_field_* entries of AViT, for tante_encode_window_raw with its three tante_*enc1_raw* helpers, and for the ten tante_convnext_* / tante_pack_convnext / tante_dwconv_ln* / tante_l2norm_rows* / tante_conv3x3* entries of UNetConvNext, and for the eight tante_conv3x3_mfma* / tante_pack_conv3x3 / tante_conv3x3_pack_bytes / tante_attn_gate* / tante_pack_attn_gate entries of AttentionUNet)
+ABI_VERSION = 14     # include/tante_hip.h: bumped whenever an entry point is added or changes (round 4: 6 tante_head_enc_*, 7 tante_pos_embed_tmajor + tante_spectral_*bf16out*; round 5: 8 tante_block_bwd_fused, 9 TanteGemm.a_pad; round 6: 10 tante_tail_*, 11 tante_attention_masked_bwd, 12 tante_spectral_layer_x, tante_axis_mlp_film; round 7: 13 tante_block_fused_last; 14 tante_attention_flash*; still 14: tante_attention_flash_masked + tante_attention_flash_masked_bwd were ADDED without a bump -- nothing that existed changed its signature or meaning, so a caller built against 14 runs unchanged, and the suite pins 14 (test_abi_version_is_14); a caller that needs the two looks the symbols up; the same holds for the six tante_adaptive_* / tante_head_adaptive entries of the adaptive-step tail, for tante_cross_attention_route, for the four tante_afno_* entries of the AFNO filter, for the three tante_groupnorm* and four tante_dpot_* entries of DPOT and the three tante_groupnorm_bwd* and three tante_dpot_*_bwd* entries of its training path, for the twelve tante_instnorm* / tante_axial_attention* / tante_time_attention* / tante_field_* entries of AViT, for tante_encode_window_raw with its three tante_*enc1_raw* helpers, and for the ten tante_convnext_* / tante_pack_convnext / tante_dwconv_ln* / tante_l2norm_rows* / tante_conv3x3* entries of UNetConvNext, and for the eight tante_conv3x3_mfma* / tante_pack_conv3x3 / tante_conv3x3_pack_bytes / tante_attn_gate* / tante_pack_attn_gate entries of AttentionUNet)
 
 
 def lib():

@@ -18,8 +18,19 @@ torch allocates, reshapes and makes the one copy named above.
 `cls_head` holds its parameters for the state dict and is NEVER evaluated: the reference computes cls_pred and discards it
 (dpot.py:343-344).
 
-Inference only (eval mode under no_grad).  Training, n_spatial_dims = 3, act other than 'gelu', mixing_type other than 'afno' and
-hidden_size_factor != 1 raise NotImplementedError; there is no CPU fallback."""
+Inference is the default: a model whose parameters require a gradient refuses under grad (and in train()), as it always did.  Training is
+opt-in through `model.set_trainable()`.  An opted-in model called under grad takes dpot_train_forward: the same arithmetic as a graph of
+the training nodes of tante_amd/autograd.py (Im2colFn, LinearFn with K chunks, ActFn, DeconvFn / Col2imFn) and afno.PosRowsFn, with three
+nodes of this module: DpotFilterFn (forward the unchanged tante_dpot_filter, bit-identical to inference; backward tante_dpot_filter_bwd:
+the forward's launches 1 .. 3 again for X and U, then the chain in reverse against the conjugate-transposed tables, the block MLP against
+the conjugated transposed weights, one wave per 16 x 16 tile of a weight gradient), GroupNormFn (tante_groupnorm_bwd: statistics as the
+forward computes them, slab sums, a combine in order) and TimeAggFn (per-t GEMMs; the 'exp_mlp' fold's chain rule is parameter-sized
+float64 torch).  Every sum of the backward kernels has a fixed order and there are no atomics, so two runs give the same bits.  The input
+receives a gradient too, so `rollout_model` back-propagates through its re-fed frames and `train.train_step` works with
+`FlatAdamW(model.trained_parameters())` -- every parameter except cls_head.*, which never receives a gradient.  Under no_grad an opted-in
+model takes the unchanged inference path; train() changes nothing further (DPOT has no dropout).  n_spatial_dims = 3, act other than
+'gelu', mixing_type other than 'afno' and hidden_size_factor != 1 raise NotImplementedError with or without the opt-in; there is no CPU
+fallback."""
 from __future__ import annotations
 
 from typing import List, Optional, Tuple
@@ -27,6 +38,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd import Function
 
 from . import _lib as L
 from . import kernels as K
@@ -74,6 +86,23 @@ def pack_twiddles(H: int, W: int, modes: int) -> np.ndarray:
 def _twiddles(H: int, W: int, modes: int, device) -> torch.Tensor:
     return device_tables(("dpot", H, W) + kept_modes(H, W, modes), lambda: pack_twiddles(H, W, modes),
                          L.lib().tante_dpot_twiddle_floats(H, W, modes), f"twiddle tables for a {H} x {W} grid with {modes} modes", device)
+
+
+def pack_twiddles_bwd(H: int, W: int, modes: int) -> np.ndarray:
+    """-> the float32 buffer of adjoint tables tante_dpot_filter_bwd reads: the conjugate transposes T1^H (W, k2), T2^H (H, k1),
+    T3^H (k1, H), T4^H (k2, W) of the same float64 tables, rounded once and padded like pack_twiddles."""
+    return pack_tables([t.conj().T for t in twiddle_tables(H, W, modes)])
+
+
+def _twiddles_bwd(H: int, W: int, modes: int, device) -> torch.Tensor:
+    return device_tables(("dpot_bwd", H, W) + kept_modes(H, W, modes), lambda: pack_twiddles_bwd(H, W, modes),
+                         L.lib().tante_dpot_twiddle_bwd_floats(H, W, modes),
+                         f"adjoint twiddle tables for a {H} x {W} grid with {modes} modes", device)
+
+
+def groupnorm_bwd_supported_py(B: int, HW: int, C_: int, G: int) -> bool:
+    """Python mirror of tante_groupnorm_bwd_supported: the forward's shapes."""
+    return groupnorm_supported_py(B, HW, C_, G)
 
 
 def fold_time_weight(w: torch.Tensor, gamma: Optional[torch.Tensor]) -> torch.Tensor:
@@ -128,6 +157,235 @@ def dpot_filter(x: torch.Tensor, residual: Optional[torch.Tensor], w1: torch.Ten
     return out
 
 
+# ---- training: the mixer, GroupNorm and the time aggregation as autograd nodes ----------------------------------------------------------
+def groupnorm_bwd(dy: torch.Tensor, x: torch.Tensor, G: int, gamma: Optional[torch.Tensor], eps: float, dgamma: Optional[torch.Tensor] = None,
+                  dbeta: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """tante_groupnorm_bwd: dy (fp32 or bf16) and x (fp32), channels-last rows (B, ..., C) -> (dx fp32, dgamma, dbeta); with `accumulate`
+    the two parameter gradients are added onto the given buffers.  Without gamma there is no affine and no parameter gradient."""
+    K._dev(dy, x, gamma, dgamma, dbeta)
+    if x.dtype != torch.float32 or x.dim() < 2 or dy.shape != x.shape or dy.dtype not in K._DT:
+        raise RuntimeError("GroupNorm's backward takes fp32 channels-last rows (B, ..., C) and their gradient in fp32 or bf16")
+    B, C_ = x.shape[0], x.shape[-1]
+    HW = x.numel() // max(B * C_, 1)
+    lib = L.lib()
+    dx = torch.empty_like(x)
+    if gamma is not None and dgamma is None:
+        dgamma = torch.empty(C_, dtype=torch.float32, device=x.device)
+        dbeta = torch.empty(C_, dtype=torch.float32, device=x.device)
+        accumulate = False
+    nbytes = max(int(lib.tante_groupnorm_bwd_workspace_bytes(B, HW, C_, G)), 0)      # (-1: the call below refuses by name)
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    L.check(lib.tante_groupnorm_bwd(K._p(dy), K._DT[dy.dtype], K._p(x), B, HW, C_, G, float(eps), K._p(gamma), K._p(dx), K._p(dgamma), K._p(dbeta),
+                                    int(accumulate), K._p(work), nbytes, K._stream()), "tante_groupnorm_bwd")
+    return dx, dgamma, dbeta
+
+
+def dpot_filter_bwd(dout: torch.Tensor, x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, modes: int, grads=None,
+                    accumulate: bool = False):
+    """tante_dpot_filter_bwd: -> (dx, dw1, db1, dw2, db2) for dout, x (B, H, W, C) fp32; `grads`: the four buffers to write (or, with
+    `accumulate`, to add onto) in the state dict's layout."""
+    K._dev(dout, x, w1, b1, w2)
+    if x.dtype != torch.float32 or x.dim() != 4 or dout.dtype != torch.float32 or dout.shape != x.shape:
+        raise RuntimeError("the DPOT filter's backward takes fp32 channels-last rows (B, H, W, C) and their gradient")
+    B, H, W, C_ = x.shape
+    bs = w1.shape[2]
+    lib = L.lib()
+    if not lib.tante_dpot_filter_supported(B, H, W, C_, bs, modes, 1):
+        L.check(lib.tante_dpot_filter_bwd(None, None, B, H, W, C_, bs, modes, None, None, None, None, None, None, None, None, None, None, 0, None, 0,
+                                          None), "tante_dpot_filter_bwd")
+    if grads is None:
+        grads = [torch.empty(t.shape, dtype=torch.float32, device=x.device) for t in (w1, b1, w2, b1)]
+        accumulate = False
+    dx = torch.empty_like(x)
+    nbytes = int(lib.tante_dpot_filter_bwd_workspace_bytes(B, H, W, C_, bs, modes))
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    L.check(lib.tante_dpot_filter_bwd(K._p(dout), K._p(x), B, H, W, C_, bs, modes, K._p(_twiddles(H, W, modes, x.device)),
+                                      K._p(_twiddles_bwd(H, W, modes, x.device)), K._p(w1), K._p(b1), K._p(w2), K._p(dx), K._p(grads[0]),
+                                      K._p(grads[1]), K._p(grads[2]), K._p(grads[3]), int(accumulate), K._p(work), nbytes, K._stream()),
+            "tante_dpot_filter_bwd")
+    return (dx, *grads)
+
+
+def _slots(ctx, params, first: int):
+    """The parameters' gradient slots (autograd._grad_slot) where EVERY one of them exists and is wanted, else None."""
+    from .autograd import _grad_slot
+    slots = [_grad_slot(p) if ctx.needs_input_grad[first + i] else None for i, p in enumerate(params)]
+    return slots if all(s is not None for s in slots) else None
+
+
+class DpotFilterFn(Function):
+    """filter(x) (+ residual) on x (B, H, W, C) fp32 with the state dict's w1 / w2 (2, nb, bs, bs), b1 / b2 (2, nb, bs), read where the
+    parameters lie (no pack).  Forward: the unchanged tante_dpot_filter, bit-identical to inference; x is saved and the backward recomputes
+    the spectrum and the pre-activation from it.  Backward: tante_dpot_filter_bwd; the weight gradients go straight into the parameters'
+    gradient slots where all four exist (FlatAdamW), the residual's gradient is dout itself."""
+
+    @staticmethod
+    def forward(ctx, x, residual, w1, b1, w2, b2, modes):
+        x = x.contiguous()
+        residual = None if residual is None else residual.contiguous()
+        out = dpot_filter(x, residual, w1.detach(), b1.detach(), w2.detach(), b2.detach(), modes)
+        ctx.save_for_backward(x)
+        ctx.params, ctx.modes, ctx.has_res = (w1, b1, w2, b2), int(modes), residual is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (x,) = ctx.saved_tensors
+        w1, b1, w2, _ = ctx.params
+        dout = dout.contiguous()
+        slots = _slots(ctx, ctx.params, 2)
+        res = dpot_filter_bwd(dout, x, w1.detach(), b1.detach(), w2.detach(), ctx.modes, slots, slots is not None)
+        gs = [None] * 4 if slots is not None else [g if ctx.needs_input_grad[2 + i] else None for i, g in enumerate(res[1:])]
+        return (res[0], dout if ctx.has_res else None, *gs, None)
+
+
+class GroupNormFn(Function):
+    """GroupNorm(G, C) on channels-last fp32 rows x (B, ..., C), output in out_dtype: tante_groupnorm forward, tante_groupnorm_bwd backward
+    (dy in fp32 or bf16, dx fp32); the affine's gradients go into the parameters' gradient slots where both exist."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, G, eps, out_dtype):
+        x = x.contiguous()
+        y = groupnorm(x, G, None if gamma is None else gamma.detach(), None if beta is None else beta.detach(), eps, out_dtype)
+        ctx.save_for_backward(x)
+        ctx.params, ctx.G, ctx.eps = (gamma, beta), int(G), float(eps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        gamma, beta = ctx.params
+        dy = dy.contiguous()
+        if gamma is None:
+            return groupnorm_bwd(dy, x, ctx.G, None, ctx.eps)[0], None, None, None, None, None
+        slots = _slots(ctx, ctx.params, 1) if beta is not None else None
+        if slots is not None:
+            dx, _, _ = groupnorm_bwd(dy, x, ctx.G, gamma.detach(), ctx.eps, slots[0], slots[1], True)
+            return dx, None, None, None, None, None
+        dx, dg, db = groupnorm_bwd(dy, x, ctx.G, gamma.detach(), ctx.eps)
+        return dx, (dg if ctx.needs_input_grad[1] else None), (db if beta is not None and ctx.needs_input_grad[2] else None), None, None, None
+
+
+class TimeAggFn(Function):
+    """TimeAggregator.run on the strided ((b t) HW, C) rows.  Forward: the module's own per-t K-chunk GEMMs on the folded fp32 weights of
+    its pack cache (the values inference uses; the cache is keyed on the weight epoch and the parameters' versions, so the BPTT calls of a
+    step share one fold and an optimiser step rebuilds it).  Backward: the row gradient as per-t GEMMs against the same fold, the folded
+    weight's gradient through autograd.wgrad on the strided rows of every t, and -- parameter-sized, in float64 -- the chain rule of the
+    'exp_mlp' fold w[t, i, :] cos(t_t gamma_i) to w and gamma."""
+
+    @staticmethod
+    def forward(ctx, rows, w, gamma, agg, B, T, HW, compute):
+        rows = rows.contiguous()
+        out = agg.run(rows, B, T, HW, compute)
+        ctx.save_for_backward(rows)
+        ctx.agg, ctx.geo, ctx.params = agg, (B, T, HW, compute), (w, gamma)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from .autograd import _rm_linear, wgrad
+        (rows,) = ctx.saved_tensors
+        agg = ctx.agg
+        B, T, HW, compute = ctx.geo
+        w, gamma = ctx.params
+        C_ = agg.out_channels
+        dout = dout.contiguous()
+        M = B * HW
+        drows = dw = dgamma = None
+        if ctx.needs_input_grad[0]:
+            parts = [S.linear_chunks(dout, chunks) for chunks in agg._packed_bwd(compute)]        # dout wf[t]^T, (b HW, C) each
+            drows = torch.stack([p.view(B, HW, C_) for p in parts], dim=1).view(B * T * HW, C_)   # layout: the rows of (b, t)
+        if ctx.needs_input_grad[1] or (gamma is not None and ctx.needs_input_grad[2]):
+            # dwf[t][i][j] = sum over (b, HW) of rows_t[., i] dout[., j]: the gradient of the FOLDED weight
+            dwf = torch.stack([wgrad(_rm_linear(rows, HW, T * HW * C_, C_, t * HW * C_, cols=C_), _rm_linear(dout), M, C_, C_, (C_, C_), compute,
+                                     device=dout.device) for t in range(T)]).double()
+            if gamma is None:
+                dw = dwf.float()
+            else:
+                tt = torch.linspace(0, 1, T).double().to(dout.device)[:, None]                    # the reference's fp32 linspace
+                ang = tt * gamma.detach().double().reshape(1, -1)
+                dw = (dwf * torch.cos(ang)[:, :, None]).float()
+                dgamma = ((dwf * w.detach().double()).sum(dim=2) * (-torch.sin(ang) * tt)).sum(dim=0).reshape(gamma.shape).float()
+        return drows, dw, dgamma, None, None, None, None, None
+
+
+def _conv1x1(conv: nn.Conv2d) -> torch.Tensor:
+    """The (out, in) matrix of a 1 x 1 convolution: a view of the parameter."""
+    return conv.weight.view(conv.weight.shape[0], -1)
+
+
+def block_train(blk: "Block", x: torch.Tensor, compute: int) -> torch.Tensor:
+    """Block.run as a graph of training nodes: x (B, H, W, C) fp32 channels-last -> block(x)."""
+    from .autograd import ActFn, LinearFn
+    B, H, W, C_ = x.shape
+    M = B * H * W
+    adt = K.act_torch_dtype(compute)
+    f, fc1, fc2 = blk.filter, blk.mlp[0], blk.mlp[2]
+    n1 = GroupNormFn.apply(x, blk.norm1.weight, blk.norm1.bias, GROUPS, blk.norm1.eps, torch.float32)
+    x1 = DpotFilterFn.apply(n1, x if blk.double_skip else None, f.w1, f.b1, f.w2, f.b2, f.modes)
+    skip = x1 if blk.double_skip else x
+    n2 = GroupNormFn.apply(x1, blk.norm2.weight, blk.norm2.bias, GROUPS, blk.norm2.eps, adt)
+    h = ActFn.apply(LinearFn.apply(n2.view(M, C_), _conv1x1(fc1), fc1.bias, None, compute, adt), L.ACT_GELU_ERF, adt)
+    return LinearFn.apply(h, _conv1x1(fc2), fc2.bias, skip.reshape(M, C_), compute, torch.float32).view(B, H, W, C_)
+
+
+def patch_embed_train(pe: "PatchEmbed", img: torch.Tensor, compute: int, residual: Optional[torch.Tensor]) -> torch.Tensor:
+    """PatchEmbed.run as training nodes: img (n, h, w, cin) fp32 channels-last -> rows (n H' W', out_dim) fp32 (+ residual rows)."""
+    from .autograd import ActFn, Im2colFn, LinearFn
+    n, h, w, cin = img.shape
+    p = pe.patch_size[0]
+    c0, c2 = pe.proj[0], pe.proj[2]
+    adt = K.act_torch_dtype(compute)
+    cols = Im2colFn.apply(img, n, cin, h, w, p, p, 0, adt)                                    # columns (kh, kw, channel)
+    w0 = c0.weight.permute(0, 2, 3, 1).reshape(c0.weight.shape[0], -1).contiguous()           # the same order, a parameter-sized re-layout
+    h1 = ActFn.apply(LinearFn.apply(cols, w0, c0.bias, None, compute, adt), L.ACT_GELU_ERF, adt)
+    return LinearFn.apply(h1, _conv1x1(c2), c2.bias, residual, compute, torch.float32)
+
+
+def dpot_train_forward(model: "DPOT", x: torch.Tensor, compute: int) -> torch.Tensor:
+    """DPOT.forward with an autograd graph: x (b, t, c, h, w) -> (b, out_timesteps, c, h, w) fp32.  torch allocates, re-lays out (the
+    channels-last image with the constant coordinate channels beside the fields, the stacked per-t row gradients, the output's
+    channels-first view) and does parameter-sized work; every activation-sized operation is a HIP node."""
+    from .afno import PosRowsFn
+    from .autograd import ActFn, Col2imFn, DeconvFn, LinearFn
+    b, T, c, h, w = x.shape
+    p, C_ = model.patch_size, model.embed_dim
+    Hp, Wp = model.latent_size
+    HW = Hp * Wp
+    adt = K.act_torch_dtype(compute)
+    # the (b T, h, w, c + 3) image: the gradient reaches x through the concatenation (layout only; the coordinates are constants)
+    grid = model.get_grid_3d(T, x.device).permute(0, 2, 3, 1)
+    img = torch.cat([x.to(torch.float32).permute(0, 1, 3, 4, 2), grid[None].expand(b, -1, -1, -1, -1)], dim=4).reshape(b * T, h, w, c + 3)
+    pos = PosRowsFn.apply(model.pos_embed.permute(0, 2, 3, 1), b * T)                          # channels first -> rows (x, y, C) per image
+    rows = patch_embed_train(model.patch_embed, img, compute, pos)                             # ((b t) x y, C): x + pos_embed
+    agg = model.time_agg_layer
+    y = TimeAggFn.apply(rows, agg.w, agg.gamma if agg.type == "exp_mlp" else None, agg, b, T, HW, compute).view(b, Hp, Wp, C_)
+    for blk in model.blocks:
+        y = block_train(blk, y, compute)
+    d, a, z = model.out_layer[0], model.out_layer[2], model.out_layer[4]
+    od = model.out_layer_dim
+    if C_ <= S.KMAX:
+        pre = DeconvFn.apply(y.view(b * HW, C_), d.weight, d.bias, b, Hp, Wp, p, False, compute, adt)
+    else:       # the tap matrix (P P Cout, Cin), columns (kh, kw, co), K-chunked by LinearFn; the bias is added by the gather
+        taps = LinearFn.apply(y.view(b * HW, C_), d.weight.permute(2, 3, 1, 0).reshape(-1, C_).contiguous(), None, None, compute, torch.float32)
+        pre = Col2imFn.apply(taps, d.bias, b, Hp, Wp, p, p, 0, od, torch.float32)
+    img2 = ActFn.apply(pre, L.ACT_GELU_ERF, adt)
+    px = ActFn.apply(LinearFn.apply(img2.view(b * h * w, od), _conv1x1(a), a.bias, None, compute, adt), L.ACT_GELU_ERF, adt)
+    if od > S.KMAX:
+        raise NotImplementedError("out_layer_dim above 512 is out of scope: the last pixel-row linear writes channels first from one GEMM")
+    out = LinearFn.apply(px, _conv1x1(z), z.bias, None, compute, torch.float32)               # (b h w, (t c))
+    return out.view(b, h, w, model.out_timesteps, model.out_channels).permute(0, 3, 4, 1, 2)
+
+
+def _wants_graph(module: nn.Module, x: torch.Tensor) -> bool:
+    """True: build the autograd graph (opted in through set_trainable, grad enabled, something to differentiate).  A module that has not
+    opted in refuses as it always did; an opted-in one takes the inference path under no_grad, in train() as in eval() (no dropout)."""
+    if not module._trainable:
+        _inference_only(module)
+        return False
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
+
+
 # ---- the reference's modules -------------------------------------------------------------------------------------------------------
 def _gpu(x: torch.Tensor):
     if not x.is_cuda:
@@ -170,6 +428,13 @@ class AFNO2D(nn.Module):
         self.b1 = nn.Parameter(self.scale * torch.rand(2, num_blocks, bs * hidden_size_factor))
         self.w2 = nn.Parameter(self.scale * torch.rand(2, num_blocks, bs * hidden_size_factor, bs))
         self.b2 = nn.Parameter(self.scale * torch.rand(2, num_blocks, bs))
+        self._trainable = False
+
+    def set_trainable(self, flag: bool = True):
+        """Opt in to (or out of) training: under grad, forward then builds an autograd graph instead of refusing.  Not a constructor
+        argument and not part of the state_dict; propagates to the children and returns self."""
+        self._trainable = bool(flag)
+        return self
 
     def run(self, x: torch.Tensor, residual: Optional[torch.Tensor]) -> torch.Tensor:
         """x (B, H, W, C) fp32 channels-last -> filter(x) (+ residual); the weights are read where the parameters lie."""
@@ -177,11 +442,15 @@ class AFNO2D(nn.Module):
                            hidden_factor=self.hidden_size_factor)
 
     def forward(self, x: torch.Tensor, spatial_size=None) -> torch.Tensor:
-        """(B, H, W, C), or (B, C, H, W) with channel_first, -> the same layout  (dpot.py:47-102).  Inference only."""
-        _inference_only(self)
+        """(B, H, W, C), or (B, C, H, W) with channel_first, -> the same layout  (dpot.py:47-102).  Under grad only after set_trainable()."""
+        train = _wants_graph(self, x)
         if x.dim() != 4:
             raise NotImplementedError("the DPOT mixer is two-dimensional here: n_spatial_dims = 3 is out of scope")
         _gpu(x)
+        if train:
+            xl = x.to(torch.float32).permute(0, 2, 3, 1) if self.channel_first else x.to(torch.float32)
+            y = DpotFilterFn.apply(xl, None, self.w1, self.b1, self.w2, self.b2, self.modes)
+            return (y.permute(0, 3, 1, 2) if self.channel_first else y).to(x.dtype)
         xl = x.detach().to(torch.float32)
         if self.channel_first:
             xl = xl.permute(0, 2, 3, 1)
@@ -225,6 +494,14 @@ class Block(nn.Module):
                                  nn.Conv2d(in_channels=mlp_hidden_dim, out_channels=width, kernel_size=1, stride=1))
         self.double_skip = double_skip
         self._cache = _PackCache()
+        self._trainable = False
+
+    def set_trainable(self, flag: bool = True):
+        """Opt in to (or out of) training: under grad, forward then builds an autograd graph instead of refusing.  Not a constructor
+        argument and not part of the state_dict; propagates to the children and returns self."""
+        self._trainable = bool(flag)
+        self.filter.set_trainable(flag)
+        return self
 
     def _packed(self, compute: int):
         fc1, fc2 = self.mlp[0], self.mlp[2]
@@ -250,13 +527,15 @@ class Block(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(B, C, H, W) -> (B, C, H, W), as the reference's Block takes its images (GroupNorm and the 1 x 1 convs act on dim 1)."""
-        _inference_only(self)
+        train = _wants_graph(self, x)
         if x.dim() != 4:
             raise NotImplementedError("the DPOT block is two-dimensional here: n_spatial_dims = 3 is out of scope")
         if not self.filter.channel_first:
             raise NotImplementedError("Block(channel_first=False) hands its channel-first image to a channels-last filter in the reference; "
                                       "that mixes channels with rows and is not reproduced")
         _gpu(x)
+        if train:
+            return block_train(self, x.to(torch.float32).permute(0, 2, 3, 1), resolve_compute(None)).permute(0, 3, 1, 2).to(x.dtype)
         y = self.run(x.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous(), resolve_compute(None))
         return y.permute(0, 3, 1, 2).to(x.dtype)
 
@@ -277,6 +556,13 @@ class PatchEmbed(nn.Module):
         self.proj = nn.Sequential(nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size), self.act,
                                   nn.Conv2d(embed_dim, out_dim, kernel_size=1, stride=1))
         self._cache = _PackCache()
+        self._trainable = False
+
+    def set_trainable(self, flag: bool = True):
+        """Opt in to (or out of) training: under grad, forward then builds an autograd graph instead of refusing.  Not a constructor
+        argument and not part of the state_dict; propagates to the children and returns self."""
+        self._trainable = bool(flag)
+        return self
 
     def _packed(self, compute: int):
         c0, c2 = self.proj[0], self.proj[2]
@@ -295,12 +581,15 @@ class PatchEmbed(nn.Module):
         return S.linear_chunks(h1, c2, residual=residual)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """(B, C, H, W) -> (B, out_dim, H', W')  (dpot.py:193-197).  Inference only."""
-        _inference_only(self)
+        """(B, C, H, W) -> (B, out_dim, H', W')  (dpot.py:193-197).  Under grad only after set_trainable()."""
+        train = _wants_graph(self, x)
         _gpu(x)
         B, C_, H, W = x.shape
         assert H == self.img_size[0] and W == self.img_size[1], \
             f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
+        if train:
+            y = patch_embed_train(self, x.to(torch.float32).permute(0, 2, 3, 1), resolve_compute(None), None)
+            return y.view(B, self.out_size[0], self.out_size[1], self.out_dim).permute(0, 3, 1, 2).to(x.dtype)
         y = self.run(x.detach().to(torch.float32).contiguous(), resolve_compute(None), None)
         return y.view(B, self.out_size[0], self.out_size[1], self.out_dim).permute(0, 3, 1, 2).to(x.dtype)
 
@@ -320,6 +609,13 @@ class TimeAggregator(nn.Module):
         if type == "exp_mlp":
             self.gamma = nn.Parameter(2 ** torch.linspace(-10, 10, out_channels).unsqueeze(0))
         self._cache = _PackCache()
+        self._trainable = False
+
+    def set_trainable(self, flag: bool = True):
+        """Opt in to (or out of) training: under grad, forward then builds an autograd graph instead of refusing.  Not a constructor
+        argument and not part of the state_dict; propagates to the children and returns self."""
+        self._trainable = bool(flag)
+        return self
 
     def _packed(self, compute: int):
         gamma = self.gamma if self.type == "exp_mlp" else None
@@ -329,6 +625,17 @@ class TimeAggregator(nn.Module):
             wf = fold_time_weight(self.w, gamma)                           # (T, C_in, C_out)
             return [S.pack_linear_chunks(wf[t].t().contiguous(), None, compute) for t in range(wf.shape[0])]
         return self._cache.get(compute, params, build)
+
+    def _packed_bwd(self, compute: int):
+        """Per t the K-chunks of the row gradient's GEMM dout wf[t]^T, from the same fold; an entry of the same cache, so the weight epoch
+        and the parameters' versions rebuild it with the forward's."""
+        gamma = self.gamma if self.type == "exp_mlp" else None
+        params = [self.w] + ([gamma] if gamma is not None else [])
+
+        def build():
+            wf = fold_time_weight(self.w, gamma)                           # (T, C_in, C_out)
+            return [S.pack_linear_chunks(wf[t].contiguous(), None, compute) for t in range(wf.shape[0])]
+        return self._cache.get(("bwd", compute), params, build)
 
     def run(self, rows: torch.Tensor, B: int, T: int, HW: int, compute: int) -> torch.Tensor:
         """rows ((b t) HW, C) fp32 -> (b HW, C) fp32: the K-chunks of every t read their rows in place."""
@@ -346,10 +653,14 @@ class TimeAggregator(nn.Module):
         return out
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """(B, X, Y, T, C) -> (B, X, Y, C)  (dpot.py:213-221).  Inference only."""
-        _inference_only(self)
+        """(B, X, Y, T, C) -> (B, X, Y, C)  (dpot.py:213-221).  Under grad only after set_trainable()."""
+        train = _wants_graph(self, x)
         _gpu(x)
         B, X, Y, T, C_ = x.shape
+        if train:
+            rows = x.to(torch.float32).permute(0, 3, 1, 2, 4).reshape(B * T * X * Y, C_)
+            y = TimeAggFn.apply(rows, self.w, self.gamma if self.type == "exp_mlp" else None, self, B, T, X * Y, resolve_compute(None))
+            return y.view(B, X, Y, C_).to(x.dtype)
         rows = x.detach().to(torch.float32).permute(0, 3, 1, 2, 4).contiguous().view(B * T * X * Y, C_)
         return self.run(rows, B, T, X * Y, resolve_compute(None)).view(B, X, Y, C_).to(x.dtype)
 
@@ -404,6 +715,21 @@ class DPOT(nn.Module):
         self._cache = _PackCache()
         self._pos = _PackCache()
         self._stage = {}
+        self._trainable = False
+
+    def set_trainable(self, flag: bool = True):
+        """Opt in to (or out of) training: under grad, forward then builds an autograd graph instead of refusing.  Not a constructor
+        argument and not part of the state_dict; propagates to the children and returns self."""
+        self._trainable = bool(flag)
+        for m in (self.patch_embed, self.time_agg_layer, *self.blocks):
+            m.set_trainable(flag)
+        return self
+
+    def trained_parameters(self):
+        """Every parameter except cls_head.*: the reference computes cls_pred and discards it (dpot.py:343-344), so those weights never
+        receive a gradient and torch's AdamW never touches them.  FlatAdamW decays everything it is given: pass it THIS list, not
+        parameters()."""
+        return [p for n, p in self.named_parameters() if not n.startswith("cls_head.")]
 
     def set_compute(self, mode: Optional[str]):
         if mode is not None and mode not in K.COMPUTE:
@@ -445,8 +771,8 @@ class DPOT(nn.Module):
         return self._cache.get(compute, [d.weight, d.bias, a.weight, a.bias, z.weight, z.bias], build)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """x (b, t, c, h, w) -> (b, out_timesteps, c, h, w)   (dpot.py:323-350)."""
-        _inference_only(self)
+        """x (b, t, c, h, w) -> (b, out_timesteps, c, h, w)   (dpot.py:323-350).  Under grad only after set_trainable()."""
+        train = _wants_graph(self, x)
         if x.dim() != 5 or x.shape[1] != self.in_timesteps or x.shape[2] != self.in_channels:
             raise ValueError(f"expected (B, {self.in_timesteps}, {self.in_channels}, H, W), got {tuple(x.shape)}")
         _gpu(x)
@@ -454,6 +780,8 @@ class DPOT(nn.Module):
         if (h, w) != tuple(self.img_size):
             raise ValueError(f"Input image size ({h}*{w}) doesn't match model ({self.img_size[0]}*{self.img_size[1]}).")
         compute = resolve_compute(self.compute)
+        if train:
+            return dpot_train_forward(self, x, compute)
         adt = K.act_torch_dtype(compute)
         p, C_ = self.patch_size, self.embed_dim
         Hp, Wp = self.latent_size

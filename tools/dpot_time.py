@@ -8,8 +8,16 @@ distance from the same composition in fp32 is recorded beside it.
 
     python tools/dpot_time.py [--steps 10] [--out profiles/dpot_time.json]
 
-Writes both times, the spread of the regions, the launches per forward and the per-kernel split (torch.profiler, one forward)."""
+Writes both times, the spread of the regions, the launches per forward and the per-kernel split (torch.profiler, one forward).
+
+    python tools/dpot_time.py --train [--steps 5] [--out profiles/dpot_train_time.json]
+
+times one TRAIN step of the same config (B = 4, 8 x 8 tokens, bf16 compute): tante_amd.train_step on the opted-in model with
+FlatAdamW(model.trained_parameters()), against the same eager composition under autograd with clip_grad_norm_ and torch's fused AdamW on
+a copy of the weights -- the same scheme, and a per-kernel split of one step in which the mixer's and GroupNorm's backward kernels are
+listed by name."""
 import argparse
+import copy
 import json
 import os
 import sys
@@ -75,14 +83,104 @@ def eager_forward(m, x, grid):
     return o.view(b, h, w, m.out_timesteps, m.out_channels).permute(0, 3, 4, 1, 2)
 
 
+NEW_KERNELS = ("dpot_mlp_bwd_kernel", "dpot_wgrad_kernel", "gn_bwd_sums_kernel", "gn_bwd_apply_kernel", "gn_bwd_param_kernel", "DpotBwdEpilogue",
+               "gn_stats_kernel", "dpot_fwd_h_kernel", "dpot_inv_h_kernel", "dft_r2c_rows_kernel", "dpot_mlp_kernel")
+
+
+def step_profile(step):
+    """One profiled step: -> (launches, device us in all, the twelve heaviest kernels, the mixer's / GroupNorm's kernels by name -- the
+    new backward ones and the forward ones the backward runs again)."""
+    from torch.profiler import ProfilerActivity, profile
+    step()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        step()
+        torch.cuda.synchronize()
+    rows = [(e.key, e.count, float(getattr(e, "device_time_total", 0.0) or getattr(e, "cuda_time_total", 0.0))) for e in prof.key_averages()]
+    rows = sorted((r for r in rows if r[2] > 0.0), key=lambda r: -r[2])
+    fmt = lambda r: {"name": r[0][:96], "calls": r[1], "us": round(r[2], 1)}
+    return (sum(r[1] for r in rows), round(sum(r[2] for r in rows), 1), [fmt(r) for r in rows[:12]],
+            [fmt(r) for r in rows if any(k in r[0] for k in NEW_KERNELS)])
+
+
+def train_main(args, dev):
+    """The train step of configs/dpot_am.yaml: HIP (train_step, FlatAdamW) against eager torch under autograd, same scheme as main()."""
+    cfg = tante_amd.load_config(os.path.join(ROOT, "configs", "dpot_am.yaml"))
+    wl = cfg["workload"]
+    torch.manual_seed(cfg["seed"])
+    md = tante_amd.TanteMetadata(n_fields=wl["n_fields"], spatial_resolution=tuple(wl["spatial_resolution"]))
+    with torch.device(dev):
+        m = tante_amd.build_model(cfg, md)
+    m = m.to(dev).train().set_compute("bf16").set_trainable()
+    with torch.no_grad():       # as in main(): a default-init mixer adds 3e-4 of its input
+        for blk in m.blocks:
+            f = blk.filter
+            for wt in (f.w1, f.w2):
+                wt.copy_(torch.randn_like(wt) / f.block_size ** 0.5)
+            for bt in (f.b1, f.b2):
+                bt.copy_(0.3 * torch.randn_like(bt))
+    me = copy.deepcopy(m)           # the eager composition trains its own copy of the weights
+    B, T, res, nf = wl["batch_size"], cfg["model"]["in_T"], wl["spatial_resolution"], wl["n_fields"]
+    n_out = cfg["model"]["out_timesteps"]
+    batch = {"input": torch.randn(B, T, *res, nf, device=dev), "output": torch.randn(B, n_out, *res, nf, device=dev)}
+    fmt = tante_amd.DefaultChannelsFirstFormatter(md)
+    opt = tante_amd.FlatAdamW(m.trained_parameters(), lr=1e-5)
+    eparams = me.trained_parameters()
+    eopt = torch.optim.AdamW(eparams, lr=1e-5, weight_decay=1e-5, fused=True)
+    x = batch["input"].permute(0, 1, 4, 2, 3).contiguous()
+    grid = me.get_grid_3d(T, dev)
+
+    def hip_step():
+        return tante_amd.train_step(m, opt, batch, fmt, n_out)
+
+    def eager_step():
+        eopt.zero_grad(set_to_none=True)
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            y = eager_forward(me, x, grid)
+        loss = F.mse_loss(y.permute(0, 1, 3, 4, 2).float(), batch["output"])
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(eparams, 1.0)
+        eopt.step()
+        return loss.detach()
+
+    l_hip, l_eager = float(hip_step()), float(eager_step())         # the first step of each, from the same weights
+    torch.cuda.synchronize()
+    print(f"first losses: HIP {l_hip:.6f}, eager torch {l_eager:.6f}", flush=True)
+    if not abs(l_hip - l_eager) < 1e-2 * abs(l_eager) and not args.time_anyway:
+        raise SystemExit(f"the first losses disagree ({l_hip} vs {l_eager}): nothing timed")
+    hip = timed(hip_step, args.steps)
+    print("HIP timed", flush=True)
+    eager = timed(eager_step, args.steps)
+    print("eager timed", flush=True)
+    n_hip, us_hip, split_hip, new_hip = step_profile(hip_step)
+    n_eager, us_eager, split_eager, _ = step_profile(eager_step)
+    spread = max(hip["ms_max"] - hip["ms_min"], eager["ms_max"] - eager["ms_min"])
+    result = {"workload": {"config": "configs/dpot_am.yaml", "compute": "bf16", "batch": B, "in_T": T, "resolution": res, "n_fields": nf,
+                           "n_steps_output": n_out, "tokens": list(m.latent_size), "parameters": sum(p.numel() for p in m.parameters()),
+                           "trained_parameters": sum(p.numel() for p in m.trained_parameters())},
+              "device": torch.cuda.get_device_name(0), "first_loss": {"hip": l_hip, "eager_torch": l_eager},
+              "hip": hip, "eager_torch": eager, "speedup_median": round(eager["ms_median"] / hip["ms_median"], 3),
+              "hip_not_slower_beyond_spread": bool(hip["ms_median"] <= eager["ms_median"] + spread),
+              "launches_per_step": {"hip": n_hip, "eager_torch": n_eager}, "device_us_per_step": {"hip": us_hip, "eager_torch": us_eager},
+              "kernels_hip": split_hip, "mixer_and_groupnorm_kernels_hip": new_hip, "kernels_eager_torch": split_eager}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+    print(json.dumps({"hip_ms": hip["ms_median"], "eager_ms": eager["ms_median"], "launches": n_hip, "device_us": us_hip}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true", help="time the train step instead of the forward (default --out profiles/dpot_train_time.json)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 4])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dpot_time.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--time-anyway", action="store_true", help="time also when the two outputs miss the agreement bar (recorded as agree_under_bf16_bar: false)")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "dpot_train_time.json" if args.train else "dpot_time.json")
     dev = torch.device("cuda:0")
+    if args.train:
+        return train_main(args, dev)
     cfg = tante_amd.load_config(os.path.join(ROOT, "configs", "dpot_am.yaml"))
     wl = cfg["workload"]
     torch.manual_seed(cfg["seed"])
