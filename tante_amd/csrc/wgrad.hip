@@ -328,7 +328,8 @@ void launch_wgrad(const TanteRowMat& U, const TanteRowMat& V, long R, int I, int
   // workgroups per CU (0.7 TB/s); with the partials stored and summed by a second kernel (no 384-deep same-address atomics) the row
   // range is cut into up to 1 536 pieces of at least one chunk
   const int slab_target = tante_opt("TANTE_WGRAD_SLAB_WGS", 1536);
-  const bool slab_ok = ws != nullptr && ti == 1 && tj == 1 && slab_target > 0 && R >= 8 * RC;
+  // (a workspace that cannot hold two partials has nothing to reduce: the atomic form, and `split` below never reaches 0)
+  const bool slab_ok = ws != nullptr && ti == 1 && tj == 1 && slab_target > 0 && R >= 8 * RC && ws_bytes >= 2 * ((long)I * J + I) * 4;
   long split = (slab_ok ? slab_target : wg_target) / ((long)ti * tj);   // two workgroups per CU; fewer splits = less atomic traffic
   if (split < 1) split = 1;
   const long max_split = slab_ok ? (R + RC - 1) / RC : (R + 4 * RC - 1) / (4 * RC);
