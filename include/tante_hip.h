@@ -1176,7 +1176,9 @@ int tante_abi_version(void);
 /* Launch-heuristic overrides (workgroup counts, kernel-variant choices).  Every option switches between forms that compute the same
  * function; none changes a result beyond the summation order the variant implies.  Names start with "TANTE_" (e.g. "TANTE_FS_GROUPS":
  * 0 = automatic, 1 = unpaired, 2 = paired form of the fused block kernel; "TANTE_FS_WAVES" = 8 forces its 8-wave form;
- * "TANTE_WGRAD_WGS", "TANTE_GEMM_WGS", ... = grid sizes).  Process-wide, thread-safe; an option that was never set keeps the built-in
+ * "TANTE_FS_HALF8": 1 (default) runs the half-size inference launches of tante_block_fused -- 32-token workgroups, taken while the
+ * full-size grid fills at most a quarter of the resident slots -- on 8 waves, 0 on the 4 waves of the other launches; the rows are the
+ * same bit for bit; "TANTE_WGRAD_WGS", "TANTE_GEMM_WGS", ... = grid sizes).  Process-wide, thread-safe; an option that was never set keeps the built-in
  * default.  There is no counterpart in the reference (it has no native code to tune). */
 int tante_set_option(const char* name, int value);
 int tante_get_option(const char* name, int dflt);

@@ -822,7 +822,9 @@ extern "C" int tante_block_fused(float* x, const void* block_stream, int C, int 
   hipStream_t s = (hipStream_t)stream;
   const char* st = (const char*)block_stream;
   if (use_fs(C, n_head, hidden, seq->L, causal)) {
-    if (tante_fs_launch(x, st + block_ts_stream_bytes(C, hidden), *seq, causal, eps, s) != 0)
+    // the half-size launches run on 8 waves (the same rows bit for bit); every other shape, and TANTE_FS_HALF8 = 0, takes tante_fs_launch
+    const int half8 = tante_fs_half8_launch(x, st + block_ts_stream_bytes(C, hidden), *seq, causal, eps, s);
+    if (half8 < 0 || (half8 == 0 && tante_fs_launch(x, st + block_ts_stream_bytes(C, hidden), *seq, causal, eps, s) != 0))
       TANTE_FAIL(-2, "tante_block_fused: too many sequences (%d)", seq->nseq);
     TANTE_CHECK_LAUNCH();
     return 0;

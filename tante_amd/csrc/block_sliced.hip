@@ -161,18 +161,30 @@ constexpr int fs_group(int ntt, int nk) {
 // row stores, and with TPROP a quarter of the propagated-row stores.  Those rows are the full form's bit for bit (the arithmetic is the
 // same instruction stream).  The residual re-reads stay whole: skipping three rows in four made the loads lane-divergent branches and
 // the launch SLOWER (41.1 -> 45.5 us, cfg2 B = 8).
-template <int TPS, int NTT, int NW, bool TRAIN, int G = 1, bool TPROP = false, bool LASTQ = false>
+//
+// PAIR (inference, 8 waves on 2 tiles: fs_launch_half8 below): the rows of the 4-wave 2-tile form, bit for bit, from twice the
+// waves.  Waves 2 w and 2 w + 1 together own the 64 output features of 4-wave wave w in the same accumulator layout (row tiles 0, 1 and
+// 2, 3 of it), and every step of the block is per token row, per head or per output tile -- but LayerNorm2's statistics, which a wave
+// sums over ITS features in one sequential chain per lane.  So here the chain is the 4-wave one: wave 2 w runs it over its two row tiles
+// and hands the per-lane (s, q) of each token tile to wave 2 w + 1 through LDS (one more workgroup barrier), which continues the SAME
+// chain over its two row tiles, reduces over the rows and writes `stat` in the four-entry layout the final sum of the 4-wave form reads.
+template <int TPS, int NTT, int NW, bool TRAIN, int G = 1, bool TPROP = false, bool LASTQ = false, bool PAIR = false>
 __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
   static_assert(!TPROP || (TPS == 1 && !TRAIN), "the fused temporal propagator: T letter (L = 4), inference");
   static_assert(!LASTQ || (TPS == 1 && NW == 4 && G == 1 && !TRAIN), "the last-slot form: T letter (L = 4), 4 waves, inference");
   static_assert(G == 1 || (G == 2 && NW == 4), "the paired form is two 4-wave groups");
+  static_assert(!PAIR || (NW == 8 && NTT == 2 && G == 1 && !TRAIN && !TPROP && !LASTQ), "pair-chained statistics: 8 waves on 2 tiles, inference");
+  constexpr int SNW = PAIR ? NW / 2 : NW;      // entries per token of `stat`
   constexpr int RT = 16 / NW;            // 16-row output tiles per wave
   constexpr int HPW = RT / 2;            // heads per wave
   constexpr int FS_PF8 = 3, FS_PF4 = 2;      // 8-wave / 4-wave forms (4 waves at 3 k-steps spill: +5.5 us per launch)
   // weight k-steps in flight.  The register-heaviest instantiations (training forward at 4 token tiles, the element-masked any-L forms,
   // the 8-tile 8-wave forms) spilled 20 - 290 bytes per lane at the full depth: they run one k-step shallower (16 RT fewer registers)
   constexpr bool TIGHT = (NW == 4 && NTT == 4 && (TRAIN || TPS == 0)) || (NW == 8 && NTT == 8);
-  constexpr int PF = (NW == 8 ? FS_PF8 : FS_PF4) - (TIGHT ? 1 : 0);
+  // the PAIR form's own depth (110 registers at 3).  5 and 7 k-steps (130 / 146 registers, no scratch, same bits) ran 13.8 / 13.7 us per
+  // launch against 14.7 us at 3 in kernel traces of different visits; the rollout did not resolve them: not kept
+  constexpr int FS_PFH = 3;
+  constexpr int PF = PAIR ? FS_PFH : (NW == 8 ? FS_PF8 : FS_PF4) - (TIGHT ? 1 : 0);
   constexpr int IMG = 16 * NTT * FS_ROW;
   constexpr int LDS_G = 2 * IMG + 16 * NTT * NW * 8 + FS_BIAS_FLOATS * 4;      // bytes of LDS per group
   extern __shared__ __attribute__((aligned(16))) char smem_all[];
@@ -742,29 +754,64 @@ __global__ __launch_bounds__(64 * NW * G, 2) void block_fs_kernel(FsArgs A) {
     if (A.x1) slice_store(A.x1, x1);
   }
   FS_STAMP(10);
+  if constexpr (PAIR) {
+    // this wave's features of token tile tt into the per-lane chain (s, q): the loop of the other forms below
+    auto stat_chain = [&](int tt, float& s, float& q) {
 #pragma unroll
-  for (int tt = 0; tt < NTT; ++tt) {
-    float s = 0.f, q = 0.f;
+      for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
+        for (int r = 0; r < 4; ++r) {
+          s += x1[rt][tt][r];
+          q = fmaf(x1[rt][tt][r], x1[rt][tt][r], q);
+        }
+    };
+    // float2 [NW / 2 pairs][NTT tiles][64 lanes] behind the biases: the even wave's chain, taken up by its odd partner
+    float2* const hand = (float2*)(smem + LDS_G) + (wave >> 1) * (NTT * 64) + lane;
+    if ((wave & 1) == 0) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s += x1[rt][tt][r];
-        q = fmaf(x1[rt][tt][r], x1[rt][tt][r], q);
+      for (int tt = 0; tt < NTT; ++tt) {
+        float s = 0.f, q = 0.f;
+        stat_chain(tt, s, q);
+        hand[64 * tt] = make_float2(s, q);
       }
-    s = rows_sum(s);
-    q = rows_sum(q);
-    if (kk == 0) *(float2*)(stat + ((16 * tt + l15) * NW + wave) * 8) = make_float2(s, q);
+    }
+    __syncthreads();
+    if ((wave & 1) == 1) {
+#pragma unroll
+      for (int tt = 0; tt < NTT; ++tt) {
+        const float2 h = hand[64 * tt];
+        float s = h.x, q = h.y;
+        stat_chain(tt, s, q);
+        s = rows_sum(s);
+        q = rows_sum(q);
+        if (kk == 0) *(float2*)(stat + ((16 * tt + l15) * SNW + (wave >> 1)) * 8) = make_float2(s, q);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int tt = 0; tt < NTT; ++tt) {
+      float s = 0.f, q = 0.f;
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          s += x1[rt][tt][r];
+          q = fmaf(x1[rt][tt][r], x1[rt][tt][r], q);
+        }
+      s = rows_sum(s);
+      q = rows_sum(q);
+      if (kk == 0) *(float2*)(stat + ((16 * tt + l15) * NW + wave) * 8) = make_float2(s, q);
+    }
   }
   __syncthreads();
   FS_STAMP(11);
   // every wave normalises its own feature slice of every token with the full-row statistics, -> bufA (free since phase 1 ended)
 #pragma unroll
   for (int tt = 0; tt < NTT; ++tt) {
-    const f32x4* sp = (const f32x4*)(stat + (16 * tt + l15) * NW * 8);
+    const f32x4* sp = (const f32x4*)(stat + (16 * tt + l15) * SNW * 8);
     float s = 0.f, q = 0.f;
 #pragma unroll
-    for (int j = 0; j < NW / 2; ++j) {
+    for (int j = 0; j < SNW / 2; ++j) {
       const f32x4 a = sp[j];
       s += a[0] + a[2];
       q += a[1] + a[3];
@@ -972,6 +1019,15 @@ void fs_launch_tt(const FsArgs& A, int nwg, hipStream_t s) {
   attr.once([&] { (void)hipFuncSetAttribute((const void*)block_fs_kernel<TPS, NTT, NW, TRAIN, G, TPROP, LASTQ>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); });
   hipLaunchKernelGGL((block_fs_kernel<TPS, NTT, NW, TRAIN, G, TPROP, LASTQ>), dim3((nwg + G - 1) / G), dim3(64 * NW * G), LDS, s, A);
 }
+// the 2-tile launch on 8 waves with pair-chained LayerNorm2 statistics (PAIR): one 32-token workgroup per CU, two waves per SIMD; the
+// 8-wave images, statistics and biases, and behind them the pairs' hand-over, float2 [4 pairs][2 tiles][64 lanes]
+template <int TPS>
+void fs_launch_half8(const FsArgs& A, int nwg, hipStream_t s) {
+  constexpr int LDS = 2 * 16 * 2 * FS_ROW + 16 * 2 * 8 * 8 + FS_BIAS_FLOATS * 4 + 4 * 2 * 64 * 8;
+  static TantePerDevice attr;
+  attr.once([&] { (void)hipFuncSetAttribute((const void*)block_fs_kernel<TPS, 2, 8, false, 1, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); });
+  hipLaunchKernelGGL((block_fs_kernel<TPS, 2, 8, false, 1, false, false, true>), dim3(nwg), dim3(512), LDS, s, A);
+}
 // the last-slot form (LASTQ) at the geometries of the T letter's 4-wave launch: 4 tiles (three-quarter grids run the full size:
 // the form is per sequence, any geometry gives the same rows) or the half-size 2 tiles
 template <int NTT>
@@ -1040,6 +1096,39 @@ void tante_fs_pack_folded_multi(const float* const (*params)[8], char* const* ds
     B.dst[e] = dst[e];
   }
   hipLaunchKernelGGL(fs_pack_multi_kernel, dim3((unsigned)(n * FSP_BLOCKS)), dim3(256), 0, s, B);
+}
+
+// The half-size (2-tile) inference launches on 8 waves: fs_launch_half8 (PAIR), the rows of the 4-wave 2-tile form bit for bit from one
+// workgroup per CU with two waves per SIMD.  It serves exactly the plain launches (no training record, no propagator, not the last-slot
+// form) that the launch rule below sends to its half-size 4-wave instances: 4 waves (L <= 64, TANTE_FS_WAVES not 8), tile-aligned with
+// 32 % L == 0 (L | 16, or L = 32 non-causal), TANTE_FS_HALF on, and the full-size grid -- three tiles where the rule below would take
+// the three-quarter form, else four -- on at most a quarter of the 512 resident slots.  Returns 1 after a launch, 0 when the shape is
+// not one of these or TANTE_FS_HALF8 is 0 (the caller then takes the launch below: the 4-wave instance), < 0 as the launch below does.
+int tante_fs_half8_launch(float* x, const char* stream, const TanteSeq& sq, int causal, float eps, hipStream_t s) {
+  if (sq.nseq >= (1 << 23)) return -2;
+  const int L = sq.L;
+  if (sq.nseq < 1 || L < 1 || 32 % L != 0 || (L == 32 && causal) || fs_waves(L) != 4) return 0;
+  if (!tante_opt("TANTE_FS_HALF", 1) || !tante_opt("TANTE_FS_HALF8", 1)) return 0;
+  auto nwg_at = [&](int ntt) { return ((long)sq.nseq + 16 * ntt / L - 1) / (16 * ntt / L); };
+  auto rounds = [&](int ntt) { return ((nwg_at(ntt) + 511) / 512) * ntt; };
+  const int ntt_full = (L != 32 && rounds(3) < rounds(4)) ? 3 : 4;
+  if (nwg_at(ntt_full) * 4 > 512) return 0;
+  FsArgs A;
+  A.x = x; A.w = stream; A.sq = sq; A.causal = causal; A.eps = eps;
+  A.out = nullptr;
+  A.seed_mix = nullptr;
+  A.tprop = nullptr;
+  A.stamps = nullptr;
+#ifdef TANTE_ABLATE
+  A.stamps = g_fs_stamps;
+#endif
+  A.magic = (65536u + (unsigned)L - 1u) / (unsigned)L;
+  A.spw = 32 / L;
+  A.skew = 0;
+  const int nwg = (int)nwg_at(2);      // (at most 256: one workgroup per CU)
+  if (L == 32) fs_launch_half8<2>(A, nwg, s);
+  else fs_launch_half8<1>(A, nwg, s);
+  return 1;
 }
 
 int tante_fs_launch(float* x, const char* stream, const TanteSeq& sq, int causal, float eps, hipStream_t s, const TanteBlockTrain* tr,
