@@ -7,6 +7,7 @@ evaluates with torch so that their gradients come for free.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import NamedTuple, Optional
 
@@ -61,7 +62,7 @@ def _rm_patch(t: torch.Tensor, nhwc: bool, n_img: int, Hin: int, Win: int, Cin: 
     return m
 
 
-_AXIS_WS = {}
+_AXIS_WS = {}      # (device, stream) -> workspace: allocated once, reused by every pass
 
 
 def _axis_wgrad_workspace(device) -> torch.Tensor:
@@ -98,18 +99,13 @@ def _grad_slot(p) -> Optional[torch.Tensor]:
 # Measured on the cfg3 train step (alternating runs on one box): 29.5-29.9 ms against 30.0-30.1 ms on one stream, but with outliers at
 # 33-34.6 ms when the two streams' workgroups interleave badly -- a small, unreliable gain, so it is opt-in (TANTE_WGRAD_SIDE_STREAM=1).
 SIDE_STREAM_WGRAD = _O.register("TANTE_WGRAD_SIDE_STREAM", False, __name__, "SIDE_STREAM_WGRAD")
-_SIDE = {"stream": None, "armed": False, "task": -1}
-
-
-def _join_side():
-    _SIDE["armed"] = False
-    if _SIDE["stream"] is not None:
-        torch.cuda.current_stream().wait_stream(_SIDE["stream"])
+_SIDE_STREAM = None      # the side torch.cuda.Stream, created on first use: it outlives every pass (streams are not free to create)
 
 
 def join_side_stream():
     """Make the current stream wait for every weight-gradient kernel issued so far (before reading gradient slots)."""
-    _join_side()
+    if _SIDE_STREAM is not None:
+        torch.cuda.current_stream().wait_stream(_SIDE_STREAM)
 
 
 class _side_wgrad:
@@ -119,31 +115,25 @@ class _side_wgrad:
         self.tensors = tensors
 
     def __enter__(self):
+        global _SIDE_STREAM
         if not SIDE_STREAM_WGRAD:
             self.ctxm = None
             return self
-        if _SIDE["stream"] is None:
-            _SIDE["stream"] = torch.cuda.Stream()
-        side = _SIDE["stream"]
-        side.wait_stream(torch.cuda.current_stream())
+        if _SIDE_STREAM is None:
+            _SIDE_STREAM = torch.cuda.Stream()
+        _SIDE_STREAM.wait_stream(torch.cuda.current_stream())
         for t in self.tensors:
-            t.record_stream(side)
-        task = _graph_task()
-        if not _SIDE["armed"] or _SIDE["task"] != task:   # a callback queued by a backward pass that died is gone with it
-            _SIDE["armed"], _SIDE["task"] = True, task
-            try:
-                torch.autograd.Variable._execution_engine.queue_callback(_join_side)
-            except RuntimeError:      # not inside a backward pass
-                _SIDE["armed"] = False
-        self.ctxm = torch.cuda.stream(side)
+            t.record_stream(_SIDE_STREAM)
+        self.in_pass = _pass() is not None      # the pass's end-of-pass callback re-joins the main stream
+        self.ctxm = torch.cuda.stream(_SIDE_STREAM)
         self.ctxm.__enter__()
         return self
 
     def __exit__(self, *exc):
         if self.ctxm is not None:
             self.ctxm.__exit__(*exc)
-            if not _SIDE["armed"]:
-                _join_side()
+            if not self.in_pass:      # no pass is running: nothing would join later
+                join_side_stream()
         return False
 
 
@@ -154,55 +144,80 @@ class _side_wgrad:
 # needs its accumulators -- the uses of one weight run as ONE tante_wgrad_multi launch over the concatenated row range.  The recorded
 # operands stay alive a little longer (~3 GB at cfg3 on a 288 GB part).
 DEFER_WGRAD = _O.register("TANTE_WGRAD_DEFER", True, __name__, "DEFER_WGRAD")
-DEFER_MAX_GB = _O.register("TANTE_WGRAD_DEFER_MAX_GB", 32.0, __name__, "DEFER_MAX_GB")
-# (recorded operands held at most DEFER_MAX_GB GiB)
-_DEFER = {"pending": {}, "armed": False, "bytes": 0, "task": -1}
+DEFER_MAX_GB = _O.register("TANTE_WGRAD_DEFER_MAX_GB", 32.0, __name__, "DEFER_MAX_GB")      # (recorded operands held at most this many GiB)
+# id -> accumulator buffer of a FoldFn whose backward has not consumed (and thereby zeroed) it yet: they live on the weights across steps
+_FOLD_DIRTY = {}
 
 
-def _graph_task() -> int:
-    """Id of the backward pass (autograd graph task) this thread is executing, -1 outside one."""
-    return torch._C._current_graph_task_id()
+# ---- the state of ONE backward pass ------------------------------------------------------------------------------------------------------
+class BackwardPass:
+    """What the nodes of one autograd graph task share.  Created by the first node that asks (_pass), which queues the task's one engine
+    callback (_end_of_pass); dropped by that callback, by the flush it held back, by a later task's first node and by reset_backward_state."""
+
+    def __init__(self, task: int):
+        self.task = task
+        self.pending = {}         # (slot address, M, N, K, compute, layout) -> PendingWgrad: the recorded weight gradients
+        self.bytes = 0            # operands the recorded uses keep alive
+        self.deferred = False     # a deferred use was recorded in this pass: its FoldFn backwards may wait for the end too
+        self.folds = []           # PendingFold records
+        self.frames = {}          # id(frame encoding) -> the gradient accumulator the pass's FilmPosFramesFn nodes share (see its backward)
+        self.ended = False        # the pass is over and its flush is held back for the caller (backward_scope(hold=True))
 
 
-_FOLD_DIRTY = {}     # id -> accumulator buffer of a FoldFn whose backward has not consumed (and thereby zeroed) it yet
-
-# id(frame encoding) -> the gradient accumulator FilmPosFramesFn nodes of ONE backward pass share (see its backward)
-_FRAME_ACC = {"task": -1, "acc": {}}
+_PASS: Optional[BackwardPass] = None      # the record of the current (or, held, of the last) backward pass
+_SCOPE = (None, False)                    # (driver, hold) of the innermost backward_scope: what its caller wants from the passes inside it
 
 
-def _drop_frame_accumulators():
-    _FRAME_ACC["task"] = -1
-    _FRAME_ACC["acc"] = {}
+def _pass() -> Optional[BackwardPass]:
+    """The record of the backward pass this thread is executing, None outside one (nothing is recorded or shared then).  A record of
+    another task is discarded first, its operands and folds dropped, NOT launched: that pass raised (OOM, a kernel error,
+    KeyboardInterrupt -- its queued callback died with it) or was held and never flushed; consecutive passes get different task ids."""
+    global _PASS
+    task = torch._C._current_graph_task_id()      # the autograd graph task this thread is executing, -1 outside one
+    if task < 0:
+        return None
+    if _PASS is None or _PASS.task != task:
+        _PASS = None
+        try:
+            torch.autograd.Variable._execution_engine.queue_callback(_end_of_pass)
+        except RuntimeError:      # not inside a backward pass the engine runs callbacks for: nothing would end the record
+            return None
+        _PASS = BackwardPass(task)
+    return _PASS
+
+
+def _end_of_pass():
+    """The engine's end-of-pass callback, the only one a pass queues: join the side stream, flush (or hold) what was recorded, drop."""
+    global _PASS
+    p, (driver, hold) = _PASS, _SCOPE
+    if p is None:      # (reset_backward_state inside the pass)
+        return
+    join_side_stream()      # weight gradients issued on the side stream, when that option is on, are part of "final"
+    if p.deferred:
+        if hold:
+            p.ended = True
+        elif driver is not None:
+            driver()
+        else:
+            flush_run(1)
+    p.frames = {}
+    if not p.ended:
+        _PASS = None
 
 
 def _frame_accumulators():
-    """The table of the backward pass this thread is executing (created on its first use, dropped by an engine callback when the pass
-    ends and by reset_backward_state); None outside a backward pass: nothing is shared then, every node returns its own gradient."""
-    task = _graph_task()
-    if task < 0:
-        return None
-    if _FRAME_ACC["task"] != task:
-        _FRAME_ACC["task"], _FRAME_ACC["acc"] = task, {}
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(_drop_frame_accumulators)
-        except RuntimeError:
-            _drop_frame_accumulators()
-            return None
-    return _FRAME_ACC["acc"]
+    """The table of the backward pass this thread is executing; None outside one: then every node returns its own gradient."""
+    p = _pass()
+    return None if p is None else p.frames
 
 
 def reset_backward_state(after: bool = False):
-    """Forget everything recorded for a backward pass that is not running any more.  'armed' means "the engine's end-of-backward
-    callback of THIS backward pass is queued"; a backward pass that raises (OOM, a kernel error, KeyboardInterrupt) drops its
-    callbacks, so the flag is keyed to the graph task and additionally cleared here: train_step* call this before and -- in a
-    finally -- after every loss.backward(), so operands recorded by a dead pass can never reach a later step's gradient slots."""
-    _reset_recorded()
-    _FOLD_PENDING.clear()
-    _drop_frame_accumulators()
-    _SIDE["armed"] = False
-    _SIDE["task"] = -1
-    if _SIDE["stream"] is not None:
-        torch.cuda.current_stream().wait_stream(_SIDE["stream"])
+    """Forget everything recorded for a backward pass that is not running any more: a pass that raises drops its engine callback and
+    leaves its record behind.  _pass() discards it at the next pass's first use; backward_scope also calls this before and -- in a
+    finally -- after its passes, so what a dead pass recorded can never reach a later step's gradient slots.  The scope itself stays."""
+    global _PASS
+    _PASS = None
+    join_side_stream()
     if after and _FOLD_DIRTY:
         # fold accumulators live across steps and are zeroed by the fold's own backward kernel; whatever a dead (or partial) backward
         # pass left non-empty is cleared here, so the next step starts from zeros in every case
@@ -211,16 +226,28 @@ def reset_backward_state(after: bool = False):
         _FOLD_DIRTY.clear()
 
 
-def run_backward(loss: torch.Tensor):
-    """loss.backward() with the deferred / side-stream state guaranteed clean on entry and on ANY exit."""
+@contextlib.contextmanager
+def backward_scope(driver=None, hold: bool = False):
+    """The backward passes inside start from clean per-pass state, and leave it clean on ANY exit.  driver: a callable() that runs the
+    end-of-pass flush itself, called only in a pass that deferred something (train.py: flush_plan + flush_run around the all-reduce calls).
+    hold: the end of the pass leaves the recorded work to the caller's flush_plan / flush_steps (train.GraphedTrainStep).  Scopes nest."""
+    global _SCOPE
     reset_backward_state()
+    outer, _SCOPE = _SCOPE, (driver, hold)
     try:
-        loss.backward()
+        yield
     finally:
+        _SCOPE = outer
         reset_backward_state(after=True)
 
 
-_WG_WS = {}      # device index -> 64 MiB scratch of the shared weight-gradient launches (split-R partial tiles, summed by a second kernel)
+def run_backward(loss: torch.Tensor, driver=None):
+    """loss.backward() inside a backward_scope."""
+    with backward_scope(driver):
+        loss.backward()
+
+
+_WG_WS = {}      # device index -> 64 MiB scratch of the shared weight-gradient launches (split-R partial tiles, summed by a second kernel); kept across passes
 
 
 def _wgrad_workspace(device) -> torch.Tensor:
@@ -261,18 +288,6 @@ class PendingFold(NamedTuple):
     K: int
 
 
-_FOLD_PENDING = []      # PendingFold records of this backward pass
-HOLD_FLUSH = [False]         # True: the engine callback leaves the recorded work alone (train.GraphedTrainStep flushes in a graph of its own)
-FLUSH_DRIVER = [None]        # callable() that runs the end-of-pass flush itself (train.py: flush_plan + flush_run around the all-reduce calls)
-
-
-def _reset_recorded(armed: bool = False, task: int = -1):
-    """Drop the recorded weights; 'armed' / 'task': the engine's end-of-pass callback of that backward pass is queued."""
-    _DEFER["pending"].clear()
-    _DEFER["bytes"] = 0
-    _DEFER["armed"], _DEFER["task"] = armed, task
-
-
 def _wgrad_groups(entries, per_launch: Optional[int] = None):
     """Recorded weights -> the launch groups: consecutive ones in recording order (the four of a block sit next to each other), at most
     WGRAD_JOBS each; weights on different devices do not share a launch."""
@@ -307,8 +322,7 @@ def _launch_folds(folds):
     """FoldFn backwards as ONE launch (tante_fold_bwd_multi), after the weight-gradient launches that fill their accumulators."""
     if not folds:
         return
-    if _SIDE["stream"] is not None:      # the accumulators are written by weight-gradient kernels on the side stream
-        torch.cuda.current_stream().wait_stream(_SIDE["stream"])
+    join_side_stream()      # the accumulators are written by weight-gradient kernels on the side stream
     arr = (L.Fold * len(folds))()
     for f, p in zip(arr, folds):
         f.GW, f.Gb, f.W, f.gamma, f.beta = p.GW.data_ptr(), p.Gb.data_ptr(), p.W.data_ptr(), p.gamma.data_ptr(), p.beta.data_ptr()
@@ -319,15 +333,15 @@ def _launch_folds(folds):
         _FOLD_DIRTY.pop(id(p.acc_buf), None)      # the kernel left the accumulators zeroed
 
 
-def _flush_wgrads(slot: Optional[torch.Tensor] = None):
-    """A partial flush in the middle of a pass: the recorded uses of the weight whose accumulator is `slot`, each entry a launch of its
+def _flush_wgrads(p: BackwardPass, slot: Optional[torch.Tensor] = None):
+    """A partial flush in the middle of pass `p`: the recorded uses of the weight whose accumulator is `slot`, each entry a launch of its
     own -- or, without one, every recorded weight in the usual groups.  The folds and the queued end-of-pass callback stay as they are."""
-    pend = _DEFER["pending"]
+    pend = p.pending
     ents = [pend.pop(k) for k in [k for k in pend if slot is None or k[0] == slot.data_ptr()]]
     for grp in _wgrad_groups(ents, None if slot is None else 1):
         _launch_group(grp)
     if slot is None:
-        _DEFER["bytes"] = 0
+        p.bytes = 0
 
 
 # ---- the end-of-pass flush in SEGMENTS (round 6: the data-parallel all-reduce pipelined against it, dist.GradAllReduce) ------------------
@@ -336,10 +350,11 @@ def _flush_wgrads(slot: Optional[torch.Tensor] = None):
 # launch.  In segments, every fold runs right behind the launch group that fills its accumulator, so a block's whole span of the bucket is
 # final when its group is: the spans of the first segments travel while the later segments still compute.
 def _pending_groups():
-    groups = _wgrad_groups(list(_DEFER["pending"].values()))
+    p = _PASS or BackwardPass(-1)      # (whatever its task: a held record is flushed after its pass ended)
+    groups = _wgrad_groups(list(p.pending.values()))
     # fold f is ready behind the last group that writes its accumulator (group 0 when nothing pending writes it)
     ready = {}
-    for fi, f in enumerate(_FOLD_PENDING):
+    for fi, f in enumerate(p.folds):
         last = 0
         for gi, grp in enumerate(groups):
             if any(e.gW.data_ptr() == f.GW.data_ptr() for e in grp):
@@ -358,9 +373,10 @@ def flush_plan(bucket: torch.Tensor, segments: int):
     (first element, end element) ranges of `bucket`.  `early` = what no segment writes (final already); every element of the bucket is in
     exactly one list.  None when nothing is pending."""
     groups, ready = _pending_groups()
-    if not groups and not _FOLD_PENDING:
+    folds = _PASS.folds if _PASS else []
+    if not groups and not folds:
         return None
-    fold_acc = {f.GW.data_ptr() for f in _FOLD_PENDING}
+    fold_acc = {f.GW.data_ptr() for f in folds}
     base, esz, n = bucket.data_ptr(), bucket.element_size(), bucket.numel()
     owner = {}      # (lo, hi) -> the LAST segment that writes it
     bounds = _segment_bounds(len(groups), segments)
@@ -380,11 +396,11 @@ def flush_plan(bucket: torch.Tensor, segments: int):
                 add(e.gW, seg_of(gi))
                 add(e.gb, seg_of(gi))
         for fi in ready.get(gi, ()):
-            f = _FOLD_PENDING[fi]
+            f = folds[fi]
             for t in (f.dW, f.db, f.dgamma, f.dbeta):
                 add(t, seg_of(gi))
     if not groups:
-        for f in _FOLD_PENDING:
+        for f in folds:
             for t in (f.dW, f.db, f.dgamma, f.dbeta):
                 add(t, 0)
     n_seg = len(bounds) - 1
@@ -410,21 +426,22 @@ def flush_plan(bucket: torch.Tensor, segments: int):
 
 def flush_steps(segments: int):
     """Generator form of the flush: every next() launches one segment and yields its index.  One segment is the plain flush: every group,
-    then the folds as ONE launch; with more, each group is followed at once by the folds it completes.  The last segment also resets the
-    recorded state.  (train.GraphedTrainStep captures each next() as a graph.)"""
+    then the folds as ONE launch; with more, each group is followed at once by the folds it completes.  The last segment also drops the
+    record.  (train.GraphedTrainStep captures each next() as a graph.)"""
+    global _PASS
     groups, ready = _pending_groups()
+    folds = _PASS.folds if _PASS else []
     bounds = _segment_bounds(len(groups), segments)
     n_seg = len(bounds) - 1
     for s in range(n_seg):
         for gi in range(bounds[s], bounds[s + 1]):
             _launch_group(groups[gi])
             if n_seg > 1:
-                _launch_folds([_FOLD_PENDING[fi] for fi in ready.get(gi, ())])
+                _launch_folds([folds[fi] for fi in ready.get(gi, ())])
         if s == n_seg - 1:      # (before the yield: the caller may never come back)
-            _reset_recorded()
+            _PASS = None
             if n_seg == 1:
-                _launch_folds(list(_FOLD_PENDING))
-            _FOLD_PENDING.clear()
+                _launch_folds(folds)
         yield s
 
 
@@ -435,39 +452,23 @@ def flush_run(segments: int, on_segment=None):
             on_segment(s)
 
 
-def flush_deferred_wgrads(force: bool = False):
-    """Run every recorded weight-gradient launch now (called automatically at the end of a backward pass), then the folds that wait for them."""
-    if HOLD_FLUSH[0] and not force:
-        return
-    if FLUSH_DRIVER[0] is not None:
-        _join_side()                     # (weight gradients issued on the side stream, when that option is on, are part of "final")
-        FLUSH_DRIVER[0]()
-        return
-    flush_run(1)
-
-
 def _defer_wgrad(gW, gb, dy, a, M, N, Kk, comp, lay=(L.W_LINEAR, 0, 0, False)) -> bool:
     """Record one use (dW[N x Kk] += dy^T a over M dense bf16 rows; lay = (output layout, P, C_other, swap) as in tante_wgrad);
     False when this use has to run immediately (feature off, shape / dtype outside the shared-launch kernel)."""
     if not DEFER_WGRAD or comp != L.BF16 or dy.dtype != torch.bfloat16 or a.dtype != torch.bfloat16 or not _tr_shape(M, N, Kk):
         return False
-    task = _graph_task()
-    if not _DEFER["armed"] or _DEFER["task"] != task:
-        # first deferred use of THIS backward pass (a different graph task id means the pass that armed the flag is gone, and its
-        # queued callback with it: re-queue, and drop whatever it had recorded)
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(flush_deferred_wgrads)
-        except RuntimeError:          # not inside a backward pass: nothing would flush it
-            return False
-        _reset_recorded(True, task)   # leftovers of a backward pass that died half-way must not leak into this one
+    p = _pass()
+    if p is None:                     # not inside a backward pass: nothing would flush it
+        return False
+    p.deferred = True
     key = (gW.data_ptr(), M, N, Kk, comp, lay)
-    ent = _DEFER["pending"].get(key)
+    ent = p.pending.get(key)
     if ent is None:
-        ent = _DEFER["pending"][key] = PendingWgrad(gW, gb, M, N, Kk, comp, lay, [])
+        ent = p.pending[key] = PendingWgrad(gW, gb, M, N, Kk, comp, lay, [])
     ent.uses.append((dy, a))
-    _DEFER["bytes"] += dy.numel() * dy.element_size() + a.numel() * a.element_size()
-    if _DEFER["bytes"] > int(DEFER_MAX_GB * 2 ** 30):      # a very large model / batch: do not sit on more activations than this
-        _flush_wgrads()                  # (the engine callback stays queued for the rest of this backward pass)
+    p.bytes += dy.numel() * dy.element_size() + a.numel() * a.element_size()
+    if p.bytes > int(DEFER_MAX_GB * 2 ** 30):      # a very large model / batch: do not sit on more activations than this
+        _flush_wgrads(p)                 # (the engine callback stays queued for the rest of this backward pass)
     return True
 
 
@@ -555,17 +556,18 @@ class FoldFn(Function):
         W, gamma, beta = ctx.saved_tensors
         GW, Gb = ctx.acc
         N, Kk = W.shape
-        if gWe is None and gbe is None and Kk <= 256 and _DEFER["armed"] and _DEFER["task"] == _graph_task():
+        p = _pass()
+        if gWe is None and gbe is None and Kk <= 256 and p is not None and p.deferred:
             # the usual case on the train path: every use added into the accumulators (or is recorded to), nothing arrives through
             # autograd.  The fold joins the others of this backward pass: ONE launch after the recorded weight-gradient launches
-            # (flush_deferred_wgrads, the engine's end-of-pass callback that the recorded uses queued)
+            # (_end_of_pass, the engine's end-of-pass callback)
             slots = [_grad_slot(q) for q in ctx.params]
             if all(g is not None for g, q in zip(slots, ctx.params) if q is not None):
-                _FOLD_PENDING.append(PendingFold(ctx.acc_buf, GW, Gb, W, gamma, beta, *slots, N, Kk))
+                p.folds.append(PendingFold(ctx.acc_buf, GW, Gb, W, gamma, beta, *slots, N, Kk))
                 return None, None, None, None, None
-        _flush_wgrads(GW)                    # the recorded uses of this folded weight run now, as one launch
-        if _SIDE["stream"] is not None:      # the accumulators are written by weight-gradient kernels on the side stream
-            torch.cuda.current_stream().wait_stream(_SIDE["stream"])
+        if p is not None:
+            _flush_wgrads(p, GW)             # the recorded uses of this folded weight run now, as one launch
+        join_side_stream()                   # the accumulators are written by weight-gradient kernels on the side stream
         if gWe is not None:
             GW = GW + gWe
         if gbe is not None:
@@ -928,7 +930,7 @@ class ActFn(Function):
         return d, None, None
 
 
-_SEED = [0]
+_SEED = [0]      # ops seeded so far in this process: forward and backward of every step draw from one sequence
 
 
 def next_seed() -> int:

@@ -10,6 +10,7 @@ launch.  The clip therefore uses the norm of the AVERAGED gradient, exactly as a
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict
 
 import torch
@@ -56,11 +57,7 @@ def _backward_and_allreduce(loss, opt: FlatAdamW, world: int):
         early, segs = plan
         ar.ranges(early)
         A.flush_run(len(segs), on_segment=lambda sg: ar.ranges(segs[sg]) if sg + 1 < len(segs) else None)
-    A.FLUSH_DRIVER[0] = driver
-    try:
-        run_backward(loss)
-    finally:
-        A.FLUSH_DRIVER[0] = None
+    run_backward(loss, driver=driver)
     ar.finish()
     D.LAST_CALLS[:] = ar.calls
 
@@ -121,6 +118,7 @@ class GraphedTrainStep:
         TF.BLOCK_CALLS[0] = TF.BLOCK_CALLS[1] = 0
         A._SEED[0] = snap[4]            # the captured step draws the seeds an eager step would have drawn here
         ws_before = set(A._AXIS_WS)
+        held = contextlib.ExitStack()      # the split capture's backward_scope: entered inside the first graph, closed behind the last
         try:
             # thread-local capture mode: RCCL's proxy / watchdog threads of an initialised process group make HIP calls of their own,
             # which a global-mode capture would take for violations
@@ -129,12 +127,8 @@ class GraphedTrainStep:
                 y_pred, y_ref = rollout_model(model, self.batch, formatter, n_steps_output)
                 self.loss = MseMeanFn.apply(y_pred, y_ref)
                 if self.split:
-                    A.reset_backward_state()
-                    A.HOLD_FLUSH[0] = True          # the engine's end-of-pass callback leaves the recorded weight gradients alone
-                    try:
-                        self.loss.backward()
-                    finally:
-                        A.HOLD_FLUSH[0] = False
+                    held.enter_context(A.backward_scope(hold=True))      # the end of the pass leaves the recorded weight gradients alone
+                    self.loss.backward()
                 else:
                     run_backward(self.loss)
             if self.split:
@@ -150,13 +144,14 @@ class GraphedTrainStep:
                         next(gen)
                     self.graph2.append(g2)
                 next(gen, None)
-                A.reset_backward_state(after=True)
+                held.close()
             calls, fused = TF.BLOCK_CALLS
             if calls == 0 or fused != calls:
                 raise RuntimeError(f"GraphedTrainStep: {calls - fused} of {calls} block calls are not on the fused one-node path "
                                    "(their dropout seeds would be frozen in the graph)")
         except BaseException:
             self.close()            # the kernels must not keep reading a seed word that dies with this object
+            held.close()
             A.reset_backward_state(after=True)
             raise
         finally:

@@ -400,7 +400,7 @@ def _mlp_run(dev, monkeypatch, c, mode, fused_opt, route, routes, view=False, si
         torch.cuda.synchronize()
     assert {k: spy.n[k] for k in ROUTE_CALLS[route]} == ROUTE_CALLS[route], (route, spy.n)
     if side:
-        assert len(streams) == 2 and streams[0] == streams[1] == A._SIDE["stream"].cuda_stream != K._stream(), streams
+        assert len(streams) == 2 and streams[0] == streams[1] == A._SIDE_STREAM.cuda_stream != K._stream(), streams
     what = (f"AxisMlpFn ({c.outer},{c.n},{c.inner}) {mode} {route} {'/'.join(sorted(set(routes)))}" + (" view" if view else "")
             + (" side stream" if side else ""))
     by, bx, bp = mlp_bars(c, mode, route)

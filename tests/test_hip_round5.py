@@ -44,12 +44,9 @@ def _g14_grads(dev, monkeypatch, frame_film, n_loss_calls, passes=1):
     b = {k: v.to(dev) for k, v in batch.items()}
     y_pred, y_ref = tante_amd.rollout_model(m, b, fmt, 4)
     loss = A.MseMeanFn.apply(y_pred[:, :n_loss_calls].contiguous(), y_ref[:, :n_loss_calls].contiguous())
-    A.reset_backward_state()
-    try:
+    with A.backward_scope():
         for i in range(passes):
             loss.backward(retain_graph=i + 1 < passes)
-    finally:
-        A.reset_backward_state(after=True)
     return {k: p.grad.detach().clone() for k, p in m.named_parameters()}, names
 
 

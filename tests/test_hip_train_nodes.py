@@ -865,17 +865,12 @@ def _flush_graph_run(dev, spy, driver=None):
             terms.append(functional(y, d["G"][(i, u)].to(dev)))
     loss = torch.stack(terms).sum()
     before = dict(spy.n)
-    A.reset_backward_state()
-    A.FLUSH_DRIVER[0] = driver
-    try:
+    with A.backward_scope(driver=driver):
         loss.backward()
         torch.cuda.synchronize()
-        assert not A._DEFER["pending"] and not A._DEFER["armed"] and not A._FOLD_PENDING and not A._FOLD_DIRTY
+        assert A._PASS is None and not A._FOLD_DIRTY
         for i in FL_FOLDED:
             assert not bool(P[(i, "W")]._tante_fold_acc.any()), f"fold accumulator of weight {i} not left zeroed"
-    finally:
-        A.FLUSH_DRIVER[0] = None
-        A.reset_backward_state(after=True)
     return flat_g, {e: spy.n[e] - before[e] for e in spy.n}
 
 
@@ -894,7 +889,7 @@ def _flush_close(flat_g, tag):
 
 
 def test_flush_paths_agree(dev, monkeypatch):
-    """The same backward run by the engine callback alone, by a FLUSH_DRIVER that calls flush_run(1), by one that calls flush_run(2), and
+    """The same backward run by the engine callback alone, by a scope driver that calls flush_run(1), by one that calls flush_run(2), and
     with one weight per launch.  Recording order is the reverse of the forward's: groups (5, 4, 3, 2) and (1, 0), a fold behind each.
     * callback, flush_run(1), flush_run(2): 2 shared launches; the folds as one launch, one launch, two launches; on_segment(0), (1).
       The weight and bias slots are equal bit for bit (the shared launches sum their split-R partials in a fixed order, and the fold

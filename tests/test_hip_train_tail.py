@@ -389,13 +389,10 @@ def test_tail_second_backward_is_a_clear_error(dev, node):
     else:
         cfg = _cfg(1, 1, 1, 16, 4, [], enc, [], True)
         loss = A.EncTailFn.apply(randn((1, 4, 8, 128), gen).to(dev), cfg, *_enc_params(enc)).sum()
-    A.reset_backward_state()
-    try:
+    with A.backward_scope():
         loss.backward(retain_graph=True)
         with pytest.raises(RuntimeError, match=f"{node}: the fused training tail.*TANTE_TRAIN_FUSED_TAIL"):
             loss.backward()
-    finally:
-        A.reset_backward_state(after=True)
 
 
 # ---- TaylorFn alone (fp32) -----------------------------------------------------------------------------------------------------------

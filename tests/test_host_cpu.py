@@ -536,13 +536,13 @@ def test_flush_plan_partitions_the_bucket_by_launch_group():
             lo = (t.data_ptr() - base) // 4
             want[lo: lo + t.numel()] = seg_of_weight[i]
         return want
-    saved = dict(A._DEFER["pending"]), list(A._FOLD_PENDING), tante_amd.get_option("TANTE_WGRAD_JOBS_PER_LAUNCH")
+    saved = A._PASS, tante_amd.get_option("TANTE_WGRAD_JOBS_PER_LAUNCH")
     try:
-        A._DEFER["pending"].clear()
-        A._DEFER["pending"].update({(e.gW.data_ptr(), e.M, e.N, e.K, e.comp, e.lay): e for e in ents})
-        A._FOLD_PENDING[:] = folds
+        A._PASS = A.BackwardPass(-1)
+        A._PASS.pending.update({(e.gW.data_ptr(), e.M, e.N, e.K, e.comp, e.lay): e for e in ents})
+        A._PASS.folds[:] = folds
         tante_amd.set_option("TANTE_WGRAD_JOBS_PER_LAUNCH", 4)
-        groups = A._wgrad_groups(list(A._DEFER["pending"].values()))
+        groups = A._wgrad_groups(list(A._PASS.pending.values()))
         assert [len(g) for g in groups] == [4, 2] and [e for g in groups for e in g] == ents
         assert A._pending_groups() == (groups, {0: [0], 1: [1]})
         for segments, n_seg, seg_of_weight in [(1, 1, [0] * 6), (2, 2, [0, 0, 0, 0, 1, 1]), (3, 2, [0, 0, 0, 0, 1, 1])]:
@@ -551,17 +551,15 @@ def test_flush_plan_partitions_the_bucket_by_launch_group():
             assert torch.equal(owners(plan), expected(seg_of_weight)), segments
         assert A.flush_plan(bucket, 2)[1][1] == [(pos[0] - 2 * W - 4 * V, pos[0] - W - 2 * V), (pos[0] - W - V, pos[0])]      # fold 1's three, weight 5's two
         tante_amd.set_option("TANTE_WGRAD_JOBS_PER_LAUNCH", 1)
-        groups = A._wgrad_groups(list(A._DEFER["pending"].values()))
+        groups = A._wgrad_groups(list(A._PASS.pending.values()))
         assert groups == [[e] for e in ents]
         assert A._pending_groups()[1] == {1: [0], 4: [1]}
         plan = A.flush_plan(bucket, 3)
         assert len(plan[1]) == 3 and plan[0] == gaps
         assert torch.equal(owners(plan), expected([0, 0, 1, 1, 2, 2]))
     finally:
-        A._DEFER["pending"].clear()
-        A._DEFER["pending"].update(saved[0])
-        A._FOLD_PENDING[:] = saved[1]
-        tante_amd.set_option("TANTE_WGRAD_JOBS_PER_LAUNCH", saved[2])
+        A._PASS = saved[0]
+        tante_amd.set_option("TANTE_WGRAD_JOBS_PER_LAUNCH", saved[1])
 
 
 def _split_allreduce_worker(rank, world, port, q):
