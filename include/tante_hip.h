@@ -1089,6 +1089,26 @@ int tante_dwconv_ln(const float* x, int64_t n_img, int H, int W, int C, const fl
  * and its bias is never applied, as in the reference.  A row of zeros gives zeros. */
 int tante_l2norm_rows_supported(int64_t M, int C);
 int tante_l2norm_rows(const float* x, int64_t M, int C, float eps, void* y, int y_dtype, void* stream);
+/* The backward of both (convnext_bwd.hip; added without an ABI bump: nothing that existed changed), for training a model that opted in
+ * (UNetConvNext.set_trainable).  fp32 arithmetic, no atomics: every sum has a fixed order and two runs give the same bits.
+ * tante_dwconv_ln_bwd: what torch.autograd derives for norm(dwconv(x)) of Block.forward (unet_convnext.py:136-139) on x (n_img, H, W, C)
+ * fp32 with dy (n_img H W, C) fp32 or bf16 (dy_dtype), the gradient of what tante_dwconv_ln wrote.  Only x is kept by the forward:
+ * u = dwconv(x) + dw_b, mean, rstd and xh = (u - mean) rstd are recomputed by the forward's own code.  With g = dy ln_w (dy without
+ * the affine), per token
+ *   du = rstd (g - mean_c g - xh mean_c (g xh)),   dx[p] = sum_t dw_w[t] du[p - (t - 3)],   d_taps[c][t] = sum_p du[p] x[p + (t - 3)],
+ *   d_dwbias = sum_p du,   d_ln_w = sum_p dy xh,   d_ln_b = sum_p dy.
+ * dx fp32 (may alias neither dy nor x); d_taps (C, 49), d_dwbias, d_ln_w, d_ln_b (C) or NULL (d_ln_* only with ln_w); accumulate != 0
+ * adds onto what they hold.  Same served shapes and refusals as the forward.  work: _bwd_workspace_bytes(n_img, H, W, C) bytes,
+ * 16-byte aligned: du (n_img, H, W, C) and at most 512 partial rows per sum.
+ * tante_l2norm_rows_bwd: with r = ||x[m]||_2 and y = x / r:  r > eps: dx = (dy - y (y . dy)) / r;  r <= eps: dx = dy / eps (what
+ * autograd gives for x / x.norm().clamp_min(eps), rows of zeros included).  dy fp32 or bf16, x and dx fp32. */
+int tante_dwconv_ln_bwd_supported(int64_t n_img, int H, int W, int C);
+int64_t tante_dwconv_ln_bwd_workspace_bytes(int64_t n_img, int H, int W, int C);
+int tante_dwconv_ln_bwd(const void* dy, int dy_dtype, const float* x, int64_t n_img, int H, int W, int C, const float* dw_w, const float* dw_b,
+                        float eps, const float* ln_w, float* dx, float* d_taps, float* d_dwbias, float* d_ln_w, float* d_ln_b, int accumulate,
+                        void* work, int64_t work_bytes, void* stream);
+int tante_l2norm_rows_bwd_supported(int64_t M, int C);
+int tante_l2norm_rows_bwd(const void* dy, int dy_dtype, const float* x, int64_t M, int C, float eps, float* dx, void* stream);
 /* tante_conv3x3: Conv2d(Cin, Cout, kernel 3, padding 1) (unet_convnext.py:227-232), w (Cout, Cin, 3, 3), bias (Cout) or NULL, fp32
  * throughout; in_nchw / out_nchw choose (n, C, H, W) or (n, H, W, C) on either side.  Served: Cin <= 128, Cout <= 64. */
 int tante_conv3x3_supported(int64_t n_img, int Cin, int Cout, int H, int W);

@@ -308,6 +308,12 @@ SIGNATURES = {
     "tante_dwconv_ln": ([c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_vp], c_i32),
     "tante_l2norm_rows_supported": ([c_i64, c_i32], c_i32),
     "tante_l2norm_rows": ([c_vp, c_i64, c_i32, c_f32, c_vp, c_i32, c_vp], c_i32),
+    "tante_dwconv_ln_bwd_supported": ([c_i64, c_i32, c_i32, c_i32], c_i32),
+    "tante_dwconv_ln_bwd_workspace_bytes": ([c_i64, c_i32, c_i32, c_i32], c_i64),
+    "tante_dwconv_ln_bwd": ([c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64,
+                             c_vp], c_i32),
+    "tante_l2norm_rows_bwd_supported": ([c_i64, c_i32], c_i32),
+    "tante_l2norm_rows_bwd": ([c_vp, c_i32, c_vp, c_i64, c_i32, c_f32, c_vp, c_vp], c_i32),
     "tante_conv3x3_supported": ([c_i64, c_i32, c_i32, c_i32, c_i32], c_i32),
     "tante_conv3x3": ([c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp], c_i32),
     "tante_conv3x3_mfma_supported": ([c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32], c_i32),

@@ -9,8 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libtante_hip.so")
-SOURCES = ["gemm.hip", "attention.hip", "pointwise.hip", "block_fused.hip", "block_sliced.hip", "block_bwd.hip", "block_bwd_fs.hip", "train.hip", "backward.hip", "wgrad.hip", "head_fused.hip", "head_enc.hip", "operators.hip", "enc_fused.hip", "axis_bwd.hip", "spectral_dft.hip", "cvit_fused.hip", "axis_mfma.hip", "tail_chain.hip", "attn_flash.hip", "adaptive_tail.hip", "afno_filter.hip", "afno_filter_bwd.hip", "dpot_mixer.hip", "dpot_mixer_bwd.hip", "avit_ops.hip", "convnext.hip", "unet_att.hip", "uno_ops.hip"]
-HEADERS = [os.path.join(CSRC, "common.hip.h"), os.path.join(CSRC, "fused_common.hip.h"), os.path.join(CSRC, "fs_common.hip.h"), os.path.join(CSRC, "block_sliced.h"), os.path.join(CSRC, "spectral_dft.h"), os.path.join(CSRC, "dft_rows.hip.h"), os.path.join(CSRC, "afno_filter.hip.h"), os.path.join(CSRC, "dpot_mixer.hip.h"), os.path.join(os.path.dirname(HERE), "include", "tante_hip.h")]
+SOURCES = ["gemm.hip", "attention.hip", "pointwise.hip", "block_fused.hip", "block_sliced.hip", "block_bwd.hip", "block_bwd_fs.hip", "train.hip", "backward.hip", "wgrad.hip", "head_fused.hip", "head_enc.hip", "operators.hip", "enc_fused.hip", "axis_bwd.hip", "spectral_dft.hip", "cvit_fused.hip", "axis_mfma.hip", "tail_chain.hip", "attn_flash.hip", "adaptive_tail.hip", "afno_filter.hip", "afno_filter_bwd.hip", "dpot_mixer.hip", "dpot_mixer_bwd.hip", "avit_ops.hip", "convnext.hip", "convnext_bwd.hip", "unet_att.hip", "uno_ops.hip"]
+HEADERS = [os.path.join(CSRC, "common.hip.h"), os.path.join(CSRC, "fused_common.hip.h"), os.path.join(CSRC, "fs_common.hip.h"), os.path.join(CSRC, "block_sliced.h"), os.path.join(CSRC, "spectral_dft.h"), os.path.join(CSRC, "dft_rows.hip.h"), os.path.join(CSRC, "afno_filter.hip.h"), os.path.join(CSRC, "dpot_mixer.hip.h"), os.path.join(CSRC, "convnext_stages.hip.h"), os.path.join(os.path.dirname(HERE), "include", "tante_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast"]
 # the fused bf16 kernels are bound by VALU issue: without NaN-honouring every fmaxf / clamp loses its v_max canonicalisation

@@ -26,14 +26,26 @@ stored and never read (unet_convnext.py:274, 279: skips[-j] for j >= 1); `n_spat
 In bf16 mode bf16 is the GEMM operand type of the groups in BF16_SITES; the depthwise sum, every norm, the skip and the two edge
 convolutions stay fp32.
 
-Inference only (eval mode under no_grad).  Training, 3-D metadata, a wrong t * c and H or W not divisible by 2 ** stages raise; there is
-no CPU fallback."""
+Inference is the default: a model whose parameters require a gradient refuses under grad (and in train()), as it always did.  Training is
+opt-in through `model.set_trainable()` (also on Stage, Block, Upsample, Downsample and the channels-last LayerNorm; it propagates to the
+children).  An opted-in model called under grad takes convnext_train_forward: the same arithmetic as a graph of the training nodes of
+tante_amd/autograd.py (Im2colFn, LinearFn with K chunks, ActFn, DeconvFn / Col2imFn) with two nodes of this module: DwConvLnFn (forward
+the unchanged tante_dwconv_ln, bit-identical to inference; backward tante_dwconv_ln_bwd: the forward's two tile stages again from x, the
+three-term LayerNorm gradient, the flipped-tap correlation and the 49 tap sums per channel) and L2NormRowsFn (tante_l2norm_rows_bwd).
+Every training block is the MODULAR composition with the norm's affine applied by the kernel; the fused one-launch block stays inference
+only.  gamma and the channels-first norm's weight are folded as parameter-sized differentiable torch (float64, rounded once).  Every sum
+of the backward kernels has a fixed order and there are no atomics, so two runs give the same bits.  The input receives a gradient too,
+so `rollout_model` back-propagates through its re-fed frames and `train.train_step` works with `FlatAdamW(model.trained_parameters())`
+-- every parameter except *.resample.block.0.bias, which never receives a gradient.  Under no_grad an opted-in model takes the unchanged
+inference path; train() changes nothing further (drop_path is 0).  3-D metadata, drop_path > 0, a wrong t * c and H or W not divisible by
+2 ** stages raise with or without the opt-in; there is no CPU fallback."""
 from __future__ import annotations
 
 from typing import Optional
 
 import torch
 import torch.nn as nn
+from torch.autograd import Function
 
 from . import _lib as L
 from . import kernels as K
@@ -155,6 +167,243 @@ def l2norm_rows(x: torch.Tensor, eps: float, out_dtype: torch.dtype = torch.floa
     return out
 
 
+# ---- training: the two backward kernels, their autograd nodes, the graph ------------------------------------------------------------------
+def dwconv_ln_bwd_supported_py(n_img: int, H: int, W: int, C_: int) -> bool:
+    """Python mirror of tante_dwconv_ln_bwd_supported: the forward's shapes."""
+    return dwconv_ln_supported_py(n_img, H, W, C_)
+
+
+def l2norm_rows_bwd_supported_py(M: int, C_: int) -> bool:
+    """Python mirror of tante_l2norm_rows_bwd_supported: the forward's shapes."""
+    return l2norm_rows_supported_py(M, C_)
+
+
+def dwconv_ln_bwd(dy: torch.Tensor, x: torch.Tensor, dw_w: torch.Tensor, dw_b: torch.Tensor, eps: float, ln_w: Optional[torch.Tensor] = None,
+                  grads=None, accumulate: bool = False):
+    """tante_dwconv_ln_bwd: dy (n H W, C) fp32 or bf16, x (n, H, W, C) fp32, dw_w (C, 49) -> (dx, d_taps (C, 49), d_dwbias, d_ln_w, d_ln_b);
+    the last two None without ln_w.  `grads`: the four buffers to write (or, with `accumulate`, to add onto)."""
+    K._dev(dy, x, dw_w, dw_b, ln_w)
+    if x.dtype != torch.float32 or x.dim() != 4 or dy.dtype not in K._DT or dy.numel() != x.numel():
+        raise RuntimeError("the depthwise convolution's backward takes fp32 channels-last images (n, H, W, C) and their rows' gradient in "
+                           "fp32 or bf16")
+    n, H, W, C_ = x.shape
+    lib = L.lib()
+    if grads is None:
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=x.device)      # noqa: E731
+        grads = [new(C_, 49), new(C_), new(C_) if ln_w is not None else None, new(C_) if ln_w is not None else None]
+        accumulate = False
+    dx = torch.empty_like(x)
+    nbytes = max(int(lib.tante_dwconv_ln_bwd_workspace_bytes(n, H, W, C_)), 0)      # (-1: the call below refuses by name)
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    L.check(lib.tante_dwconv_ln_bwd(K._p(dy), K._DT[dy.dtype], K._p(x), n, H, W, C_, K._p(dw_w), K._p(dw_b), float(eps), K._p(ln_w), K._p(dx),
+                                    K._p(grads[0]), K._p(grads[1]), K._p(grads[2]), K._p(grads[3]), int(accumulate), K._p(work), nbytes, K._stream()),
+            "tante_dwconv_ln_bwd")
+    return (dx, *grads)
+
+
+def l2norm_rows_bwd(dy: torch.Tensor, x: torch.Tensor, eps: float) -> torch.Tensor:
+    """tante_l2norm_rows_bwd: dy (M, C) fp32 or bf16, x (M, C) fp32 -> dx fp32."""
+    K._dev(dy, x)
+    if x.dtype != torch.float32 or x.dim() != 2 or dy.dtype not in K._DT or dy.shape != x.shape:
+        raise RuntimeError("the row norm's backward takes fp32 rows (M, C) and their gradient in fp32 or bf16")
+    dx = torch.empty_like(x)
+    L.check(L.lib().tante_l2norm_rows_bwd(K._p(dy), K._DT[dy.dtype], K._p(x), x.shape[0], x.shape[1], float(eps), K._p(dx), K._stream()),
+            "tante_l2norm_rows_bwd")
+    return dx
+
+
+class DwConvLnFn(Function):
+    """LN(dwconv7x7(x) + dw_b) [* ln_w + ln_b] on x (n, H, W, C) fp32 -> rows (n H W, C) in out_dtype; dw_w is the Conv2d's (C, 1, 7, 7)
+    parameter, read where it lies.  Forward: the unchanged dwconv_ln, bit-identical to it; only x is saved.  Backward:
+    tante_dwconv_ln_bwd (dy fp32 or bf16, dx fp32); the parameter gradients go straight into the parameters' gradient slots where all of
+    them exist (FlatAdamW)."""
+
+    @staticmethod
+    def forward(ctx, x, dw_w, dw_b, ln_w, ln_b, eps, out_dtype):
+        x = x.contiguous()
+        C_ = x.shape[-1]
+        y = dwconv_ln(x, dw_w.detach().reshape(C_, 49), dw_b.detach(), eps, None if ln_w is None else ln_w.detach(),
+                      None if ln_b is None else ln_b.detach(), out_dtype)
+        ctx.save_for_backward(x)
+        ctx.params, ctx.eps = (dw_w, dw_b, ln_w, ln_b), float(eps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .dpot import _slots
+        (x,) = ctx.saved_tensors
+        dw_w, dw_b, ln_w, ln_b = ctx.params
+        C_ = x.shape[-1]
+        dy = dy.contiguous()
+        taps, lw = dw_w.detach().reshape(C_, 49), None if ln_w is None else ln_w.detach()
+        slots = _slots(ctx, ctx.params, 1) if (ln_w is not None and ln_b is not None) else None
+        if slots is not None:
+            dx = dwconv_ln_bwd(dy, x, taps, dw_b.detach(), ctx.eps, lw, [slots[0].view(C_, 49), *slots[1:]], True)[0]
+            return dx, None, None, None, None, None, None
+        dx, dt, db, dlw, dlb = dwconv_ln_bwd(dy, x, taps, dw_b.detach(), ctx.eps, lw)
+        want = ctx.needs_input_grad
+        return (dx, dt.view(dw_w.shape) if want[1] else None, db if want[2] else None, dlw if (ln_w is not None and want[3]) else None,
+                dlb if (ln_b is not None and want[4]) else None, None, None)
+
+
+class L2NormRowsFn(Function):
+    """x / max(||x||_2, eps) on rows (M, C) fp32 -> out_dtype: tante_l2norm_rows forward (bit-identical to l2norm_rows),
+    tante_l2norm_rows_bwd backward (dy fp32 or bf16, dx fp32)."""
+
+    @staticmethod
+    def forward(ctx, x, eps, out_dtype):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        ctx.eps = float(eps)
+        return l2norm_rows(x, eps, out_dtype)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return l2norm_rows_bwd(dy.contiguous(), x, ctx.eps), None, None
+
+
+def _fold32(expr64: torch.Tensor) -> torch.Tensor:
+    """A parameter-sized float64 expression rounded to fp32 once -- differentiable torch, so the fold's chain rule is torch's."""
+    return expr64.float().contiguous()
+
+
+def block_train(blk: "Block", x: torch.Tensor, compute: int) -> torch.Tensor:
+    """Block.run as a graph of training nodes, the MODULAR composition at every width: DwConvLnFn (the norm's affine applied by the
+    kernel, not folded, so that its backward returns d_ln_w / d_ln_b) -> LinearFn -> ActFn (erf GELU) -> LinearFn with the skip as the
+    residual operand and gamma folded into pwconv2 (float64, rounded once, as fold_block computes it).  The one-launch
+    tante_convnext_block stays inference only: its backward is not built."""
+    from .autograd import ActFn, LinearFn
+    compute = _site(compute, "block")
+    n, H, W, C_ = x.shape
+    if not dwconv_ln_supported_py(n, H, W, C_):
+        raise NotImplementedError(f"a block of {C_} channels is out of scope: tante_dwconv_ln serves 1..{DWLN_MAX_C}")
+    M = n * H * W
+    adt = K.act_torch_dtype(compute)
+    a = DwConvLnFn.apply(x, blk.dwconv.weight, blk.dwconv.bias, blk.norm.weight, blk.norm.bias, blk.norm.eps, adt)
+    h = ActFn.apply(LinearFn.apply(a, blk.pwconv1.weight, blk.pwconv1.bias, None, compute, adt), L.ACT_GELU_ERF, adt)
+    w2, b2 = blk.pwconv2.weight, blk.pwconv2.bias
+    if blk.gamma is not None:
+        g = blk.gamma.double()
+        w2, b2 = _fold32(w2.double() * g[:, None]), _fold32(b2.double() * g)
+    return LinearFn.apply(h, w2, b2, x.reshape(M, C_), compute, torch.float32).view(n, H, W, C_)
+
+
+def downsample_train(ds: "Downsample", x: torch.Tensor, compute: int) -> torch.Tensor:
+    """Downsample.run as training nodes: L2NormRowsFn -> Im2colFn (2 x 2 / 2) -> LinearFn on the weight with the norm's weight folded in."""
+    from .autograd import Im2colFn, LinearFn
+    compute = _site(compute, "resample")
+    n, H, W, C_ = x.shape
+    if H % 2 or W % 2:
+        raise ValueError(f"the 2 x 2 / 2 convolution takes even H and W, got {H} x {W}")
+    norm, conv = ds.block[0], ds.block[1]
+    adt = K.act_torch_dtype(compute)
+    rows = L2NormRowsFn.apply(x.reshape(n * H * W, C_), norm.eps, adt)
+    cols = Im2colFn.apply(rows.view(n, H, W, C_), n, C_, H, W, 2, 2, 0, adt)                   # columns (kh, kw, channel)
+    wf = conv.weight.double() * norm.weight.double().reshape(1, -1, 1, 1)
+    w = _fold32(wf.permute(0, 2, 3, 1).reshape(conv.weight.shape[0], -1))                       # the same order
+    return LinearFn.apply(cols, w, conv.bias, None, compute, torch.float32).view(n, H // 2, W // 2, -1)
+
+
+def upsample_train(us: "Upsample", x: torch.Tensor, compute: int) -> torch.Tensor:
+    """Upsample.run as training nodes: L2NormRowsFn -> DeconvFn, or LinearFn (tap matrix) + Col2imFn past 512 input channels, on the
+    weight with the norm's weight folded into its rows."""
+    from .autograd import Col2imFn, DeconvFn, LinearFn
+    compute = _site(compute, "resample")
+    n, H, W, C_ = x.shape
+    norm, dec = us.block[0], us.block[1]
+    cout = dec.weight.shape[1]
+    adt = K.act_torch_dtype(compute)
+    rows = L2NormRowsFn.apply(x.reshape(n * H * W, C_), norm.eps, adt)
+    wf = dec.weight.double() * norm.weight.double().reshape(-1, 1, 1, 1)                        # (Cin, Cout, 2, 2)
+    if C_ <= S.KMAX:
+        return DeconvFn.apply(rows, _fold32(wf), dec.bias, n, H, W, 2, False, compute, torch.float32)
+    taps = LinearFn.apply(rows, _fold32(wf.permute(2, 3, 1, 0).reshape(-1, C_)), None, None, compute, torch.float32)
+    return Col2imFn.apply(taps, dec.bias, n, H, W, 2, 2, 0, cout, torch.float32)
+
+
+def stage_train(st: "Stage", x: torch.Tensor, compute: int, skip: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Stage.run as training nodes; skip_proj(cat([x, skip])) is two LinearFn calls through the residual operand: the concatenated tensor
+    is never written, forward or backward."""
+    from .autograd import LinearFn
+    if isinstance(st.skip_proj, nn.Identity):
+        if skip is not None:
+            raise ValueError("this stage has no skip projection")
+    else:
+        if skip is None:
+            raise ValueError("a stage with skip_proj takes the skip")
+        if tuple(skip.shape) != tuple(x.shape):
+            raise ValueError(f"the skip must have the stream's shape {tuple(x.shape)}, got {tuple(skip.shape)}")
+        cs = _site(compute, "skip")
+        n, H, W, C_ = x.shape
+        sp = st.skip_proj
+        w = sp.weight.view(C_, 2 * C_)
+        adt = K.act_torch_dtype(cs)
+        xa, sa = x.reshape(n * H * W, C_), skip.reshape(n * H * W, C_)
+        if adt != torch.float32:                                                             # the GEMM's operand type, rounded by a HIP node
+            from .autograd import ActFn
+            xa, sa = ActFn.apply(xa, L.ACT_NONE, adt), ActFn.apply(sa, L.ACT_NONE, adt)
+        out = LinearFn.apply(xa, w[:, :C_].contiguous(), sp.bias, None, cs, torch.float32)
+        x = LinearFn.apply(sa, w[:, C_:].contiguous(), None, out, cs, torch.float32).view(n, H, W, C_)
+    for blk in st.blocks:
+        x = block_train(blk, x, compute)
+    if isinstance(st.resample, Downsample):
+        x = downsample_train(st.resample, x, compute)
+    elif isinstance(st.resample, Upsample):
+        x = upsample_train(st.resample, x, compute)
+    return x
+
+
+def _conv3x3_train(x: torch.Tensor, conv: nn.Conv2d) -> torch.Tensor:
+    """An edge convolution as training nodes, fp32 in both modes: x (n, H, W, Cin) channels-last -> (n, H, W, Cout): Im2colFn (3 x 3, pad 1)
+    + LinearFn (K chunks past 512)."""
+    from .autograd import Im2colFn, LinearFn
+    n, H, W, Cin = x.shape
+    cols = Im2colFn.apply(x, n, Cin, H, W, 3, 1, 1, torch.float32)                             # columns (kh, kw, channel)
+    w = conv.weight.permute(0, 2, 3, 1).reshape(conv.weight.shape[0], -1).contiguous()          # the same order, parameter-sized
+    return LinearFn.apply(cols, w, conv.bias, None, L.F32, torch.float32).view(n, H, W, -1)
+
+
+def convnext_train_forward(model: "UNetConvNext", x: torch.Tensor, compute: int) -> torch.Tensor:
+    """UNetConvNext.forward with an autograd graph: x (b, t, c, h, w) -> (b, 1, c, h, w) fp32.  torch allocates, re-lays out (the input to
+    channels-last, the output back: layout only) and does parameter-sized work (the folds); every other activation-sized operation is a
+    HIP node."""
+    b, t, c, h, w = x.shape
+    cur = _conv3x3_train(x.to(torch.float32).reshape(b, t * c, h, w).permute(0, 2, 3, 1), model.in_proj)
+    skips = []
+    for enc in model.encoder:
+        skips.append(cur)                                                   # skips[0] is stored and never read, as in the reference
+        cur = stage_train(enc, cur, compute)
+    cur = stage_train(model.neck, cur, compute)
+    for j, dec in enumerate(model.decoder):
+        cur = stage_train(dec, cur, compute, skips[-j] if j > 0 else None)
+    y = _conv3x3_train(cur, model.out_proj)
+    return y.permute(0, 3, 1, 2).reshape(b, 1, model.dim_out, h, w)
+
+
+def _wants_graph(module: nn.Module, x: torch.Tensor) -> bool:
+    """True: build the autograd graph (opted in through set_trainable, grad enabled, something to differentiate).  A module that has not
+    opted in refuses as it always did; an opted-in one takes the inference path under no_grad, in train() as in eval() (drop_path is 0)."""
+    if not getattr(module, "_trainable", False):
+        _inference_only(module)
+        return False
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
+
+
+class _Trainable:
+    """set_trainable for the modules of this file: the flag on the module and on every child that has one."""
+
+    _trainable = False
+
+    def set_trainable(self, flag: bool = True):
+        """Opt in to (or out of) training: under grad, forward then builds an autograd graph instead of refusing.  Not a constructor
+        argument and not part of the state_dict; propagates to the children and returns self."""
+        for m in self.modules():
+            if isinstance(m, _Trainable):
+                m._trainable = bool(flag)
+        return self
+
+
 def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], in_nchw: bool, out_nchw: bool) -> torch.Tensor:
     """tante_conv3x3: x (n, Cin, H, W) or (n, H, W, Cin) fp32 -> (n, Cout, H, W) or (n, H, W, Cout) fp32."""
     weight = weight.detach()
@@ -213,7 +462,7 @@ def _to_nchw(y: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
     return y.permute(0, 3, 1, 2).contiguous().to(like.dtype)
 
 
-class LayerNorm(nn.Module):
+class LayerNorm(_Trainable, nn.Module):
     """unet_convnext.py:39-70.  channels_last: a LayerNorm over the last axis.  channels_first: NOT a LayerNorm but
     F.normalize(x, p=2, dim=1, eps) * weight; `bias` is held and never applied.  A parameter holder: its owner folds the affine into the
     GEMM behind it; forward evaluates it alone."""
@@ -234,20 +483,26 @@ class LayerNorm(nn.Module):
         self.normalized_shape = (normalized_shape,)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """Inference only.  channels_last (..., C) -> (..., C); channels_first is evaluated by Downsample / Upsample."""
-        _inference_only(self)
+        """channels_last (..., C) -> (..., C); channels_first is evaluated by Downsample / Upsample.  Under grad only after set_trainable()."""
+        train = _wants_graph(self, x)
         if self.data_format != "channels_last":
             raise NotImplementedError("the channels_first norm is evaluated by its Downsample / Upsample (tante_l2norm_rows, weight folded "
                                       "into the convolution)")
         _gpu(x)
+        if train:
+            from .autograd import LayerNormAffineFn
+            return LayerNormAffineFn.apply(x.to(torch.float32), self.weight, self.bias, self.eps).to(x.dtype)
         return K.layernorm_affine(x.detach().to(torch.float32), self.weight.detach(), self.bias.detach(), self.eps).to(x.dtype)
 
 
-class _Resample(nn.Module):
+class _Resample(_Trainable, nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """(n, C, H, W) -> (n, C', H', W').  Inference only."""
-        _inference_only(self)
+        """(n, C, H, W) -> (n, C', H', W').  Under grad only after set_trainable()."""
+        train = _wants_graph(self, x)
         _gpu(x)
+        if train:
+            fn = downsample_train if isinstance(self, Downsample) else upsample_train
+            return fn(self, x.to(torch.float32).permute(0, 2, 3, 1), resolve_compute(None)).permute(0, 3, 1, 2).to(x.dtype)
         return _to_nchw(self.run(_to_nhwc(x), resolve_compute(None)), x)
 
 
@@ -315,7 +570,7 @@ class Downsample(_Resample):
         return y.view(n, H // 2, W // 2, -1)
 
 
-class Block(nn.Module):
+class Block(_Trainable, nn.Module):
     """dwconv 7 x 7 -> LayerNorm -> Linear C -> 4 C -> GELU -> Linear 4 C -> C -> gamma -> + input  (unet_convnext.py:103-148)."""
 
     def __init__(self, dim, n_spatial_dims, drop_path=0.0, layer_scale_init_value=1e-6):
@@ -373,13 +628,15 @@ class Block(nn.Module):
         return out
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """(n, C, H, W) -> (n, C, H, W)  (unet_convnext.py:134-148).  Inference only."""
-        _inference_only(self)
+        """(n, C, H, W) -> (n, C, H, W)  (unet_convnext.py:134-148).  Under grad only after set_trainable(), and then by block_train."""
+        train = _wants_graph(self, x)
         _gpu(x)
+        if train:
+            return block_train(self, x.to(torch.float32).permute(0, 2, 3, 1).contiguous(), resolve_compute(None)).permute(0, 3, 1, 2).to(x.dtype)
         return _to_nchw(self.run(_to_nhwc(x), resolve_compute(None)), x)
 
 
-class Stage(nn.Module):
+class Stage(_Trainable, nn.Module):
     """skip_proj -> blocks -> resample  (unet_convnext.py:151-199)."""
 
     def __init__(self, dim_in, dim_out, n_spatial_dims, depth=1, drop_path=0.0, layer_scale_init_value=1e-6, mode="down", skip_project=False):
@@ -436,17 +693,24 @@ class Stage(nn.Module):
         return x
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """(n, C, H, W), or (n, 2 C, H, W) = cat([x, skip]) for a stage with skip_proj -> the stage's output, channels first.  Inference only."""
-        _inference_only(self)
+        """(n, C, H, W), or (n, 2 C, H, W) = cat([x, skip]) for a stage with skip_proj -> the stage's output, channels first.  Under grad only
+        after set_trainable()."""
+        train = _wants_graph(self, x)
         _gpu(x)
         compute = resolve_compute(None)
+        if train:
+            xl = x.to(torch.float32).permute(0, 2, 3, 1)
+            if isinstance(self.skip_proj, nn.Identity):
+                return stage_train(self, xl.contiguous(), compute).permute(0, 3, 1, 2).to(x.dtype)
+            C_ = self.skip_proj.weight.shape[0]
+            return stage_train(self, xl[..., :C_].contiguous(), compute, xl[..., C_:].contiguous()).permute(0, 3, 1, 2).to(x.dtype)
         if isinstance(self.skip_proj, nn.Identity):
             return _to_nchw(self.run(_to_nhwc(x), compute), x)
         C_ = self.skip_proj.weight.shape[0]
         return _to_nchw(self.run(_to_nhwc(x[:, :C_]), compute, _to_nhwc(x[:, C_:])), x)
 
 
-class UNetConvNext(nn.Module):
+class UNetConvNext(_Trainable, nn.Module):
     """models/unet_convnext.py:202-283 -- same constructor, attributes, parameters and forward contract."""
 
     def __init__(self, in_T, dset_metadata, stages: int = 4, blocks_per_stage: int = 1, blocks_at_neck: int = 1, n_spatial_dims: int = 2,
@@ -477,6 +741,12 @@ class UNetConvNext(nn.Module):
         self.compute: Optional[str] = None
         self._cache = _PackCache()
 
+    def trained_parameters(self):
+        """Every parameter except *.resample.block.0.bias: the channels_first norm's bias, which the reference holds and never applies
+        (unet_convnext.py:69), so it never receives a gradient and torch's AdamW never touches it.  FlatAdamW decays everything it is
+        given: pass it THIS list, not parameters()."""
+        return [p for n, p in self.named_parameters() if not n.endswith("resample.block.0.bias")]
+
     def set_compute(self, mode: Optional[str]):
         if mode is not None and mode not in K.COMPUTE:
             raise ValueError("compute must be None, 'fp32' or 'bf16'")
@@ -484,8 +754,8 @@ class UNetConvNext(nn.Module):
         return self
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """x (b, t, c, h, w) -> (b, 1, c, h, w)   (unet_convnext.py:269-283)."""
-        _inference_only(self)
+        """x (b, t, c, h, w) -> (b, 1, c, h, w)   (unet_convnext.py:269-283).  Under grad only after set_trainable()."""
+        train = _wants_graph(self, x)
         if x.dim() != 5:
             raise ValueError(f"expected (B, T, C, H, W), got {tuple(x.shape)}")
         b, t, c, h, w = x.shape
@@ -496,6 +766,8 @@ class UNetConvNext(nn.Module):
             raise ValueError(f"H and W must be multiples of 2 ** stages = {div} (the decoder's skips would not match), got {h} x {w}")
         _gpu(x)
         compute = resolve_compute(self.compute)
+        if train:
+            return convnext_train_forward(self, x, compute)
         x4 = x.detach().to(torch.float32).contiguous().view(b, t * c, h, w)       # b t c h w contiguous IS b (t c) h w
         cur = _conv3x3_any(x4, self.in_proj, self._cache, True, False)
         skips = []

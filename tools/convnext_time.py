@@ -15,8 +15,18 @@ fused, ... regions), in both modes.
 
     python tools/convnext_time.py [--steps 5] [--out profiles/convnext_time.json]
 
-Writes the times, the spread of the regions, the launches per forward and the per-kernel split (torch.profiler, one forward)."""
+Writes the times, the spread of the regions, the launches per forward and the per-kernel split (torch.profiler, one forward).
+
+    python tools/convnext_time.py --train [--steps 3] [--out profiles/convnext_train_time.json]
+
+times one TRAIN step of the same config (B = 4, bf16 compute): tante_amd.train_step on the opted-in model with
+FlatAdamW(model.trained_parameters()), against the same eager composition under autograd (bf16 autocast) with clip_grad_norm_ and torch's
+fused AdamW on its own copy of the weights -- the parent has no training path, so eager torch is the only yardstick, and no ratio is
+promised.  It also records, on the two g21 model fixtures, every trained parameter's bf16-mode gradient error against the eager
+composition in float64, beside the error of the eager composition under bf16 autocast against the same float64, and names the HIP
+gradients that are more than twice as far from float64 as the eager ones."""
 import argparse
+import copy
 import json
 import os
 import sys
@@ -52,7 +62,7 @@ def eager_stage(st, x):
     return x
 
 
-def eager_forward(m, x):
+def eager_forward(m, x, out_dtype=torch.float32):
     """models.UNetConvNext.forward from the mathematics, on m's parameters, as eager torch ops, channels first."""
     b, t, c, h, w = x.shape
     x = m.in_proj(x.reshape(b, t * c, h, w))
@@ -65,7 +75,7 @@ def eager_forward(m, x):
         if j > 0:
             x = torch.cat([x, skips[-j]], dim=1)
         x = eager_stage(dec, x)
-    return m.out_proj(x).float().unsqueeze(1)
+    return m.out_proj(x).to(out_dtype).unsqueeze(1)
 
 
 def rescale(m):
@@ -125,14 +135,131 @@ def block_ab(m, B, res, steps):
     return rows
 
 
+NEW_KERNELS = ("dlb_a_kernel", "dlb_b_kernel", "dlb_c_kernel", "l2_bwd_kernel", "dl_kernel", "l2_kernel")
+
+
+def step_profile(step):
+    """One profiled step: -> (launches, device us in all, the twelve heaviest kernels, the block's and the row norm's kernels by name)."""
+    from torch.profiler import ProfilerActivity, profile
+    step()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        step()
+        torch.cuda.synchronize()
+    rows = [(e.key, e.count, float(getattr(e, "device_time_total", 0.0) or getattr(e, "cuda_time_total", 0.0))) for e in prof.key_averages()]
+    rows = sorted((r for r in rows if r[2] > 0.0), key=lambda r: -r[2])
+    fmt = lambda r: {"name": r[0][:96], "calls": r[1], "us": round(r[2], 1)}      # noqa: E731
+    return (sum(r[1] for r in rows), round(sum(r[2] for r in rows), 1), [fmt(r) for r in rows[:12]],
+            [fmt(r) for r in rows if any(k in r[0] for k in NEW_KERNELS)])
+
+
+def gradient_errors(dev):
+    """The two g21 model fixtures: rel L2 error per trained parameter of the bf16-mode HIP gradient and of the eager composition's gradient
+    under bf16 autocast, both against the eager composition in float64 (same weights, same output gradient)."""
+    import types
+
+    import numpy as np
+    out = {}
+    for name in ("g21_convnext_model_f15_s2_20x28", "g21_convnext_model_f8_s3_16x24"):
+        raw = np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))
+        sd = {k[2:]: torch.from_numpy(raw[k]) for k in raw.files if k.startswith("w.")}
+        m = tante_amd.UNetConvNext(int(raw["in_T"]), types.SimpleNamespace(n_fields=int(raw["n_fields"]), n_spatial_dims=2), stages=int(raw["stages"]),
+                                   blocks_per_stage=int(raw["blocks_per_stage"]), blocks_at_neck=int(raw["blocks_at_neck"]),
+                                   init_features=int(raw["init_features"]))
+        m.load_state_dict(sd, strict=True)
+        m = m.to(dev).eval().set_compute("bf16").set_trainable()
+        m64 = copy.deepcopy(m).double()
+        names = [k for k, _ in m.named_parameters() if not k.endswith("resample.block.0.bias")]
+        x = torch.from_numpy(raw["x"]).float().to(dev)
+        y64 = eager_forward(m64, x.double(), torch.float64)
+        gy = torch.randn(y64.shape, generator=torch.Generator().manual_seed(32)).to(dev)
+        want = torch.autograd.grad(y64, m64.trained_parameters(), gy.double())
+        hip = torch.autograd.grad(m(x), m.trained_parameters(), gy)
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            ye = eager_forward(m, x)
+        eager = torch.autograd.grad(ye, m.trained_parameters(), gy)
+        rel = lambda a, b: float((a.double() - b).norm() / b.norm())      # noqa: E731
+        rows = {k: {"hip": rel(a, w), "eager_autocast": rel(e, w)} for k, a, e, w in zip(names, hip, eager, want)}
+        flagged = [k for k, r in rows.items() if r["hip"] > 2 * r["eager_autocast"]]
+        hs, es = sorted(r["hip"] for r in rows.values()), sorted(r["eager_autocast"] for r in rows.values())
+        out[name] = {"parameters": len(rows), "hip_median": hs[len(hs) // 2], "hip_max": hs[-1], "eager_median": es[len(es) // 2], "eager_max": es[-1],
+                     "hip_more_than_twice_eager": flagged, "per_parameter": rows}
+        print(f"{name}: bf16 gradients vs float64: HIP median {hs[len(hs) // 2]:.3e} max {hs[-1]:.3e}; eager autocast median {es[len(es) // 2]:.3e} "
+              f"max {es[-1]:.3e}; HIP > 2 x eager: {flagged}", flush=True)
+    return out
+
+
+def train_main(args, dev):
+    """The train step of configs/unet_convnext_am.yaml: HIP (train_step, FlatAdamW) against eager torch under autograd."""
+    cfg = tante_amd.load_config(os.path.join(ROOT, "configs", "unet_convnext_am.yaml"))
+    wl = cfg["workload"]
+    torch.manual_seed(cfg["seed"])
+    md = tante_amd.TanteMetadata(n_fields=wl["n_fields"], spatial_resolution=tuple(wl["spatial_resolution"]))
+    grad_err = gradient_errors(dev)
+    m = tante_amd.build_model(cfg, md).to(dev)
+    rescale(m)
+    m = m.train().set_compute("bf16").set_trainable()
+    me = copy.deepcopy(m)           # the eager composition trains its own copy of the weights
+    B, T, res, nf = wl["batch_size"], cfg["model"]["in_T"], wl["spatial_resolution"], wl["n_fields"]
+    batch = {"input": torch.randn(B, T, *res, nf, device=dev), "output": torch.randn(B, 1, *res, nf, device=dev)}
+    fmt = tante_amd.DefaultChannelsFirstFormatter(md)
+    opt = tante_amd.FlatAdamW(m.trained_parameters(), lr=1e-5)
+    eparams = me.trained_parameters()
+    eopt = torch.optim.AdamW(eparams, lr=1e-5, weight_decay=1e-5, fused=True)
+    x = batch["input"].permute(0, 1, 4, 2, 3).contiguous()
+
+    def hip_step():
+        return tante_amd.train_step(m, opt, batch, fmt, 1)
+
+    def eager_step():
+        eopt.zero_grad(set_to_none=True)
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            y = eager_forward(me, x)
+        loss = F.mse_loss(y.permute(0, 1, 3, 4, 2).float(), batch["output"])
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(eparams, 1.0)
+        eopt.step()
+        return loss.detach()
+
+    l_hip, l_eager = float(hip_step()), float(eager_step())         # the first step of each, from the same weights
+    torch.cuda.synchronize()
+    print(f"first losses: HIP {l_hip:.6f}, eager torch {l_eager:.6f}", flush=True)
+    if not abs(l_hip - l_eager) < 1e-2 * abs(l_eager) and not args.time_anyway:
+        raise SystemExit(f"the first losses disagree ({l_hip} vs {l_eager}): nothing timed")
+    hip = timed(hip_step, args.steps)
+    print("HIP timed", flush=True)
+    eager = timed(eager_step, args.steps)
+    print("eager timed", flush=True)
+    n_hip, us_hip, split_hip, new_hip = step_profile(hip_step)
+    n_eager, us_eager, split_eager, _ = step_profile(eager_step)
+    spread = max(hip["ms_max"] - hip["ms_min"], eager["ms_max"] - eager["ms_min"])
+    result = {"workload": {"config": "configs/unet_convnext_am.yaml", "compute": "bf16", "batch": B, "in_T": T, "resolution": res, "n_fields": nf,
+                           "n_steps_output": 1, "parameters": sum(p.numel() for p in m.parameters()),
+                           "trained_parameters": sum(p.numel() for p in m.trained_parameters())},
+              "device": torch.cuda.get_device_name(0), "first_loss": {"hip": l_hip, "eager_torch": l_eager},
+              "hip": hip, "eager_torch": eager, "speedup_median": round(eager["ms_median"] / hip["ms_median"], 3),
+              "hip_not_slower_beyond_spread": bool(hip["ms_median"] <= eager["ms_median"] + spread),
+              "launches_per_step": {"hip": n_hip, "eager_torch": n_eager}, "device_us_per_step": {"hip": us_hip, "eager_torch": us_eager},
+              "kernels_hip": split_hip, "block_and_row_norm_kernels_hip": new_hip, "kernels_eager_torch": split_eager,
+              "bf16_gradient_rel_errors_vs_float64": grad_err}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+    print(json.dumps({"hip_ms": hip["ms_median"], "eager_ms": eager["ms_median"], "launches": n_hip, "device_us": us_hip}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true", help="time the train step instead of the forward (default --out profiles/convnext_train_time.json)")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 4])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "convnext_time.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--time-anyway", action="store_true", help="time also when a HIP output misses its gate (recorded as gate_passed: false)")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "convnext_train_time.json" if args.train else "convnext_time.json")
     dev = torch.device("cuda:0")
+    if args.train:
+        return train_main(args, dev)
     cfg = tante_amd.load_config(os.path.join(ROOT, "configs", "unet_convnext_am.yaml"))
     wl = cfg["workload"]
     torch.manual_seed(cfg["seed"])
