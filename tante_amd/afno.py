@@ -37,6 +37,7 @@ from . import kernels as K
 from . import stages as S
 from .attn_backbone import _PackCache, resolve_compute
 from .dft_tables import cis, device_tables, pack_tables
+from .model_shell import ComputeSwitch, Trainable, gpu_only, wants_graph
 
 MAX_GRID = 64     # token-grid points per axis the filter kernels serve
 MAX_BLOCK = 64    # channels per diagonal block
@@ -120,8 +121,7 @@ def _filter_launch(x, residual, w1, w2, bs, lam, out=None) -> Tuple[torch.Tensor
         L.check(lib.tante_afno_filter(None, None, B, H, W, C_, bs, None, None, None, float(lam), None, None, 0, None), "tante_afno_filter")
     if out is None:
         out = torch.empty_like(x)
-    nbytes = int(lib.tante_afno_filter_workspace_bytes(B, H, W, C_))
-    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    work, nbytes = K.workspace(lib.tante_afno_filter_workspace_bytes(B, H, W, C_), x.device)
     L.check(lib.tante_afno_filter(K._p(x), K._p(residual), B, H, W, C_, bs, K._p(_twiddles(H, W, x.device)), K._p(w1), K._p(w2), float(lam),
                                   K._p(out), K._p(work), nbytes, K._stream()), "tante_afno_filter")
     return out, work
@@ -185,48 +185,27 @@ class AfnoFilterFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
-        from .autograd import _grad_slot
+        from .autograd import grad_slots
         work, w1, w2 = ctx.saved_tensors
         B, H, W, C_, bs, lam = ctx.geo
         dout = dout.contiguous()
         dev = dout.device
         lib = L.lib()
         dx = torch.empty_like(dout)
-        slots = [_grad_slot(p) if ctx.needs_input_grad[2 + i] else None for i, p in enumerate(ctx.params)]
-        into = slots[0] is not None and slots[1] is not None
+        slots = grad_slots(ctx, ctx.params, 2)
+        into = slots is not None
         dws = slots if into else [torch.empty(p.shape, dtype=torch.float32, device=dev) for p in ctx.params]
         keep = None
         if _KEEP_SINK[0] is not None:
             Lc, Kc = kept_modes(H, W)
             keep = torch.empty(B, Lc, Kc, 2, C_, dtype=torch.uint8, device=dev)
             _KEEP_SINK[0].append(keep)
-        nbytes = int(lib.tante_afno_filter_bwd_workspace_bytes(B, H, W, C_, bs))
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        ws, nbytes = K.workspace(lib.tante_afno_filter_bwd_workspace_bytes(B, H, W, C_, bs), dev)
         L.check(lib.tante_afno_filter_bwd(K._p(dout), K._p(work), B, H, W, C_, bs, K._p(_twiddles(H, W, dev)), K._p(_twiddles_bwd(H, W, dev)),
                                           K._p(w1), K._p(w2), lam, K._p(dx), K._p(dws[0]), K._p(dws[1]), int(into), K._p(keep), K._p(ws), nbytes,
                                           K._stream()), "tante_afno_filter_bwd")
         g1, g2 = (None, None) if into else (dws[0] if ctx.needs_input_grad[2] else None, dws[1] if ctx.needs_input_grad[3] else None)
         return dx, (dout if ctx.has_res else None), g1, g2, None, None
-
-
-class PosRowsFn(Function):
-    """pos_embed (1, H', W', C) -> its rows repeated per sample (b H' W', C), the residual operand of the patch-embedding GEMM.  Backward:
-    the sum over the samples through tante_colsum, not a torch reduction (up to 64 samples one workgroup per 64 columns adds them in a
-    fixed order)."""
-
-    @staticmethod
-    def forward(ctx, pos, b):
-        ctx.param, ctx.b = pos, b
-        return pos.detach().expand(b, -1, -1, -1).reshape(-1, pos.shape[-1]).contiguous()
-
-    @staticmethod
-    def backward(ctx, d):
-        from .autograd import _grad_slot, colsum
-        d = d.contiguous()
-        pos, b = ctx.param, ctx.b
-        slot = _grad_slot(pos)
-        g = colsum(d, b, pos.numel(), 1, into=None if slot is None else slot.view(-1))
-        return (None if slot is not None else g.view(pos.shape)), None
 
 
 def _no_dropout(training: bool, *rates):
@@ -255,7 +234,7 @@ def block_train(blk: "Block", x: torch.Tensor, compute: int) -> torch.Tensor:
 def afno_train_forward(model: "AFNO", x: torch.Tensor, compute: int) -> torch.Tensor:
     """AFNO.forward with an autograd graph: x (b, t, c, h, w) -> (b, 1, c, h, w) fp32.  torch only re-lays out (the channels-last copy of
     the input, parameter-sized weight views); every activation-sized operation is a HIP node."""
-    from .autograd import DeconvFn, Im2colFn, LinearFn
+    from .autograd import DeconvFn, Im2colFn, LinearFn, PosRowsFn
     b, t, c, h, w = x.shape
     p, C_ = model.patch_size, model.hidden_dim
     Hp, Wp = h // p, w // p
@@ -301,7 +280,7 @@ class Mlp(nn.Module):
         self.drop = nn.Dropout(drop)
 
 
-class AFNO_ND(nn.Module):
+class AFNO_ND(Trainable, nn.Module):
     """The spectral filter  (afno.py:78-117)."""
 
     def __init__(self, hidden_size: int, resolution, cmlp_diagonal_blocks=8, sparsity_threshold=0.01):
@@ -316,12 +295,6 @@ class AFNO_ND(nn.Module):
         self.cmlp = nn.Sequential(ComplexBlockLinear(hidden_size, cmlp_diagonal_blocks=cmlp_diagonal_blocks), RealImagGELU(),
                                   ComplexBlockLinear(hidden_size, cmlp_diagonal_blocks=cmlp_diagonal_blocks))
         self._cache = _PackCache()
-        self._trainable = False
-
-    def set_trainable(self, flag: bool = True):
-        """Opt in to (or out of) training: under grad, forward then builds an autograd graph through AfnoFilterFn instead of refusing."""
-        self._trainable = bool(flag)
-        return self
 
     def _packed(self):
         ws = [self.cmlp[0].weight, self.cmlp[2].weight]
@@ -334,10 +307,10 @@ class AFNO_ND(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(b, H, W, C) -> (b, W, H, C), as the reference returns it (afno.py:103-117).  Under grad only after set_trainable()."""
-        train = _wants_graph(self, x)
+        train = wants_graph(self, x, _refuse)
         if x.dim() != 4:
             raise NotImplementedError("the AFNO filter is two-dimensional here: n_spatial_dims = 3 is out of scope")
-        _gpu(x)
+        gpu_only(x, "AFNO")
         if train:
             y = AfnoFilterFn.apply(x.to(torch.float32), None, self.cmlp[0].weight, self.cmlp[2].weight,
                                    self.hidden_size // self.cmlp_diagonal_blocks, self.sparsity_threshold)
@@ -345,7 +318,7 @@ class AFNO_ND(nn.Module):
         return self.run(x.detach().to(torch.float32).contiguous(), None).transpose(1, 2).to(x.dtype)
 
 
-class Block(nn.Module):
+class Block(Trainable, nn.Module):
     """x = swap_hw(filter(norm1 x)) + x;  x = mlp(norm2 x) + x   (afno.py:120-166)."""
 
     def __init__(self, hidden_dim, resolution, mlp_ratio=4.0, drop=0.0, drop_path=0.0, act_layer=nn.GELU, norm_layer=nn.LayerNorm,
@@ -361,12 +334,6 @@ class Block(nn.Module):
         self.double_skip = double_skip
         self.hidden_dim = hidden_dim
         self._cache = _PackCache()
-        self._trainable = False
-
-    def set_trainable(self, flag: bool = True):
-        self._trainable = bool(flag)
-        self.filter.set_trainable(flag)
-        return self
 
     def _packed(self, compute: int):
         n2, m = self.norm2, self.mlp
@@ -392,37 +359,27 @@ class Block(nn.Module):
         return S.linear_chunks(h, pk["fc2"], residual=skip.view(M, C_)).view(B, H, W, C_)       # the skip rides the residual operand
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        train = _wants_graph(self, x)
+        train = wants_graph(self, x, _refuse)
         if train:
             _no_dropout(self.training, self.drop_path_rate, self.mlp.drop.p)
         if x.dim() != 4:
             raise NotImplementedError("the AFNO block is two-dimensional here: n_spatial_dims = 3 is out of scope")
-        _gpu(x)
+        gpu_only(x, "AFNO")
         if train:
             return block_train(self, x.to(torch.float32), resolve_compute(None))
         return self.run(x.detach().to(torch.float32).contiguous(), resolve_compute(None))
 
 
-def _gpu(x: torch.Tensor):
-    if not x.is_cuda:
-        raise RuntimeError("tante_amd.AFNO runs on the GPU only (no CPU fallback); move the model and its input to cuda")
-
-
-def _wants_graph(module: nn.Module, x: torch.Tensor) -> bool:
-    """True: build the autograd graph (opted in, grad enabled, something to differentiate).  A module that has not opted in refuses
-    under grad as it always did."""
-    if not torch.is_grad_enabled():
-        return False
-    params = any(p.requires_grad for p in module.parameters())
-    if module._trainable:
-        return params or x.requires_grad
-    if params:
+def _refuse(module: nn.Module):
+    """AFNO's refusal of a module that has not opted in.  Unlike DPOT and UNetConvNext, which hand model_shell.inference_only to the gate,
+    it refuses only under grad with a parameter that requires one -- not in train() under no_grad -- and in words of its own.  That
+    difference is pinned behaviour: tests/test_afno_train_cpu.py::test_opt_in_surface and tests/test_hip_afno_train.py."""
+    if torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()):
         raise NotImplementedError("tante_amd.AFNO is inference only unless set_trainable() was called: training is out of scope for this "
                                   "model as it stands; opt in, or call it in eval mode under torch.no_grad()")
-    return False
 
 
-class AFNO(nn.Module):
+class AFNO(Trainable, ComputeSwitch, nn.Module):
     """models/afno.py:169-278 -- same constructor, attributes, parameters and forward contract."""
 
     def __init__(self, in_T, dset_metadata=None, hidden_dim=256, n_blocks=12, cmlp_diagonal_blocks=8, patch_size=8, mlp_ratio=4.0,
@@ -457,18 +414,8 @@ class AFNO(nn.Module):
                                            sparsity_threshold=sparsity_threshold) for i in range(n_blocks)])
         self.apply(self._init_weights)
         self.output_length = 1
-        self.compute: Optional[str] = None
         self._cache = _PackCache()
         self._pos = _PackCache()
-        self._trainable = False
-
-    def set_trainable(self, flag: bool = True):
-        """Opt in to (or out of) training: under grad, forward then takes afno_train_forward instead of refusing.  Not a constructor
-        argument and not part of the state_dict; returns self, like set_compute."""
-        self._trainable = bool(flag)
-        for blk in self.blocks:
-            blk.set_trainable(flag)
-        return self
 
     def _init_weights(self, m):
         if isinstance(m, nn.Linear):
@@ -482,12 +429,6 @@ class AFNO(nn.Module):
     @torch.jit.ignore
     def no_weight_decay(self):
         return {"pos_embed", "cls_token"}
-
-    def set_compute(self, mode: Optional[str]):
-        if mode is not None and mode not in K.COMPUTE:
-            raise ValueError("compute must be None, 'fp32' or 'bf16'")
-        self.compute = mode
-        return self
 
     def _packed(self, compute: int):
         pe, pd = self.patch_embed, self.patch_debed
@@ -514,11 +455,11 @@ class AFNO(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x (b, t, c, h, w) -> (b, 1, c, h, w)   (afno.py:270-278)."""
-        train = _wants_graph(self, x)
+        train = wants_graph(self, x, _refuse)
         _no_dropout(self.training, self.drop_rate, self.drop_path_rate)
         if x.dim() != 5 or x.shape[1] * x.shape[2] != self.dim_in:
             raise ValueError(f"expected (B, {self.in_T}, {self.dim_out}, H, W), got {tuple(x.shape)}")
-        _gpu(x)
+        gpu_only(x, "AFNO")
         b, t, c, h, w = x.shape
         p = self.patch_size
         if [h // p, w // p] != list(self.inner_size) or h % p or w % p:

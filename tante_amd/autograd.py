@@ -91,6 +91,13 @@ def _grad_slot(p) -> Optional[torch.Tensor]:
     return g if (g.dtype == torch.float32 and g.is_contiguous() and g.shape == p.shape and g.is_cuda) else None
 
 
+def grad_slots(ctx, params, first: int):
+    """The gradient slots (_grad_slot) of a node's parameters, inputs `first` onwards of its forward, where EVERY one of them exists and
+    is wanted, else None: a backward kernel that writes several parameter gradients adds into all of the slots or into none."""
+    slots = [_grad_slot(p) if ctx.needs_input_grad[first + i] else None for i, p in enumerate(params)]
+    return slots if all(s is not None for s in slots) else None
+
+
 # ---- weight gradients on a side stream -------------------------------------------------------------------------------------------
 # The weight-gradient kernel of a layer and the data-gradient GEMM of the same layer are independent (both read dY), each is bound by
 # latency / lockstep rather than by a saturated unit, and their resources add up to exactly one CU (3 x 32 KB + 64 KB of LDS, 4 x 128
@@ -494,6 +501,25 @@ def colsum(x: torch.Tensor, outer: int, Cc: int, inner: int, into: Optional[torc
     out = into if into is not None else torch.empty(Cc, dtype=torch.float32, device=x.device)
     L.check(L.lib().tante_colsum(x.data_ptr(), _DT[x.dtype], outer, Cc, inner, out.data_ptr(), int(into is not None), _s()), "tante_colsum")
     return out
+
+
+class PosRowsFn(Function):
+    """pos_embed (1, H', W', C) -> its rows repeated per sample (b H' W', C), the residual operand of the patch-embedding GEMM.  Backward:
+    the sum over the samples through tante_colsum, not a torch reduction (up to 64 samples one workgroup per 64 columns adds them in a
+    fixed order)."""
+
+    @staticmethod
+    def forward(ctx, pos, b):
+        ctx.param, ctx.b = pos, b
+        return pos.detach().expand(b, -1, -1, -1).reshape(-1, pos.shape[-1]).contiguous()
+
+    @staticmethod
+    def backward(ctx, d):
+        d = d.contiguous()
+        pos, b = ctx.param, ctx.b
+        slot = _grad_slot(pos)
+        g = colsum(d, b, pos.numel(), 1, into=None if slot is None else slot.view(-1))
+        return (None if slot is not None else g.view(pos.shape)), None
 
 
 class LayerNormFn(Function):

@@ -44,6 +44,7 @@ from . import _lib as L
 from . import kernels as K
 from . import stages as S
 from .attn_backbone import _PackCache, resolve_compute
+from .model_shell import ComputeSwitch, gpu_only, inference_only, site
 
 MAX_TOKENS = 4096   # tokens per image tante_instnorm serves
 MAX_AXIS = 64       # tokens per axis tante_axial_attention serves
@@ -51,11 +52,6 @@ MAX_T = 16          # time steps tante_time_attention serves
 HEAD_DIMS = (16, 32, 64)
 OUT_STEPS = 4       # x[-4:]  (avit.py:450)
 BF16_SITES = ("mlp",)   # the GEMM groups that take bf16 operands in bf16 mode; "stem", "attn" and "head" miss the 1e-2 bar
-
-
-def _site(compute: int, site: str) -> int:
-    """The compute mode of one GEMM group: the caller's for the groups in BF16_SITES, fp32 for the rest."""
-    return compute if site in BF16_SITES else L.F32
 
 
 # ---- host side of the kernels: the predicates' mirrors, the wrappers, the folds, the bias table -----------------------------------------
@@ -97,8 +93,7 @@ def instnorm(x: torch.Tensor, form: int, weight: Optional[torch.Tensor], bias: O
     lib = L.lib()
     if out is None:
         out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    nbytes = max(int(lib.tante_instnorm_workspace_bytes(n, HW, C_)), 0)           # (-1: the call below refuses by name)
-    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    work, nbytes = K.workspace(lib.tante_instnorm_workspace_bytes(n, HW, C_), x.device)           # (-1: the call below refuses by name)
     L.check(lib.tante_instnorm(K._p(x), n, HW, C_, form, float(eps), K._p(weight), K._p(bias), act, K._p(residual), K._p(gamma), K._p(out),
                                K._DT[out.dtype], K._p(work), nbytes, K._stream()), "tante_instnorm")
     return out
@@ -148,8 +143,7 @@ def field_stats(x: torch.Tensor, normalise: bool = True, eps: float = 1e-7):
     lib = L.lib()
     stats = torch.empty(B, C_, 2, dtype=torch.float32, device=x.device)
     xn = torch.empty(T * B, H, W, C_, dtype=torch.float32, device=x.device) if normalise else None
-    nbytes = max(int(lib.tante_field_stats_workspace_bytes(B, T, C_, H * W)), 0)
-    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    work, nbytes = K.workspace(lib.tante_field_stats_workspace_bytes(B, T, C_, H * W), x.device)
     L.check(lib.tante_field_stats(K._p(x), B, T, C_, H * W, float(eps), K._p(stats), K._p(xn), K._p(work), nbytes, K._stream()), "tante_field_stats")
     return stats, xn
 
@@ -211,34 +205,9 @@ def fold_stem(bag_weight: torch.Tensor, bag_bias: torch.Tensor, conv_weight: tor
     return w.reshape(w.shape[0], -1).float().contiguous(), b.float().contiguous()
 
 
-def _deconv2(rows: torch.Tensor, dec, n: int, Hi: int, Wi: int, Cout: int) -> torch.Tensor:
-    """A 2 x 2 / 2 transposed convolution without bias on channels-last rows -> (n, 2 Hi, 2 Wi, Cout) fp32."""
-    if isinstance(dec, K.PackedWeight):
-        img = torch.empty(n, 2 * Hi, 2 * Wi, Cout, dtype=torch.float32, device=rows.device)
-        return K.deconv(rows, dec, img, n_img=n, Hi=Hi, Wi=Wi, P=2, Cout=Cout, nchw_out=False, act=L.ACT_NONE)
-    taps = S.linear_chunks(rows, dec, torch.float32)
-    return K.col2im_nhwc(taps, n, Hi, Wi, 2, 2, 0, Cout, None, torch.float32)
-
-
-def _pack_deconv2(weight: torch.Tensor, compute: int):
-    cin, cout = weight.shape[0], weight.shape[1]
-    if cin <= S.KMAX:
-        return K.pack_weight(weight, None, compute, L.W_DECONV_NHWC, N=cout * 4, K=cin, P=2, C_other=cout)
-    # the tap matrix (P P Cout, Cin), columns (kh, kw, co), K-chunked
-    return S.pack_linear_chunks(weight.detach().permute(2, 3, 1, 0).reshape(-1, cin).contiguous(), None, compute)
-
-
 # ---- the reference's modules -------------------------------------------------------------------------------------------------------
-def _gpu(x: torch.Tensor):
-    if not x.is_cuda:
-        raise RuntimeError("tante_amd.AViT runs on the GPU only (no CPU fallback); move the model and its input to cuda")
-
-
-def _inference_only(module: nn.Module):
-    if module.training or (torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters())):
-        raise NotImplementedError("tante_amd.AViT is inference only: training is out of scope (the backward of the instance norms and of "
-                                  "the axial / time attention are kernels of their own that are not built); call .eval() under "
-                                  "torch.no_grad()")
+WHY_INFERENCE_ONLY = ("the backward of the instance norms and of the axial / time attention are kernels of their own that are not "
+                      "built")
 
 
 def _token_grid(Hp: int, Wp: int):
@@ -331,8 +300,8 @@ class RMSInstanceNorm2d(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(B, C, H, W) -> (B, C, H, W).  Inference only."""
-        _inference_only(self)
-        _gpu(x)
+        inference_only(self, "AViT", WHY_INFERENCE_ONLY)
+        gpu_only(x, "AViT")
         B, C_, H, W = x.shape
         y = self.run(x.detach().to(torch.float32).permute(0, 2, 3, 1).reshape(B, H * W, C_).contiguous())
         return y.view(B, H, W, C_).permute(0, 3, 1, 2).to(x.dtype)
@@ -376,7 +345,7 @@ class hMLP_stem(nn.Module):
         if H % 16 or W % 16:
             raise ValueError(f"H and W must be multiples of 16 (the stem is 4 x 2 x 2), got {H} x {W}")
         _token_grid(H // 16, W // 16)
-        compute = _site(compute, "stem")
+        compute = site(compute, "stem", BF16_SITES)
         own = self._packed(compute)
         adt = K.act_torch_dtype(compute)
         E4 = self.embed_dim // 4
@@ -392,8 +361,8 @@ class hMLP_stem(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(n, in_chans, H, W) -> (n, embed_dim, H/16, W/16).  Inference only."""
-        _inference_only(self)
-        _gpu(x)
+        inference_only(self, "AViT", WHY_INFERENCE_ONLY)
+        gpu_only(x, "AViT")
         n, _, H, W = x.shape
         y = self.run(x.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous(), resolve_compute(None))
         return y.view(n, H // 16, W // 16, self.embed_dim).permute(0, 3, 1, 2).to(x.dtype)
@@ -426,19 +395,19 @@ class hMLP_output(nn.Module):
         def build():
             wk = self.out_kernel.detach()[:, labels].contiguous()
             bk = self.out_bias.detach()[labels].contiguous()
-            return (_pack_deconv2(d0.weight, compute), _pack_deconv2(d3.weight, compute),
+            return (S.pack_deconv_nhwc(d0.weight, None, 2, compute), S.pack_deconv_nhwc(d3.weight, None, 2, compute),
                     K.pack_weight(wk, bk, compute, L.W_DECONV_NCHW, N=len(labels) * 16, K=E4, P=4, C_other=len(labels)))
         return self._cache.get((compute, tuple(labels)), [d0.weight, d3.weight, self.out_kernel, self.out_bias], build)
 
     def run(self, rows: torch.Tensor, n: int, Hp: int, Wp: int, labels, compute: int) -> torch.Tensor:
         """rows (n Hp Wp, embed_dim) fp32 -> (n, len(labels), 16 Hp, 16 Wp) fp32 channels first."""
-        compute = _site(compute, "head")
+        compute = site(compute, "head", BF16_SITES)
         d0, d3, last = self._packed(compute, labels)
         adt = K.act_torch_dtype(compute)
         E4 = self.embed_dim // 4
-        img = _deconv2(rows, d0, n, Hp, Wp, E4)
+        img = S.deconv_nhwc(rows, d0, None, n, Hp, Wp, 2, E4)
         a = self.out_proj[1].run(img.view(n, 4 * Hp * Wp, E4), adt, L.ACT_GELU_ERF)
-        img = _deconv2(a.view(n * 4 * Hp * Wp, E4), d3, n, 2 * Hp, 2 * Wp, E4)
+        img = S.deconv_nhwc(a.view(n * 4 * Hp * Wp, E4), d3, None, n, 2 * Hp, 2 * Wp, 2, E4)
         a = self.out_proj[4].run(img.view(n, 16 * Hp * Wp, E4), adt, L.ACT_GELU_ERF)
         c = len(list(labels))
         out = torch.empty(n, c, 16 * Hp, 16 * Wp, dtype=torch.float32, device=rows.device)
@@ -446,8 +415,8 @@ class hMLP_output(nn.Module):
 
     def forward(self, x: torch.Tensor, state_labels) -> torch.Tensor:
         """(n, embed_dim, H', W') -> (n, len(state_labels), 16 H', 16 W').  Inference only."""
-        _inference_only(self)
-        _gpu(x)
+        inference_only(self, "AViT", WHY_INFERENCE_ONLY)
+        gpu_only(x, "AViT")
         n, E, Hp, Wp = x.shape
         rows = x.detach().to(torch.float32).permute(0, 2, 3, 1).reshape(n * Hp * Wp, E).contiguous()
         return self.run(rows, n, Hp, Wp, state_labels, resolve_compute(None)).to(x.dtype)
@@ -493,7 +462,7 @@ class AxialAttentionBlock(nn.Module):
 
         def build():
             wo, bo = fold_layer_scale(oh.weight, oh.bias, self.gamma_att)
-            ca, cm = _site(compute, "attn"), _site(compute, "mlp")
+            ca, cm = site(compute, "attn", BF16_SITES), site(compute, "mlp", BF16_SITES)
             return (S.pack_linear_chunks(ih.weight.detach().reshape(ih.weight.shape[0], -1), ih.bias, ca),
                     S.pack_linear_chunks(wo, bo, ca), S.pack_linear_chunks(f1.weight.detach(), f1.bias, cm),
                     S.pack_linear_chunks(f2.weight.detach(), f2.bias, cm))
@@ -503,7 +472,7 @@ class AxialAttentionBlock(nn.Module):
         """x (n Hp Wp, C) fp32 rows, updated IN PLACE and returned."""
         _token_grid(Hp, Wp)
         M, C_ = x.shape
-        adt, mdt = K.act_torch_dtype(_site(compute, "attn")), K.act_torch_dtype(_site(compute, "mlp"))
+        adt, mdt = K.act_torch_dtype(site(compute, "attn", BF16_SITES)), K.act_torch_dtype(site(compute, "mlp", BF16_SITES))
         inp, outp, fc1, fc2 = self._packed(compute)
         x3 = x.view(n, Hp * Wp, C_)
         n1 = self.norm1.run(x3, adt)
@@ -522,8 +491,8 @@ class AxialAttentionBlock(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(B, C, H, W) -> (B, C, H, W)  (avit.py:250-286).  Inference only."""
-        _inference_only(self)
-        _gpu(x)
+        inference_only(self, "AViT", WHY_INFERENCE_ONLY)
+        gpu_only(x, "AViT")
         B, C_, H, W = x.shape
         rows = x.detach().to(torch.float32).permute(0, 2, 3, 1).reshape(B * H * W, C_).contiguous()
         y = self.run(rows, B, H, W, resolve_compute(None))
@@ -555,7 +524,7 @@ class AttentionBlock(nn.Module):
 
         def build():
             wo, bo = fold_layer_scale(oh.weight, oh.bias, self.gamma)
-            ca = _site(compute, "attn")
+            ca = site(compute, "attn", BF16_SITES)
             return (S.pack_linear_chunks(ih.weight.detach().reshape(ih.weight.shape[0], -1), ih.bias, ca), S.pack_linear_chunks(wo, bo, ca))
         return self._cache.get(compute, params, build)
 
@@ -575,7 +544,7 @@ class AttentionBlock(nn.Module):
             raise NotImplementedError(f"T = {T} is out of scope: tante_time_attention serves 1..{MAX_T} time steps")
         _token_grid(1, HW)
         M, C_ = x.shape
-        adt = K.act_torch_dtype(_site(compute, "attn"))
+        adt = K.act_torch_dtype(site(compute, "attn", BF16_SITES))
         inp, outp = self._packed(compute)
         n1 = instnorm(x.view(T * B, HW, C_), L.INSTNORM_INSTANCE, self.norm1.weight.detach(), self.norm1.bias.detach(), self.norm1.eps, adt)
         qkv = S.linear_chunks(n1.view(M, C_), inp)
@@ -585,8 +554,8 @@ class AttentionBlock(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(T, B, C, H, W) -> (T, B, C, H, W)  (avit.py:308-331).  Inference only."""
-        _inference_only(self)
-        _gpu(x)
+        inference_only(self, "AViT", WHY_INFERENCE_ONLY)
+        gpu_only(x, "AViT")
         T, B, C_, H, W = x.shape
         rows = x.detach().to(torch.float32).permute(0, 1, 3, 4, 2).reshape(T * B * H * W, C_).contiguous()
         y = self.run(rows, T, B, H * W, resolve_compute(None))
@@ -610,15 +579,15 @@ class SpaceTimeBlock(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(T, B, C, H, W) -> (T, B, C, H, W).  Inference only."""
-        _inference_only(self)
-        _gpu(x)
+        inference_only(self, "AViT", WHY_INFERENCE_ONLY)
+        gpu_only(x, "AViT")
         T, B, C_, H, W = x.shape
         rows = x.detach().to(torch.float32).permute(0, 1, 3, 4, 2).reshape(T * B * H * W, C_).contiguous()
         y = self.run(rows, T, B, H, W, resolve_compute(None))
         return y.view(T, B, H, W, C_).permute(0, 1, 4, 2, 3).to(x.dtype)
 
 
-class AViT(nn.Module):
+class AViT(ComputeSwitch, nn.Module):
     """models/avit.py:379-454 -- same constructor, attributes, parameters and forward contract."""
 
     def __init__(self, in_T, dset_metadata=None, out_steps: int = 4, patch_size=(16, 16), embed_dim=768, num_heads=12, processor_blocks=8,
@@ -636,21 +605,14 @@ class AViT(nn.Module):
         self.blocks = nn.ModuleList([inner_block(drop_path=self.dp[i]) for i in range(processor_blocks)])
         self.debed = hMLP_output(patch_size=patch_size, embed_dim=embed_dim, out_chans=n_states)
         self.n_states, self.embed_dim, self.num_heads, self.patch_size = n_states, embed_dim, num_heads, patch_size
-        self.compute: Optional[str] = None
         self._cache = _PackCache()
-
-    def set_compute(self, mode: Optional[str]):
-        if mode is not None and mode not in K.COMPUTE:
-            raise ValueError("compute must be None, 'fp32' or 'bf16'")
-        self.compute = mode
-        return self
 
     def _packed_stem(self, compute: int, c: int):
         sb, c0 = self.space_bag, self.embed.in_proj[0]
 
         def build():
             w, b = fold_stem(sb.weight, sb.bias, c0.weight, c)
-            return S.pack_linear_chunks(w, b, _site(compute, "stem"))
+            return S.pack_linear_chunks(w, b, site(compute, "stem", BF16_SITES))
         return self._cache.get((compute, c), [sb.weight, sb.bias, c0.weight], build)
 
     def encode(self, xn: torch.Tensor, compute: Optional[int] = None) -> torch.Tensor:
@@ -664,10 +626,10 @@ class AViT(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x (b, t, c, h, w) -> (b, min(t, 4), c, h, w)   (avit.py:419-454)."""
-        _inference_only(self)
+        inference_only(self, "AViT", WHY_INFERENCE_ONLY)
         if x.dim() != 5:
             raise ValueError(f"expected (B, T, C, H, W), got {tuple(x.shape)}")
-        _gpu(x)
+        gpu_only(x, "AViT")
         b, T, c, h, w = x.shape
         if c > self.n_states:
             raise ValueError(f"the input has {c} fields, the model holds {self.n_states} states")

@@ -52,6 +52,7 @@ from . import kernels as K
 from . import options as _O
 from . import stages as S
 from .attn_backbone import _PackCache, resolve_compute
+from .model_shell import ComputeSwitch, Trainable, gpu_only, inference_only, site, to_nchw, to_nhwc, wants_graph
 
 FUSED_MAX_C = 256      # channels tante_convnext_block serves
 FUSED_DEFAULT_MAX_C = 32   # ... and the widest block it is the DEFAULT for: on the config's pyramid (token count x C^2 constant) the one launch
@@ -64,11 +65,6 @@ BF16_SITES = ("block", "resample", "skip")   # the GEMM groups that take bf16 op
 # True: blocks up to FUSED_DEFAULT_MAX_C channels run as one launch; False: every block runs the modular route (tante_dwconv_ln + two
 # tante_gemm), the A/B and parity partner of the fused launch
 FUSED = _O.register("TANTE_CONVNEXT_FUSED", True, __name__, "FUSED")
-
-
-def _site(compute: int, site: str) -> int:
-    """The compute mode of one GEMM group: the caller's for the groups in BF16_SITES, fp32 for the rest."""
-    return compute if site in BF16_SITES else L.F32
 
 
 # ---- host side of the kernels: the predicates' mirrors, the wrappers, the folds -----------------------------------------------------------
@@ -125,8 +121,7 @@ def pack_convnext(dw_w, dw_b, w1, b1, w2, b2, C_: int, compute: int) -> torch.Te
     ts = [t.detach().to(torch.float32).contiguous() for t in (dw_w.reshape(C_, 49), dw_b, w1, b1, w2, b2)]
     K._dev(*ts)
     lib = L.lib()
-    nbytes = int(lib.tante_convnext_stream_bytes(C_))
-    out = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=ts[0].device)
+    out, _ = K.workspace(lib.tante_convnext_stream_bytes(C_), ts[0].device)      # the stream's buffer; the entry point takes no size
     L.check(lib.tante_pack_convnext(*[K._p(t) for t in ts], C_, compute, K._p(out), K._stream()), "tante_pack_convnext")
     return out
 
@@ -193,8 +188,7 @@ def dwconv_ln_bwd(dy: torch.Tensor, x: torch.Tensor, dw_w: torch.Tensor, dw_b: t
         grads = [new(C_, 49), new(C_), new(C_) if ln_w is not None else None, new(C_) if ln_w is not None else None]
         accumulate = False
     dx = torch.empty_like(x)
-    nbytes = max(int(lib.tante_dwconv_ln_bwd_workspace_bytes(n, H, W, C_)), 0)      # (-1: the call below refuses by name)
-    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    work, nbytes = K.workspace(lib.tante_dwconv_ln_bwd_workspace_bytes(n, H, W, C_), x.device)      # (-1: the call below refuses by name)
     L.check(lib.tante_dwconv_ln_bwd(K._p(dy), K._DT[dy.dtype], K._p(x), n, H, W, C_, K._p(dw_w), K._p(dw_b), float(eps), K._p(ln_w), K._p(dx),
                                     K._p(grads[0]), K._p(grads[1]), K._p(grads[2]), K._p(grads[3]), int(accumulate), K._p(work), nbytes, K._stream()),
             "tante_dwconv_ln_bwd")
@@ -230,13 +224,13 @@ class DwConvLnFn(Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from .dpot import _slots
+        from .autograd import grad_slots
         (x,) = ctx.saved_tensors
         dw_w, dw_b, ln_w, ln_b = ctx.params
         C_ = x.shape[-1]
         dy = dy.contiguous()
         taps, lw = dw_w.detach().reshape(C_, 49), None if ln_w is None else ln_w.detach()
-        slots = _slots(ctx, ctx.params, 1) if (ln_w is not None and ln_b is not None) else None
+        slots = grad_slots(ctx, ctx.params, 1) if (ln_w is not None and ln_b is not None) else None
         if slots is not None:
             dx = dwconv_ln_bwd(dy, x, taps, dw_b.detach(), ctx.eps, lw, [slots[0].view(C_, 49), *slots[1:]], True)[0]
             return dx, None, None, None, None, None, None
@@ -274,7 +268,7 @@ def block_train(blk: "Block", x: torch.Tensor, compute: int) -> torch.Tensor:
     residual operand and gamma folded into pwconv2 (float64, rounded once, as fold_block computes it).  The one-launch
     tante_convnext_block stays inference only: its backward is not built."""
     from .autograd import ActFn, LinearFn
-    compute = _site(compute, "block")
+    compute = site(compute, "block", BF16_SITES)
     n, H, W, C_ = x.shape
     if not dwconv_ln_supported_py(n, H, W, C_):
         raise NotImplementedError(f"a block of {C_} channels is out of scope: tante_dwconv_ln serves 1..{DWLN_MAX_C}")
@@ -292,7 +286,7 @@ def block_train(blk: "Block", x: torch.Tensor, compute: int) -> torch.Tensor:
 def downsample_train(ds: "Downsample", x: torch.Tensor, compute: int) -> torch.Tensor:
     """Downsample.run as training nodes: L2NormRowsFn -> Im2colFn (2 x 2 / 2) -> LinearFn on the weight with the norm's weight folded in."""
     from .autograd import Im2colFn, LinearFn
-    compute = _site(compute, "resample")
+    compute = site(compute, "resample", BF16_SITES)
     n, H, W, C_ = x.shape
     if H % 2 or W % 2:
         raise ValueError(f"the 2 x 2 / 2 convolution takes even H and W, got {H} x {W}")
@@ -308,18 +302,12 @@ def downsample_train(ds: "Downsample", x: torch.Tensor, compute: int) -> torch.T
 def upsample_train(us: "Upsample", x: torch.Tensor, compute: int) -> torch.Tensor:
     """Upsample.run as training nodes: L2NormRowsFn -> DeconvFn, or LinearFn (tap matrix) + Col2imFn past 512 input channels, on the
     weight with the norm's weight folded into its rows."""
-    from .autograd import Col2imFn, DeconvFn, LinearFn
-    compute = _site(compute, "resample")
+    compute = site(compute, "resample", BF16_SITES)
     n, H, W, C_ = x.shape
     norm, dec = us.block[0], us.block[1]
-    cout = dec.weight.shape[1]
-    adt = K.act_torch_dtype(compute)
-    rows = L2NormRowsFn.apply(x.reshape(n * H * W, C_), norm.eps, adt)
-    wf = dec.weight.double() * norm.weight.double().reshape(-1, 1, 1, 1)                        # (Cin, Cout, 2, 2)
-    if C_ <= S.KMAX:
-        return DeconvFn.apply(rows, _fold32(wf), dec.bias, n, H, W, 2, False, compute, torch.float32)
-    taps = LinearFn.apply(rows, _fold32(wf.permute(2, 3, 1, 0).reshape(-1, C_)), None, None, compute, torch.float32)
-    return Col2imFn.apply(taps, dec.bias, n, H, W, 2, 2, 0, cout, torch.float32)
+    rows = L2NormRowsFn.apply(x.reshape(n * H * W, C_), norm.eps, K.act_torch_dtype(compute))
+    wf = dec.weight.double() * norm.weight.double().reshape(-1, 1, 1, 1)                        # (Cin, Cout, 2, 2), rounded once by the node
+    return S.deconv_nhwc_train(rows, wf, dec.bias, n, H, W, 2, compute, torch.float32)
 
 
 def stage_train(st: "Stage", x: torch.Tensor, compute: int, skip: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -334,7 +322,7 @@ def stage_train(st: "Stage", x: torch.Tensor, compute: int, skip: Optional[torch
             raise ValueError("a stage with skip_proj takes the skip")
         if tuple(skip.shape) != tuple(x.shape):
             raise ValueError(f"the skip must have the stream's shape {tuple(x.shape)}, got {tuple(skip.shape)}")
-        cs = _site(compute, "skip")
+        cs = site(compute, "skip", BF16_SITES)
         n, H, W, C_ = x.shape
         sp = st.skip_proj
         w = sp.weight.view(C_, 2 * C_)
@@ -381,29 +369,6 @@ def convnext_train_forward(model: "UNetConvNext", x: torch.Tensor, compute: int)
     return y.permute(0, 3, 1, 2).reshape(b, 1, model.dim_out, h, w)
 
 
-def _wants_graph(module: nn.Module, x: torch.Tensor) -> bool:
-    """True: build the autograd graph (opted in through set_trainable, grad enabled, something to differentiate).  A module that has not
-    opted in refuses as it always did; an opted-in one takes the inference path under no_grad, in train() as in eval() (drop_path is 0)."""
-    if not getattr(module, "_trainable", False):
-        _inference_only(module)
-        return False
-    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
-
-
-class _Trainable:
-    """set_trainable for the modules of this file: the flag on the module and on every child that has one."""
-
-    _trainable = False
-
-    def set_trainable(self, flag: bool = True):
-        """Opt in to (or out of) training: under grad, forward then builds an autograd graph instead of refusing.  Not a constructor
-        argument and not part of the state_dict; propagates to the children and returns self."""
-        for m in self.modules():
-            if isinstance(m, _Trainable):
-                m._trainable = bool(flag)
-        return self
-
-
 def conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], in_nchw: bool, out_nchw: bool) -> torch.Tensor:
     """tante_conv3x3: x (n, Cin, H, W) or (n, H, W, Cin) fp32 -> (n, Cout, H, W) or (n, H, W, Cout) fp32."""
     weight = weight.detach()
@@ -438,15 +403,11 @@ def _conv3x3_any(x: torch.Tensor, conv: nn.Conv2d, cache: _PackCache, in_nchw: b
 
 
 # ---- the reference's modules -------------------------------------------------------------------------------------------------------
-def _gpu(x: torch.Tensor):
-    if not x.is_cuda:
-        raise RuntimeError("tante_amd.UNetConvNext runs on the GPU only (no CPU fallback); move the model and its input to cuda")
+WHY_INFERENCE_ONLY = "the backward of the fused block is a kernel of its own that is not built"
 
 
-def _inference_only(module: nn.Module):
-    if module.training or (torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters())):
-        raise NotImplementedError("tante_amd.UNetConvNext is inference only: training is out of scope (the backward of the fused block is a "
-                                  "kernel of its own that is not built); call .eval() under torch.no_grad()")
+def _refuse(module: nn.Module):
+    inference_only(module, "UNetConvNext", WHY_INFERENCE_ONLY)
 
 
 def _two_d(n_spatial_dims: int):
@@ -454,15 +415,7 @@ def _two_d(n_spatial_dims: int):
         raise NotImplementedError(f"n_spatial_dims = {n_spatial_dims} is out of scope: the HIP path serves 2-D fields")
 
 
-def _to_nhwc(x: torch.Tensor) -> torch.Tensor:
-    return x.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
-
-
-def _to_nchw(y: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
-    return y.permute(0, 3, 1, 2).contiguous().to(like.dtype)
-
-
-class LayerNorm(_Trainable, nn.Module):
+class LayerNorm(Trainable, nn.Module):
     """unet_convnext.py:39-70.  channels_last: a LayerNorm over the last axis.  channels_first: NOT a LayerNorm but
     F.normalize(x, p=2, dim=1, eps) * weight; `bias` is held and never applied.  A parameter holder: its owner folds the affine into the
     GEMM behind it; forward evaluates it alone."""
@@ -484,26 +437,26 @@ class LayerNorm(_Trainable, nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """channels_last (..., C) -> (..., C); channels_first is evaluated by Downsample / Upsample.  Under grad only after set_trainable()."""
-        train = _wants_graph(self, x)
+        train = wants_graph(self, x, _refuse)
         if self.data_format != "channels_last":
             raise NotImplementedError("the channels_first norm is evaluated by its Downsample / Upsample (tante_l2norm_rows, weight folded "
                                       "into the convolution)")
-        _gpu(x)
+        gpu_only(x, "UNetConvNext")
         if train:
             from .autograd import LayerNormAffineFn
             return LayerNormAffineFn.apply(x.to(torch.float32), self.weight, self.bias, self.eps).to(x.dtype)
         return K.layernorm_affine(x.detach().to(torch.float32), self.weight.detach(), self.bias.detach(), self.eps).to(x.dtype)
 
 
-class _Resample(_Trainable, nn.Module):
+class _Resample(Trainable, nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(n, C, H, W) -> (n, C', H', W').  Under grad only after set_trainable()."""
-        train = _wants_graph(self, x)
-        _gpu(x)
+        train = wants_graph(self, x, _refuse)
+        gpu_only(x, "UNetConvNext")
         if train:
             fn = downsample_train if isinstance(self, Downsample) else upsample_train
             return fn(self, x.to(torch.float32).permute(0, 2, 3, 1), resolve_compute(None)).permute(0, 3, 1, 2).to(x.dtype)
-        return _to_nchw(self.run(_to_nhwc(x), resolve_compute(None)), x)
+        return to_nchw(self.run(to_nhwc(x), resolve_compute(None)), x)
 
 
 class Upsample(_Resample):
@@ -518,28 +471,21 @@ class Upsample(_Resample):
 
     def _packed(self, compute: int):
         norm, dec = self.block[0], self.block[1]
-        cin, cout = dec.weight.shape[0], dec.weight.shape[1]
 
         def build():
             w = fold_cf_norm(dec.weight.transpose(0, 1), norm.weight).transpose(0, 1).contiguous()      # (Cin, Cout, 2, 2)
-            if cin <= S.KMAX:
-                return K.pack_weight(w, dec.bias.detach(), compute, L.W_DECONV_NHWC, N=cout * 4, K=cin, P=2, C_other=cout)
-            return S.pack_linear_chunks(w.permute(2, 3, 1, 0).reshape(-1, cin).contiguous(), None, compute)
+            return S.pack_deconv_nhwc(w, dec.bias.detach(), 2, compute)
         return self._cache.get(compute, [norm.weight, dec.weight, dec.bias], build)
 
     def run(self, x: torch.Tensor, compute: int) -> torch.Tensor:
         """x (n, H, W, C) fp32 -> (n, 2 H, 2 W, C') fp32."""
-        compute = _site(compute, "resample")
+        compute = site(compute, "resample", BF16_SITES)
         n, H, W, C_ = x.shape
         dec = self.block[1]
         cout = dec.weight.shape[1]
         pw = self._packed(compute)
         rows = l2norm_rows(x.view(n * H * W, C_), self.block[0].eps, K.act_torch_dtype(compute))
-        if isinstance(pw, K.PackedWeight):
-            img = torch.empty(n, 2 * H, 2 * W, cout, dtype=torch.float32, device=x.device)
-            return K.deconv(rows, pw, img, n_img=n, Hi=H, Wi=W, P=2, Cout=cout, nchw_out=False, act=L.ACT_NONE)
-        taps = S.linear_chunks(rows, pw, torch.float32)
-        return K.col2im_nhwc(taps, n, H, W, 2, 2, 0, cout, dec.bias.detach(), torch.float32)
+        return S.deconv_nhwc(rows, pw, dec.bias.detach(), n, H, W, 2, cout)
 
 
 class Downsample(_Resample):
@@ -559,7 +505,7 @@ class Downsample(_Resample):
 
     def run(self, x: torch.Tensor, compute: int) -> torch.Tensor:
         """x (n, H, W, C) fp32 -> (n, H / 2, W / 2, C') fp32."""
-        compute = _site(compute, "resample")
+        compute = site(compute, "resample", BF16_SITES)
         n, H, W, C_ = x.shape
         if H % 2 or W % 2:
             raise ValueError(f"the 2 x 2 / 2 convolution takes even H and W, got {H} x {W}")
@@ -570,7 +516,7 @@ class Downsample(_Resample):
         return y.view(n, H // 2, W // 2, -1)
 
 
-class Block(_Trainable, nn.Module):
+class Block(Trainable, nn.Module):
     """dwconv 7 x 7 -> LayerNorm -> Linear C -> 4 C -> GELU -> Linear 4 C -> C -> gamma -> + input  (unet_convnext.py:103-148)."""
 
     def __init__(self, dim, n_spatial_dims, drop_path=0.0, layer_scale_init_value=1e-6):
@@ -611,7 +557,7 @@ class Block(_Trainable, nn.Module):
 
     def run(self, x: torch.Tensor, compute: int, out: Optional[torch.Tensor] = None, fused: Optional[bool] = None) -> torch.Tensor:
         """x (n, H, W, C) fp32 -> `out` (a new tensor by default; never x)."""
-        compute = _site(compute, "block")
+        compute = site(compute, "block", BF16_SITES)
         n, H, W, C_ = x.shape
         fused = (FUSED and C_ <= FUSED_DEFAULT_MAX_C) if fused is None else fused
         if out is None:
@@ -629,14 +575,14 @@ class Block(_Trainable, nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(n, C, H, W) -> (n, C, H, W)  (unet_convnext.py:134-148).  Under grad only after set_trainable(), and then by block_train."""
-        train = _wants_graph(self, x)
-        _gpu(x)
+        train = wants_graph(self, x, _refuse)
+        gpu_only(x, "UNetConvNext")
         if train:
             return block_train(self, x.to(torch.float32).permute(0, 2, 3, 1).contiguous(), resolve_compute(None)).permute(0, 3, 1, 2).to(x.dtype)
-        return _to_nchw(self.run(_to_nhwc(x), resolve_compute(None)), x)
+        return to_nchw(self.run(to_nhwc(x), resolve_compute(None)), x)
 
 
-class Stage(_Trainable, nn.Module):
+class Stage(Trainable, nn.Module):
     """skip_proj -> blocks -> resample  (unet_convnext.py:151-199)."""
 
     def __init__(self, dim_in, dim_out, n_spatial_dims, depth=1, drop_path=0.0, layer_scale_init_value=1e-6, mode="down", skip_project=False):
@@ -666,7 +612,7 @@ class Stage(_Trainable, nn.Module):
 
     def project(self, x: torch.Tensor, skip: torch.Tensor, compute: int) -> torch.Tensor:
         """skip_proj(cat([x, skip], channels)) without the concatenation: W[:, :C] x + b, then + W[:, C:] skip through the residual operand."""
-        compute = _site(compute, "skip")
+        compute = site(compute, "skip", BF16_SITES)
         n, H, W, C_ = x.shape
         if tuple(skip.shape) != tuple(x.shape):
             raise ValueError(f"the skip must have the stream's shape {tuple(x.shape)}, got {tuple(skip.shape)}")
@@ -695,8 +641,8 @@ class Stage(_Trainable, nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(n, C, H, W), or (n, 2 C, H, W) = cat([x, skip]) for a stage with skip_proj -> the stage's output, channels first.  Under grad only
         after set_trainable()."""
-        train = _wants_graph(self, x)
-        _gpu(x)
+        train = wants_graph(self, x, _refuse)
+        gpu_only(x, "UNetConvNext")
         compute = resolve_compute(None)
         if train:
             xl = x.to(torch.float32).permute(0, 2, 3, 1)
@@ -705,12 +651,12 @@ class Stage(_Trainable, nn.Module):
             C_ = self.skip_proj.weight.shape[0]
             return stage_train(self, xl[..., :C_].contiguous(), compute, xl[..., C_:].contiguous()).permute(0, 3, 1, 2).to(x.dtype)
         if isinstance(self.skip_proj, nn.Identity):
-            return _to_nchw(self.run(_to_nhwc(x), compute), x)
+            return to_nchw(self.run(to_nhwc(x), compute), x)
         C_ = self.skip_proj.weight.shape[0]
-        return _to_nchw(self.run(_to_nhwc(x[:, :C_]), compute, _to_nhwc(x[:, C_:])), x)
+        return to_nchw(self.run(to_nhwc(x[:, :C_]), compute, to_nhwc(x[:, C_:])), x)
 
 
-class UNetConvNext(_Trainable, nn.Module):
+class UNetConvNext(Trainable, ComputeSwitch, nn.Module):
     """models/unet_convnext.py:202-283 -- same constructor, attributes, parameters and forward contract."""
 
     def __init__(self, in_T, dset_metadata, stages: int = 4, blocks_per_stage: int = 1, blocks_at_neck: int = 1, n_spatial_dims: int = 2,
@@ -738,7 +684,6 @@ class UNetConvNext(_Trainable, nn.Module):
         self.neck = Stage(encoder_dims[-1], encoder_dims[-1], n_spatial_dims, blocks_at_neck, mode="neck")
         self.decoder = nn.ModuleList(decoder)
         self.dim_in, self.dim_out, self.stages = dim_in, dim_out, stages
-        self.compute: Optional[str] = None
         self._cache = _PackCache()
 
     def trained_parameters(self):
@@ -747,15 +692,9 @@ class UNetConvNext(_Trainable, nn.Module):
         given: pass it THIS list, not parameters()."""
         return [p for n, p in self.named_parameters() if not n.endswith("resample.block.0.bias")]
 
-    def set_compute(self, mode: Optional[str]):
-        if mode is not None and mode not in K.COMPUTE:
-            raise ValueError("compute must be None, 'fp32' or 'bf16'")
-        self.compute = mode
-        return self
-
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x (b, t, c, h, w) -> (b, 1, c, h, w)   (unet_convnext.py:269-283).  Under grad only after set_trainable()."""
-        train = _wants_graph(self, x)
+        train = wants_graph(self, x, _refuse)
         if x.dim() != 5:
             raise ValueError(f"expected (B, T, C, H, W), got {tuple(x.shape)}")
         b, t, c, h, w = x.shape
@@ -764,7 +703,7 @@ class UNetConvNext(_Trainable, nn.Module):
         div = 2 ** self.stages
         if h % div or w % div:
             raise ValueError(f"H and W must be multiples of 2 ** stages = {div} (the decoder's skips would not match), got {h} x {w}")
-        _gpu(x)
+        gpu_only(x, "UNetConvNext")
         compute = resolve_compute(self.compute)
         if train:
             return convnext_train_forward(self, x, compute)

@@ -24,6 +24,7 @@ from . import _lib as L
 from . import kernels as K
 from . import stages as S
 from .attn_backbone import _PackCache, _no_autograd, resolve_compute
+from .model_shell import ComputeSwitch
 from .tante import TanteMetadata, s_emb_init, t_emb_init
 from . import options as _O
 
@@ -343,7 +344,7 @@ def generate_coords(h: int, w: int, device) -> torch.Tensor:
     return torch.stack([xs.flatten(), ys.flatten()], dim=-1).contiguous()
 
 
-class CViT(nn.Module):
+class CViT(ComputeSwitch, nn.Module):
     def __init__(self, in_T, dset_metadata: TanteMetadata = None, out_steps=4, patch_size: tuple = (1, 16, 16),
                  grid_size: tuple = (128, 128), latent_dim: int = 256, emb_dim: int = 256, depth: int = 3, num_heads: int = 8,
                  dec_emb_dim: int = 256, dec_num_heads: int = 8, dec_depth: int = 1, num_mlp_layers: int = 1, mlp_ratio: int = 1,
@@ -375,15 +376,8 @@ class CViT(nn.Module):
         self.mlp = Mlp(in_dim=dec_emb_dim, num_layers=num_mlp_layers, hidden_dim=dec_emb_dim, out_dim=out_dim, layer_norm_eps=layer_norm_eps)
         self.norm1 = nn.LayerNorm(emb_dim, eps=layer_norm_eps)
         self.norm2 = nn.LayerNorm(dec_emb_dim, eps=layer_norm_eps)
-        self.compute: Optional[str] = None
         self._cache = _PackCache()
         self._coord_cache = _PackCache()
-
-    def set_compute(self, mode: Optional[str]):
-        if mode is not None and mode not in K.COMPUTE:
-            raise ValueError("compute must be None, 'fp32' or 'bf16'")
-        self.compute = mode
-        return self
 
     # ---- coordinate embedding (cvit.py:434-446): input independent, so the default full-grid queries are cached per weight version
     def _embed_coords(self, coords: torch.Tensor, compute: int) -> torch.Tensor:

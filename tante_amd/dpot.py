@@ -20,7 +20,7 @@ torch allocates, reshapes and makes the one copy named above.
 
 Inference is the default: a model whose parameters require a gradient refuses under grad (and in train()), as it always did.  Training is
 opt-in through `model.set_trainable()`.  An opted-in model called under grad takes dpot_train_forward: the same arithmetic as a graph of
-the training nodes of tante_amd/autograd.py (Im2colFn, LinearFn with K chunks, ActFn, DeconvFn / Col2imFn) and afno.PosRowsFn, with three
+the training nodes of tante_amd/autograd.py (Im2colFn, LinearFn with K chunks, ActFn, DeconvFn / Col2imFn, PosRowsFn), with three
 nodes of this module: DpotFilterFn (forward the unchanged tante_dpot_filter, bit-identical to inference; backward tante_dpot_filter_bwd:
 the forward's launches 1 .. 3 again for X and U, then the chain in reverse against the conjugate-transposed tables, the block MLP against
 the conjugated transposed weights, one wave per 16 x 16 tile of a weight gradient), GroupNormFn (tante_groupnorm_bwd: statistics as the
@@ -45,6 +45,7 @@ from . import kernels as K
 from . import stages as S
 from .attn_backbone import _PackCache, resolve_compute
 from .dft_tables import cis, device_tables, pack_tables
+from .model_shell import ComputeSwitch, Trainable, gpu_only, inference_only, wants_graph
 
 MAX_GRID = 64       # token-grid points per axis the mixer serves
 MAX_BLOCK = 512     # channels per block
@@ -125,8 +126,7 @@ def groupnorm(x: torch.Tensor, G: int, gamma: Optional[torch.Tensor], beta: Opti
     HW = x.numel() // max(B * C_, 1)
     lib = L.lib()
     y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    nbytes = max(int(lib.tante_groupnorm_workspace_bytes(B, HW, C_, G)), 0)      # (-1: the call below refuses by name)
-    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    work, nbytes = K.workspace(lib.tante_groupnorm_workspace_bytes(B, HW, C_, G), x.device)      # (-1: the call below refuses by name)
     L.check(lib.tante_groupnorm(K._p(x), B, HW, C_, G, float(eps), K._p(gamma), K._p(beta), K._p(y), K._DT[out_dtype], K._p(work), nbytes,
                                 K._stream()), "tante_groupnorm")
     return y
@@ -150,8 +150,7 @@ def dpot_filter(x: torch.Tensor, residual: Optional[torch.Tensor], w1: torch.Ten
                 "tante_dpot_filter")
     if out is None:
         out = torch.empty_like(x)
-    nbytes = int(lib.tante_dpot_filter_workspace_bytes(B, H, W, C_, bs, modes))
-    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    work, nbytes = K.workspace(lib.tante_dpot_filter_workspace_bytes(B, H, W, C_, bs, modes), x.device)
     L.check(lib.tante_dpot_filter(K._p(x), K._p(residual), B, H, W, C_, bs, modes, hidden_factor, K._p(_twiddles(H, W, modes, x.device)), K._p(w1),
                                   K._p(b1), K._p(w2), K._p(b2), K._p(out), K._p(work), nbytes, K._stream()), "tante_dpot_filter")
     return out
@@ -173,8 +172,7 @@ def groupnorm_bwd(dy: torch.Tensor, x: torch.Tensor, G: int, gamma: Optional[tor
         dgamma = torch.empty(C_, dtype=torch.float32, device=x.device)
         dbeta = torch.empty(C_, dtype=torch.float32, device=x.device)
         accumulate = False
-    nbytes = max(int(lib.tante_groupnorm_bwd_workspace_bytes(B, HW, C_, G)), 0)      # (-1: the call below refuses by name)
-    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    work, nbytes = K.workspace(lib.tante_groupnorm_bwd_workspace_bytes(B, HW, C_, G), x.device)  # (-1: the call below refuses by name)
     L.check(lib.tante_groupnorm_bwd(K._p(dy), K._DT[dy.dtype], K._p(x), B, HW, C_, G, float(eps), K._p(gamma), K._p(dx), K._p(dgamma), K._p(dbeta),
                                     int(accumulate), K._p(work), nbytes, K._stream()), "tante_groupnorm_bwd")
     return dx, dgamma, dbeta
@@ -197,20 +195,12 @@ def dpot_filter_bwd(dout: torch.Tensor, x: torch.Tensor, w1: torch.Tensor, b1: t
         grads = [torch.empty(t.shape, dtype=torch.float32, device=x.device) for t in (w1, b1, w2, b1)]
         accumulate = False
     dx = torch.empty_like(x)
-    nbytes = int(lib.tante_dpot_filter_bwd_workspace_bytes(B, H, W, C_, bs, modes))
-    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    work, nbytes = K.workspace(lib.tante_dpot_filter_bwd_workspace_bytes(B, H, W, C_, bs, modes), x.device)
     L.check(lib.tante_dpot_filter_bwd(K._p(dout), K._p(x), B, H, W, C_, bs, modes, K._p(_twiddles(H, W, modes, x.device)),
                                       K._p(_twiddles_bwd(H, W, modes, x.device)), K._p(w1), K._p(b1), K._p(w2), K._p(dx), K._p(grads[0]),
                                       K._p(grads[1]), K._p(grads[2]), K._p(grads[3]), int(accumulate), K._p(work), nbytes, K._stream()),
             "tante_dpot_filter_bwd")
     return (dx, *grads)
-
-
-def _slots(ctx, params, first: int):
-    """The parameters' gradient slots (autograd._grad_slot) where EVERY one of them exists and is wanted, else None."""
-    from .autograd import _grad_slot
-    slots = [_grad_slot(p) if ctx.needs_input_grad[first + i] else None for i, p in enumerate(params)]
-    return slots if all(s is not None for s in slots) else None
 
 
 class DpotFilterFn(Function):
@@ -230,10 +220,11 @@ class DpotFilterFn(Function):
 
     @staticmethod
     def backward(ctx, dout):
+        from .autograd import grad_slots
         (x,) = ctx.saved_tensors
         w1, b1, w2, _ = ctx.params
         dout = dout.contiguous()
-        slots = _slots(ctx, ctx.params, 2)
+        slots = grad_slots(ctx, ctx.params, 2)
         res = dpot_filter_bwd(dout, x, w1.detach(), b1.detach(), w2.detach(), ctx.modes, slots, slots is not None)
         gs = [None] * 4 if slots is not None else [g if ctx.needs_input_grad[2 + i] else None for i, g in enumerate(res[1:])]
         return (res[0], dout if ctx.has_res else None, *gs, None)
@@ -253,12 +244,13 @@ class GroupNormFn(Function):
 
     @staticmethod
     def backward(ctx, dy):
+        from .autograd import grad_slots
         (x,) = ctx.saved_tensors
         gamma, beta = ctx.params
         dy = dy.contiguous()
         if gamma is None:
             return groupnorm_bwd(dy, x, ctx.G, None, ctx.eps)[0], None, None, None, None, None
-        slots = _slots(ctx, ctx.params, 1) if beta is not None else None
+        slots = grad_slots(ctx, ctx.params, 1) if beta is not None else None
         if slots is not None:
             dx, _, _ = groupnorm_bwd(dy, x, ctx.G, gamma.detach(), ctx.eps, slots[0], slots[1], True)
             return dx, None, None, None, None, None
@@ -346,8 +338,7 @@ def dpot_train_forward(model: "DPOT", x: torch.Tensor, compute: int) -> torch.Te
     """DPOT.forward with an autograd graph: x (b, t, c, h, w) -> (b, out_timesteps, c, h, w) fp32.  torch allocates, re-lays out (the
     channels-last image with the constant coordinate channels beside the fields, the stacked per-t row gradients, the output's
     channels-first view) and does parameter-sized work; every activation-sized operation is a HIP node."""
-    from .afno import PosRowsFn
-    from .autograd import ActFn, Col2imFn, DeconvFn, LinearFn
+    from .autograd import ActFn, LinearFn, PosRowsFn
     b, T, c, h, w = x.shape
     p, C_ = model.patch_size, model.embed_dim
     Hp, Wp = model.latent_size
@@ -364,11 +355,7 @@ def dpot_train_forward(model: "DPOT", x: torch.Tensor, compute: int) -> torch.Te
         y = block_train(blk, y, compute)
     d, a, z = model.out_layer[0], model.out_layer[2], model.out_layer[4]
     od = model.out_layer_dim
-    if C_ <= S.KMAX:
-        pre = DeconvFn.apply(y.view(b * HW, C_), d.weight, d.bias, b, Hp, Wp, p, False, compute, adt)
-    else:       # the tap matrix (P P Cout, Cin), columns (kh, kw, co), K-chunked by LinearFn; the bias is added by the gather
-        taps = LinearFn.apply(y.view(b * HW, C_), d.weight.permute(2, 3, 1, 0).reshape(-1, C_).contiguous(), None, None, compute, torch.float32)
-        pre = Col2imFn.apply(taps, d.bias, b, Hp, Wp, p, p, 0, od, torch.float32)
+    pre = S.deconv_nhwc_train(y.view(b * HW, C_), d.weight, d.bias, b, Hp, Wp, p, compute, adt)
     img2 = ActFn.apply(pre, L.ACT_GELU_ERF, adt)
     px = ActFn.apply(LinearFn.apply(img2.view(b * h * w, od), _conv1x1(a), a.bias, None, compute, adt), L.ACT_GELU_ERF, adt)
     if od > S.KMAX:
@@ -377,25 +364,12 @@ def dpot_train_forward(model: "DPOT", x: torch.Tensor, compute: int) -> torch.Te
     return out.view(b, h, w, model.out_timesteps, model.out_channels).permute(0, 3, 4, 1, 2)
 
 
-def _wants_graph(module: nn.Module, x: torch.Tensor) -> bool:
-    """True: build the autograd graph (opted in through set_trainable, grad enabled, something to differentiate).  A module that has not
-    opted in refuses as it always did; an opted-in one takes the inference path under no_grad, in train() as in eval() (no dropout)."""
-    if not module._trainable:
-        _inference_only(module)
-        return False
-    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
-
-
 # ---- the reference's modules -------------------------------------------------------------------------------------------------------
-def _gpu(x: torch.Tensor):
-    if not x.is_cuda:
-        raise RuntimeError("tante_amd.DPOT runs on the GPU only (no CPU fallback); move the model and its input to cuda")
+WHY_INFERENCE_ONLY = "the mixer's and GroupNorm's backward are kernels of their own that are not built"
 
 
-def _inference_only(module: nn.Module):
-    if module.training or (torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters())):
-        raise NotImplementedError("tante_amd.DPOT is inference only: training is out of scope (the mixer's and GroupNorm's backward are "
-                                  "kernels of their own that are not built); call .eval() under torch.no_grad()")
+def _refuse(module: nn.Module):
+    inference_only(module, "DPOT", WHY_INFERENCE_ONLY)
 
 
 def _gelu_only(act: str):
@@ -403,7 +377,7 @@ def _gelu_only(act: str):
         raise NotImplementedError(f"act = {act!r} is out of scope: the HIP path evaluates the erf GELU of the reference's config (act 'gelu')")
 
 
-class AFNO2D(nn.Module):
+class AFNO2D(Trainable, nn.Module):
     """The truncated-mode Fourier mixer  (dpot.py:21-102): tante_dpot_filter."""
 
     def __init__(self, width=32, num_blocks=8, channel_first=False, sparsity_threshold=0.01, modes=32, hard_thresholding_fraction=1,
@@ -428,13 +402,6 @@ class AFNO2D(nn.Module):
         self.b1 = nn.Parameter(self.scale * torch.rand(2, num_blocks, bs * hidden_size_factor))
         self.w2 = nn.Parameter(self.scale * torch.rand(2, num_blocks, bs * hidden_size_factor, bs))
         self.b2 = nn.Parameter(self.scale * torch.rand(2, num_blocks, bs))
-        self._trainable = False
-
-    def set_trainable(self, flag: bool = True):
-        """Opt in to (or out of) training: under grad, forward then builds an autograd graph instead of refusing.  Not a constructor
-        argument and not part of the state_dict; propagates to the children and returns self."""
-        self._trainable = bool(flag)
-        return self
 
     def run(self, x: torch.Tensor, residual: Optional[torch.Tensor]) -> torch.Tensor:
         """x (B, H, W, C) fp32 channels-last -> filter(x) (+ residual); the weights are read where the parameters lie."""
@@ -443,10 +410,10 @@ class AFNO2D(nn.Module):
 
     def forward(self, x: torch.Tensor, spatial_size=None) -> torch.Tensor:
         """(B, H, W, C), or (B, C, H, W) with channel_first, -> the same layout  (dpot.py:47-102).  Under grad only after set_trainable()."""
-        train = _wants_graph(self, x)
+        train = wants_graph(self, x, _refuse)
         if x.dim() != 4:
             raise NotImplementedError("the DPOT mixer is two-dimensional here: n_spatial_dims = 3 is out of scope")
-        _gpu(x)
+        gpu_only(x, "DPOT")
         if train:
             xl = x.to(torch.float32).permute(0, 2, 3, 1) if self.channel_first else x.to(torch.float32)
             y = DpotFilterFn.apply(xl, None, self.w1, self.b1, self.w2, self.b2, self.modes)
@@ -473,7 +440,7 @@ class Mlp(nn.Module):
         self.fc2 = nn.Linear(hidden_features, out_features)
 
 
-class Block(nn.Module):
+class Block(Trainable, nn.Module):
     """n1 = GN1(x); f = filter(n1) (+ x under double_skip); y = mlp(GN2(f)) + (f if double_skip else x)   (dpot.py:121-172)."""
 
     def __init__(self, mixing_type="afno", double_skip=True, width=32, n_blocks=4, mlp_ratio=1.0, channel_first=True, modes=32, drop=0.0,
@@ -494,14 +461,6 @@ class Block(nn.Module):
                                  nn.Conv2d(in_channels=mlp_hidden_dim, out_channels=width, kernel_size=1, stride=1))
         self.double_skip = double_skip
         self._cache = _PackCache()
-        self._trainable = False
-
-    def set_trainable(self, flag: bool = True):
-        """Opt in to (or out of) training: under grad, forward then builds an autograd graph instead of refusing.  Not a constructor
-        argument and not part of the state_dict; propagates to the children and returns self."""
-        self._trainable = bool(flag)
-        self.filter.set_trainable(flag)
-        return self
 
     def _packed(self, compute: int):
         fc1, fc2 = self.mlp[0], self.mlp[2]
@@ -527,20 +486,20 @@ class Block(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(B, C, H, W) -> (B, C, H, W), as the reference's Block takes its images (GroupNorm and the 1 x 1 convs act on dim 1)."""
-        train = _wants_graph(self, x)
+        train = wants_graph(self, x, _refuse)
         if x.dim() != 4:
             raise NotImplementedError("the DPOT block is two-dimensional here: n_spatial_dims = 3 is out of scope")
         if not self.filter.channel_first:
             raise NotImplementedError("Block(channel_first=False) hands its channel-first image to a channels-last filter in the reference; "
                                       "that mixes channels with rows and is not reproduced")
-        _gpu(x)
+        gpu_only(x, "DPOT")
         if train:
             return block_train(self, x.to(torch.float32).permute(0, 2, 3, 1), resolve_compute(None)).permute(0, 3, 1, 2).to(x.dtype)
         y = self.run(x.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous(), resolve_compute(None))
         return y.permute(0, 3, 1, 2).to(x.dtype)
 
 
-class PatchEmbed(nn.Module):
+class PatchEmbed(Trainable, nn.Module):
     """Conv(p x p / p) -> GELU -> Conv(1 x 1)  (dpot.py:175-197): tante_im2col + two GEMMs, channels-last rows out."""
 
     def __init__(self, img_size, patch_size=16, in_chans=3, embed_dim=768, out_dim=128, act="gelu"):
@@ -556,13 +515,6 @@ class PatchEmbed(nn.Module):
         self.proj = nn.Sequential(nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size), self.act,
                                   nn.Conv2d(embed_dim, out_dim, kernel_size=1, stride=1))
         self._cache = _PackCache()
-        self._trainable = False
-
-    def set_trainable(self, flag: bool = True):
-        """Opt in to (or out of) training: under grad, forward then builds an autograd graph instead of refusing.  Not a constructor
-        argument and not part of the state_dict; propagates to the children and returns self."""
-        self._trainable = bool(flag)
-        return self
 
     def _packed(self, compute: int):
         c0, c2 = self.proj[0], self.proj[2]
@@ -582,8 +534,8 @@ class PatchEmbed(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(B, C, H, W) -> (B, out_dim, H', W')  (dpot.py:193-197).  Under grad only after set_trainable()."""
-        train = _wants_graph(self, x)
-        _gpu(x)
+        train = wants_graph(self, x, _refuse)
+        gpu_only(x, "DPOT")
         B, C_, H, W = x.shape
         assert H == self.img_size[0] and W == self.img_size[1], \
             f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
@@ -594,7 +546,7 @@ class PatchEmbed(nn.Module):
         return y.view(B, self.out_size[0], self.out_size[1], self.out_dim).permute(0, 3, 1, 2).to(x.dtype)
 
 
-class TimeAggregator(nn.Module):
+class TimeAggregator(Trainable, nn.Module):
     """out[..., j] = sum_t sum_i w[t, i, j] x[..., t, i] (cos(t gamma_i) for 'exp_mlp')  (dpot.py:200-221): one K = T C GEMM."""
 
     def __init__(self, n_channels, n_timesteps, out_channels, type="mlp"):
@@ -609,13 +561,6 @@ class TimeAggregator(nn.Module):
         if type == "exp_mlp":
             self.gamma = nn.Parameter(2 ** torch.linspace(-10, 10, out_channels).unsqueeze(0))
         self._cache = _PackCache()
-        self._trainable = False
-
-    def set_trainable(self, flag: bool = True):
-        """Opt in to (or out of) training: under grad, forward then builds an autograd graph instead of refusing.  Not a constructor
-        argument and not part of the state_dict; propagates to the children and returns self."""
-        self._trainable = bool(flag)
-        return self
 
     def _packed(self, compute: int):
         gamma = self.gamma if self.type == "exp_mlp" else None
@@ -654,8 +599,8 @@ class TimeAggregator(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(B, X, Y, T, C) -> (B, X, Y, C)  (dpot.py:213-221).  Under grad only after set_trainable()."""
-        train = _wants_graph(self, x)
-        _gpu(x)
+        train = wants_graph(self, x, _refuse)
+        gpu_only(x, "DPOT")
         B, X, Y, T, C_ = x.shape
         if train:
             rows = x.to(torch.float32).permute(0, 3, 1, 2, 4).reshape(B * T * X * Y, C_)
@@ -665,7 +610,7 @@ class TimeAggregator(nn.Module):
         return self.run(rows, B, T, X * Y, resolve_compute(None)).view(B, X, Y, C_).to(x.dtype)
 
 
-class DPOT(nn.Module):
+class DPOT(Trainable, ComputeSwitch, nn.Module):
     """models/dpot.py:223-350 -- same constructor, attributes, parameters and forward contract."""
 
     def __init__(self, in_T: int, dset_metadata, patch_size=16, mixing_type="afno", out_timesteps=1, n_blocks=4, embed_dim=768,
@@ -711,31 +656,15 @@ class DPOT(nn.Module):
         self.mixing_type = mixing_type
         self.patch_size, self.img_size, self.out_layer_dim = patch_size, img_size, out_layer_dim
         self.output_length = out_timesteps
-        self.compute: Optional[str] = None
         self._cache = _PackCache()
         self._pos = _PackCache()
         self._stage = {}
-        self._trainable = False
-
-    def set_trainable(self, flag: bool = True):
-        """Opt in to (or out of) training: under grad, forward then builds an autograd graph instead of refusing.  Not a constructor
-        argument and not part of the state_dict; propagates to the children and returns self."""
-        self._trainable = bool(flag)
-        for m in (self.patch_embed, self.time_agg_layer, *self.blocks):
-            m.set_trainable(flag)
-        return self
 
     def trained_parameters(self):
         """Every parameter except cls_head.*: the reference computes cls_pred and discards it (dpot.py:343-344), so those weights never
         receive a gradient and torch's AdamW never touches them.  FlatAdamW decays everything it is given: pass it THIS list, not
         parameters()."""
         return [p for n, p in self.named_parameters() if not n.startswith("cls_head.")]
-
-    def set_compute(self, mode: Optional[str]):
-        if mode is not None and mode not in K.COMPUTE:
-            raise ValueError("compute must be None, 'fp32' or 'bf16'")
-        self.compute = mode
-        return self
 
     def get_grid_3d(self, T: int, device) -> torch.Tensor:
         """The three coordinate channels (T, 3, h, w) fp32: linspace(0, 1, n) over x, y and t  (dpot.py:309-319)."""
@@ -758,24 +687,17 @@ class DPOT(nn.Module):
 
     def _packed(self, compute: int):
         d, a, z = self.out_layer[0], self.out_layer[2], self.out_layer[4]
-        p = self.patch_size
-
-        def build():
-            if self.embed_dim <= S.KMAX:
-                dec = K.pack_weight(d.weight, d.bias, compute, L.W_DECONV_NHWC, N=d.weight.shape[1] * p * p, K=d.weight.shape[0], P=p,
-                                    C_other=d.weight.shape[1])
-            else:       # the tap matrix (P P Cout, Cin), columns (kh, kw, co), K-chunked; the bias is added by the gather
-                dec = S.pack_linear_chunks(d.weight.detach().permute(2, 3, 1, 0).reshape(-1, d.weight.shape[0]).contiguous(), None, compute)
-            return (dec, S.pack_linear_chunks(a.weight.detach().reshape(a.weight.shape[0], -1), a.bias, compute),
-                    S.pack_linear_chunks(z.weight.detach().reshape(z.weight.shape[0], -1), z.bias, compute))
-        return self._cache.get(compute, [d.weight, d.bias, a.weight, a.bias, z.weight, z.bias], build)
+        return self._cache.get(compute, [d.weight, d.bias, a.weight, a.bias, z.weight, z.bias], lambda: (
+            S.pack_deconv_nhwc(d.weight, d.bias, self.patch_size, compute),
+            S.pack_linear_chunks(a.weight.detach().reshape(a.weight.shape[0], -1), a.bias, compute),
+            S.pack_linear_chunks(z.weight.detach().reshape(z.weight.shape[0], -1), z.bias, compute)))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x (b, t, c, h, w) -> (b, out_timesteps, c, h, w)   (dpot.py:323-350).  Under grad only after set_trainable()."""
-        train = _wants_graph(self, x)
+        train = wants_graph(self, x, _refuse)
         if x.dim() != 5 or x.shape[1] != self.in_timesteps or x.shape[2] != self.in_channels:
             raise ValueError(f"expected (B, {self.in_timesteps}, {self.in_channels}, H, W), got {tuple(x.shape)}")
-        _gpu(x)
+        gpu_only(x, "DPOT")
         b, T, c, h, w = x.shape
         if (h, w) != tuple(self.img_size):
             raise ValueError(f"Input image size ({h}*{w}) doesn't match model ({self.img_size[0]}*{self.img_size[1]}).")
@@ -796,14 +718,7 @@ class DPOT(nn.Module):
             y = blk.run(y, compute)
         dec, mid, last = self._packed(compute)
         od = self.out_layer_dim
-        if isinstance(dec, K.PackedWeight):
-            img = torch.empty(b, h, w, od, dtype=adt, device=x.device)
-            K.deconv(y.view(b * HW, C_), dec, img, n_img=b, Hi=Hp, Wi=Wp, P=p, Cout=od, nchw_out=False, act=L.ACT_GELU_ERF)
-        else:
-            taps = S.linear_chunks(y.view(b * HW, C_), dec, torch.float32)
-            pre = K.col2im_nhwc(taps, b, Hp, Wp, p, p, 0, od, self.out_layer[0].bias.detach(), torch.float32)
-            img = torch.empty(b, h, w, od, dtype=adt, device=x.device)
-            L.check(L.lib().tante_act_fwd(pre.data_ptr(), L.F32, img.data_ptr(), K._DT[adt], pre.numel(), L.ACT_GELU_ERF, K._stream()), "tante_act_fwd")
+        img = S.deconv_nhwc(y.view(b * HW, C_), dec, self.out_layer[0].bias.detach(), b, Hp, Wp, p, od, adt, L.ACT_GELU_ERF)
         px = S.linear_chunks(img.view(b * h * w, od), mid, adt, L.ACT_GELU_ERF)
         if len(last) != 1:
             raise NotImplementedError("out_layer_dim above 512 is out of scope: the last pixel-row linear writes channels first from one GEMM")

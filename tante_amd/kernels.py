@@ -41,6 +41,12 @@ def act_torch_dtype(compute: int) -> torch.dtype:
     return torch.bfloat16 if compute == L.BF16 else torch.float32
 
 
+def workspace(nbytes: int, device) -> Tuple[torch.Tensor, int]:
+    """A byte buffer for an entry point that asked for `nbytes` (never an empty one: 16 bytes at least) and the count to hand to it:
+    a size function's -1 becomes 0, so that the entry point refuses by name."""
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device), max(int(nbytes), 0)
+
+
 class PackedWeight:
     """A weight in the GEMM's streaming layout (+ its fp32 bias, LayerNorm shift folded in)."""
     __slots__ = ("w", "bias", "N", "K", "compute", "geom")

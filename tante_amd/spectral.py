@@ -209,7 +209,7 @@ def _deconv_stage_train(rows: torch.Tensor, dc: nn.ConvTranspose2d, n_img: int, 
         # overlapping taps (enc_dec_cnn.py:128-184): tap matrix by one GEMM -> gather-sum + bias -> bilinear resize to (h P, w P)
         if dc.weight.shape[0] > S.KMAX:
             raise NotImplementedError("overlapping transposed conv with more than 512 input channels")
-        w2 = dc.weight.permute(2, 3, 1, 0).reshape(-1, dc.weight.shape[0]).contiguous()   # rows (kh, kw, co), a parameter-sized re-layout
+        w2 = S.deconv_taps(dc.weight).contiguous()                                      # rows (kh, kw, co), a parameter-sized re-layout
         taps = LinearFn.apply(rows, w2, None, None, compute, adt)
         full = Col2imFn.apply(taps, dc.bias, n_img, h, w, P, st, pd, Cout, adt)      # (n, Hf, Wf, Cout)
         return CropResizeFn.apply(full, n_img, Cout, full.shape[1], full.shape[2], (0, 0), h * P, w * P, nchw_out, out_dtype)

@@ -119,10 +119,54 @@ def _rows_to_nchw(y2d: torch.Tensor, n: int, h: int, w: int) -> torch.Tensor:
     return y2d.view(n, h, w, -1).permute(0, 3, 1, 2).float().contiguous()
 
 
+def deconv_taps(weight: torch.Tensor) -> torch.Tensor:
+    """ConvTranspose2d weight (Cin, Cout, P, P) -> the tap matrix (P P Cout, Cin), rows (kh, kw, co): a parameter-sized re-layout."""
+    return weight.permute(2, 3, 1, 0).reshape(-1, weight.shape[0])
+
+
+# ---- the kernel = stride = P transposed convolution on channels-last rows: one scatter GEMM up to KMAX input channels, the K-chunked tap
+# GEMM + tante_col2im_nhwc beyond --------------------------------------------------------------------------------------------------------
+def pack_deconv_nhwc(weight: torch.Tensor, bias: Optional[torch.Tensor], P: int, compute: int):
+    """weight (Cin, Cout, P, P) -> a K.PackedWeight with the bias in it (Cin <= KMAX), or the K-chunks of the tap matrix WITHOUT it: on
+    that route the gather of deconv_nhwc adds the bias."""
+    cin, cout = weight.shape[0], weight.shape[1]
+    if cin <= KMAX:
+        return K.pack_weight(weight, bias, compute, L.W_DECONV_NHWC, N=cout * P * P, K=cin, P=P, C_other=cout)
+    return pack_linear_chunks(deconv_taps(weight.detach()).contiguous(), None, compute)
+
+
+def deconv_nhwc(rows: torch.Tensor, packed, bias: Optional[torch.Tensor], n: int, Hi: int, Wi: int, P: int, Cout: int,
+                out_dtype: torch.dtype = torch.float32, act: int = L.ACT_NONE) -> torch.Tensor:
+    """rows (n Hi Wi, Cin) with `packed` from pack_deconv_nhwc -> act(deconv(rows)) (n, P Hi, P Wi, Cout) in out_dtype.  The scatter GEMM
+    applies `act` in its epilogue; the tap route gathers in fp32 and applies it (and the rounding to out_dtype) in tante_act_fwd."""
+    if isinstance(packed, K.PackedWeight):
+        img = torch.empty(n, P * Hi, P * Wi, Cout, dtype=out_dtype, device=rows.device)
+        return K.deconv(rows, packed, img, n_img=n, Hi=Hi, Wi=Wi, P=P, Cout=Cout, nchw_out=False, act=act)
+    taps = linear_chunks(rows, packed, torch.float32)
+    pre = K.col2im_nhwc(taps, n, Hi, Wi, P, P, 0, Cout, bias, torch.float32)
+    if act == L.ACT_NONE and out_dtype == torch.float32:
+        return pre
+    img = torch.empty(n, P * Hi, P * Wi, Cout, dtype=out_dtype, device=rows.device)
+    L.check(L.lib().tante_act_fwd(pre.data_ptr(), L.F32, img.data_ptr(), K._DT[out_dtype], pre.numel(), act, K._stream()), "tante_act_fwd")
+    return img
+
+
+def deconv_nhwc_train(rows: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], n: int, Hi: int, Wi: int, P: int, compute: int,
+                      out_dtype: torch.dtype) -> torch.Tensor:
+    """deconv_nhwc as training nodes, PRE-activation: DeconvFn up to KMAX input channels (output in out_dtype), LinearFn on the tap matrix
+    + Col2imFn beyond (fp32: the caller's ActFn rounds).  weight (Cin, Cout, P, P) is a parameter or a differentiable float64 fold of
+    one, rounded to fp32 once here."""
+    from .autograd import Col2imFn, DeconvFn, LinearFn
+    cin, cout = weight.shape[0], weight.shape[1]
+    if cin <= KMAX:
+        return DeconvFn.apply(rows, weight.float().contiguous(), bias, n, Hi, Wi, P, False, compute, out_dtype)
+    taps = LinearFn.apply(rows, deconv_taps(weight).float().contiguous(), None, None, compute, torch.float32)
+    return Col2imFn.apply(taps, bias, n, Hi, Wi, P, P, 0, cout, torch.float32)
+
+
 def deconv_taps_pack(weight: torch.Tensor, bias: Optional[torch.Tensor], compute: int):
     """ConvTranspose2d weight (Cin, Cout, P, P) -> (packed (P*P*Cout, Cin) tap GEMM weight without bias, bias) for overlapping stages."""
-    w = weight.detach()
-    w2 = w.permute(2, 3, 1, 0).reshape(-1, w.shape[0]).contiguous()
+    w2 = deconv_taps(weight.detach()).contiguous()
     if w2.shape[1] > KMAX:
         raise NotImplementedError("overlapping transposed conv with more than 512 input channels")
     return K.pack_weight(w2, None, compute, L.W_LINEAR, N=w2.shape[0], K=w2.shape[1]), (None if bias is None else bias.detach())

@@ -30,6 +30,7 @@ from . import kernels as K
 from . import route as R
 from . import stages as S
 from .attn_backbone import Attn_Backbone, _PackCache, _gpu_only, _no_autograd, _wants_grad, resolve_compute
+from .model_shell import ComputeSwitch
 
 # models/enc_dec_cnn.py:39-46
 Patch_map = {64: (4, 4, 4), 32: (4, 4, 2), 16: (4, 2, 2), 8: (2, 2, 2), 4: (2, 2, 1), 2: (2, 1, 1)}
@@ -442,7 +443,7 @@ def t_series(IP, frame_interval):
     return torch.tensor(seq)
 
 
-class TANTE(nn.Module):
+class TANTE(ComputeSwitch, nn.Module):
     def __init__(self, in_T, dset_metadata: TanteMetadata = None, taylor_order: int = 1, frame_interval: float = 1.0,
                  output_length=1, attn_axes: str = "THWTHWTHW", expanded_channel: int = 128, n_head: int = 8,
                  mlp_ratio: float = 1.0, dropout: float = 0.0, enc_dec_type: str = "cnn", embed_dim: int = 256,
@@ -489,15 +490,8 @@ class TANTE(nn.Module):
         if not self.deg:
             self.interprators = nn.ModuleList([interprator(self.C, self.H_p * self.W_p) for _ in range(taylor_order)])
             self.modifiers = nn.ModuleList([film(self.C, in_dim=1) for _ in range(taylor_order)])
-        self.compute: Optional[str] = None       # None: follow torch.autocast; "fp32" / "bf16": pinned
         self.fused_head = True                   # bf16: fused derivative head + Taylor accumulation when the shape allows
         self._film_cache = _PackCache()
-
-    def set_compute(self, mode: Optional[str]):
-        if mode is not None and mode not in K.COMPUTE:
-            raise ValueError("compute must be None, 'fp32' or 'bf16'")
-        self.compute = mode
-        return self
 
     def _apply(self, fn, *a, **k):               # keep t_seq with the parameters on .to()/.cuda()
         super()._apply(fn, *a, **k)

@@ -31,6 +31,7 @@ from . import kernels as K
 from . import options as _O
 from . import stages as S
 from .attn_backbone import _PackCache, resolve_compute
+from .model_shell import ComputeSwitch, gpu_only, inference_only, site, to_nchw, to_nhwc
 
 CONV_MAX_CIN, CONV_MAX_COUT = 2048, 1024     # channels tante_conv3x3_mfma serves
 GATE_MAX_K, GATE_MAX_N = 1024, 256           # gate plus skip channels, coefficients tante_attn_gate serves
@@ -40,11 +41,6 @@ BF16_SITES = ("conv", "gate", "head")        # the groups that take bf16 operand
 # True: the 3 x 3 convolutions and the gates run as tante_conv3x3_mfma / tante_attn_gate; False: tante_im2col + tante_gemm and separate
 # pool / upsample / cat / gate steps, the A/B and parity partner
 MFMA = _O.register("TANTE_UNETATT_MFMA", True, __name__, "MFMA")
-
-
-def _site(compute: int, site: str) -> int:
-    """The compute mode of one group: the caller's for the groups in BF16_SITES, fp32 for the rest."""
-    return compute if site in BF16_SITES else L.F32
 
 
 # ---- host side of the kernels: the predicates' mirrors, the folds, the wrappers -----------------------------------------------------------
@@ -149,23 +145,7 @@ def attn_gate(g: torch.Tensor, x: torch.Tensor, stream: torch.Tensor, N: int, co
 
 
 # ---- the reference's modules -------------------------------------------------------------------------------------------------------
-def _gpu(x: torch.Tensor):
-    if not x.is_cuda:
-        raise RuntimeError("tante_amd.AttentionUNet runs on the GPU only (no CPU fallback); move the model and its input to cuda")
-
-
-def _inference_only(module: nn.Module):
-    if module.training or (torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters())):
-        raise NotImplementedError("tante_amd.AttentionUNet is inference only: training is out of scope (batch statistics and the backward of the "
-                                  "convolution are kernels of their own that are not built); call .eval() under torch.no_grad()")
-
-
-def _to_nhwc(x: torch.Tensor) -> torch.Tensor:
-    return x.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
-
-
-def _to_nchw(y: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
-    return y.permute(0, 3, 1, 2).contiguous().to(like.dtype)
+WHY_INFERENCE_ONLY = "batch statistics and the backward of the convolution are kernels of their own that are not built"
 
 
 def _source(a: torch.Tensor, form: int, b: Optional[torch.Tensor]) -> torch.Tensor:
@@ -182,7 +162,7 @@ def _source(a: torch.Tensor, form: int, b: Optional[torch.Tensor]) -> torch.Tens
 def _conv_bn_act(a: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, cache: _PackCache, slot: str, compute: int, form: int = PLAIN,
                  b: Optional[torch.Tensor] = None, mfma: Optional[bool] = None) -> torch.Tensor:
     """relu(bn(conv3x3(source))) on channels-last fp32 images -> (n, H, W, Cout) fp32."""
-    compute = _site(compute, "conv")
+    compute = site(compute, "conv", BF16_SITES)
     mfma = MFMA if mfma is None else mfma
     params = [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
     Cout = conv.weight.shape[0]
@@ -232,9 +212,9 @@ class ConvBlock(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(n, Cin, H, W) -> (n, Cout, H, W).  Inference only."""
-        _inference_only(self)
-        _gpu(x)
-        return _to_nchw(self.run(_to_nhwc(x), resolve_compute(None)), x)
+        inference_only(self, "AttentionUNet", WHY_INFERENCE_ONLY)
+        gpu_only(x, "AttentionUNet")
+        return to_nchw(self.run(to_nhwc(x), resolve_compute(None)), x)
 
 
 class UpConv(nn.Module):
@@ -256,9 +236,9 @@ class UpConv(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(n, Cin, H, W) -> (n, Cout, 2 H, 2 W).  Inference only."""
-        _inference_only(self)
-        _gpu(x)
-        return _to_nchw(self.run(_to_nhwc(x), resolve_compute(None)), x)
+        inference_only(self, "AttentionUNet", WHY_INFERENCE_ONLY)
+        gpu_only(x, "AttentionUNet")
+        return to_nchw(self.run(to_nhwc(x), resolve_compute(None)), x)
 
 
 class AttentionBlock(nn.Module):
@@ -291,7 +271,7 @@ class AttentionBlock(nn.Module):
 
     def run(self, gate: torch.Tensor, skip: torch.Tensor, compute: int, mfma: Optional[bool] = None) -> torch.Tensor:
         """gate (n, H, W, Cg), skip (n, H, W, Cx) fp32 channels-last -> skip * psi, (n, H, W, Cx) fp32."""
-        compute = _site(compute, "gate")
+        compute = site(compute, "gate", BF16_SITES)
         mfma = MFMA if mfma is None else mfma
         if tuple(gate.shape[:3]) != tuple(skip.shape[:3]):
             raise ValueError(f"the gate and the skip must cover the same pixels, got {tuple(gate.shape)} and {tuple(skip.shape)}")
@@ -321,13 +301,13 @@ class AttentionBlock(nn.Module):
 
     def forward(self, gate: torch.Tensor, skip_connection: torch.Tensor) -> torch.Tensor:
         """(n, F_g, H, W), (n, F_l, H, W) -> (n, F_l, H, W)  (unet_att.py:70-76).  Inference only."""
-        _inference_only(self)
-        _gpu(gate)
-        _gpu(skip_connection)
-        return _to_nchw(self.run(_to_nhwc(gate), _to_nhwc(skip_connection), resolve_compute(None)), skip_connection)
+        inference_only(self, "AttentionUNet", WHY_INFERENCE_ONLY)
+        gpu_only(gate, "AttentionUNet")
+        gpu_only(skip_connection, "AttentionUNet")
+        return to_nchw(self.run(to_nhwc(gate), to_nhwc(skip_connection), resolve_compute(None)), skip_connection)
 
 
-class AttentionUNet(nn.Module):
+class AttentionUNet(ComputeSwitch, nn.Module):
     """models/unet_att.py:79-175 -- same constructor, attributes, parameters, buffers and forward contract."""
 
     def __init__(self, in_T, dset_metadata=None, depth=4, out_T=4):
@@ -374,18 +354,11 @@ class AttentionUNet(nn.Module):
         self.Conv = nn.Conv2d(64, dim_out, kernel_size=1, stride=1, padding=0)
 
         self.dim_in, self.dim_out = dim_in, dim_out
-        self.compute: Optional[str] = None
         self._cache = _PackCache()
-
-    def set_compute(self, mode: Optional[str]):
-        if mode is not None and mode not in K.COMPUTE:
-            raise ValueError("compute must be None, 'fp32' or 'bf16'")
-        self.compute = mode
-        return self
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x (b, t, c, h, w) -> (b, out_T, c, h, w)   (unet_att.py:126-175)."""
-        _inference_only(self)
+        inference_only(self, "AttentionUNet", WHY_INFERENCE_ONLY)
         if x.dim() != 5:
             raise ValueError(f"expected (B, T, C, H, W), got {tuple(x.shape)}: 3-D fields are out of scope")
         b, t, c, h, w = x.shape
@@ -394,7 +367,7 @@ class AttentionUNet(nn.Module):
         div = 2 ** (self.depth - 1)
         if h % div or w % div:
             raise ValueError(f"H and W must be multiples of 2 ** (depth - 1) = {div} (the gates' skips would not match), got {h} x {w}")
-        _gpu(x)
+        gpu_only(x, "AttentionUNet")
         compute = resolve_compute(self.compute)
         cur = x.detach().to(torch.float32).reshape(b, t * c, h, w).permute(0, 2, 3, 1).contiguous()       # b (t c) h w, channels last
         enc = [self.Conv1.run(cur, compute)]
@@ -405,7 +378,7 @@ class AttentionUNet(nn.Module):
             d = getattr(self, f"Up{i}").run(d, compute)                                    # Upsample read by the staging loop
             s = getattr(self, f"Att{i}").run(d, enc[i - 2], compute)
             d = getattr(self, f"UpConv{i}").run(s, compute, PLAIN, d)                      # cat((s, d)) read by the staging loop
-        hc = _site(compute, "head")
+        hc = site(compute, "head", BF16_SITES)
         pw = self._cache.get(("head", hc), [self.Conv.weight, self.Conv.bias], lambda: S.pack_linear_chunks(
             self.Conv.weight.detach().reshape(self.dim_out, 64).contiguous(), self.Conv.bias.detach(), hc))
         rows = d.view(b * h * w, 64)

@@ -35,6 +35,7 @@ from . import _lib as L
 from . import kernels as K
 from . import stages as S
 from .attn_backbone import _PackCache, resolve_compute
+from .model_shell import ComputeSwitch, gpu_only, inference_only
 
 MAX_DIM, MAX_CH, MAX_PLANES = 512, 512, 65535      # what tante_uno_block serves
 _TABLES = {}
@@ -160,8 +161,7 @@ def _planes(t: torch.Tensor, what: str):
     if t.dtype != torch.float32 or t.dim() != 4:
         raise RuntimeError(f"{what} must be fp32 (n, C, H, W)")
     n, C, H, W = t.shape
-    if not t.is_cuda:
-        raise RuntimeError("tante_amd.UNO runs on the GPU only (no CPU fallback); move the model and its input to cuda")
+    gpu_only(t, "UNO")
     if any(size > 1 and stride != want for size, stride, want in ((W, t.stride(3), 1), (H, t.stride(2), W), (C, t.stride(1), H * W))):
         raise RuntimeError(f"{what} must have dense channel planes (a channel slice of a channels-first buffer at most)")
     return (t.stride(0) if n > 1 else max(t.stride(0), C * H * W)), (n, C, H, W)
@@ -186,23 +186,18 @@ def uno_block(x: torch.Tensor, out: torch.Tensor, m1: int, m2: int, w1: torch.Te
     K._dev(r1, r2, pw_w, pw_b)
     lib = L.lib()
     tables = _tables_on(x.device, Hi, Wi, Ho, Wo, m1, m2, pw)
-    nbytes = int(lib.tante_uno_block_workspace_bytes(n, Ci, Co, Hi, Wi, Ho, Wo, m1, m2, int(pw)))
-    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    work, nbytes = K.workspace(lib.tante_uno_block_workspace_bytes(n, Ci, Co, Hi, Wi, Ho, Wo, m1, m2, int(pw)), x.device)
     L.check(lib.tante_uno_block(x.data_ptr(), xs, n, Ci, Co, Hi, Wi, Ho, Wo, m1, m2, K._p(tables), K._p(r1), K._p(r2), K._p(pw_w), K._p(pw_b),
                                 L.ACT_GELU_ERF if gelu else L.ACT_NONE, out.data_ptr(), os_, K._p(work), nbytes, K._stream()), "tante_uno_block")
     return out
 
 
 # ---- the reference's modules ---------------------------------------------------------------------------------------------------------------
-def _inference_only(module: nn.Module):
-    if module.training or (torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters())):
-        raise NotImplementedError("tante_amd.UNO is inference only: training is out of scope (the backward of the transforms and of the mode mix "
-                                  "are kernels of their own that are not built); call .eval() under torch.no_grad()")
+WHY_INFERENCE_ONLY = "the backward of the transforms and of the mode mix are kernels of their own that are not built"
 
 
 def _fp32_planes(x: torch.Tensor) -> torch.Tensor:
-    if not x.is_cuda:
-        raise RuntimeError("tante_amd.UNO runs on the GPU only (no CPU fallback); move the model and its input to cuda")
+    gpu_only(x, "UNO")
     if x.dim() != 4:
         raise ValueError(f"expected (n, C, H, W), got {tuple(x.shape)}")
     return x.detach().to(torch.float32).contiguous()
@@ -226,7 +221,7 @@ class SpectralConv2d_Uno(nn.Module):
 
     def forward(self, x: torch.Tensor, dim1=None, dim2=None) -> torch.Tensor:
         """(n, Ci, Hi, Wi) -> (n, Co, dim1, dim2).  Inference only."""
-        _inference_only(self)
+        inference_only(self, "UNO", WHY_INFERENCE_ONLY)
         if dim1 is not None:
             self.dim1, self.dim2 = dim1, dim2
         xp = _fp32_planes(x)
@@ -268,7 +263,7 @@ class OperatorBlock_2D(nn.Module):
 
     def forward(self, x: torch.Tensor, dim1=None, dim2=None) -> torch.Tensor:
         """(n, Ci, Hi, Wi) -> (n, Co, dim1, dim2).  Inference only."""
-        _inference_only(self)
+        inference_only(self, "UNO", WHY_INFERENCE_ONLY)
         if dim1 is None:
             dim1, dim2 = self.conv.dim1, self.conv.dim2
         self.conv.dim1, self.conv.dim2 = dim1, dim2
@@ -294,7 +289,7 @@ def block_sizes(D1: int, D2: int):
     return out
 
 
-class UNO(nn.Module):
+class UNO(ComputeSwitch, nn.Module):
     """models/uno.py:175-280 -- same constructor, attributes, parameters and forward contract."""
 
     def __init__(self, in_T, dset_metadata=None, width=32, pad=0, factor=1):
@@ -321,14 +316,7 @@ class UNO(nn.Module):
         self.fc1 = nn.Linear(2 * self.width, 3 * self.width)
         self.fc2 = nn.Linear(3 * self.width + 16, dim_out)
         self.dim_out = dim_out
-        self.compute: Optional[str] = None
         self._cache = _PackCache()
-
-    def set_compute(self, mode: Optional[str]):
-        if mode is not None and mode not in K.COMPUTE:
-            raise ValueError("compute must be None, 'fp32' or 'bf16'")
-        self.compute = mode
-        return self
 
     def _linears(self, compute: int):
         ps = [p for m in (self.fc, self.fc0, self.fc1, self.fc2) for p in (m.weight, m.bias)]
@@ -345,7 +333,7 @@ class UNO(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x (b, t, c, h, w) -> (b, 1, c, h, w)   (uno.py:227-269)."""
-        _inference_only(self)
+        inference_only(self, "UNO", WHY_INFERENCE_ONLY)
         if x.dim() != 5:
             raise ValueError(f"expected (B, T, C, H, W), got {tuple(x.shape)}: 3-D fields are out of scope")
         b, t, c, h, w = x.shape
@@ -358,8 +346,7 @@ class UNO(nn.Module):
         if D1 > MAX_DIM or D2 > MAX_DIM or 8 * fw > MAX_CH or b * 8 * fw > MAX_PLANES:
             raise NotImplementedError(f"tante_amd.UNO: {b} images of {D1} x {D2} (padded) at {8 * fw} channels are out of scope: tante_uno_block serves "
                                       f"up to {MAX_DIM} x {MAX_DIM} planes, {MAX_CH} channels and {MAX_PLANES} (image, channel) planes per call")
-        if not x.is_cuda:
-            raise RuntimeError("tante_amd.UNO runs on the GPU only (no CPU fallback); move the model and its input to cuda")
+        gpu_only(x, "UNO")
         compute = resolve_compute(self.compute)
         adt = K.act_torch_dtype(compute)
         fc, fc0, fc1, fc2a, fc2b = self._linears(compute)
